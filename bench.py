@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- NES worker-evaluations/sec of the fused MI355X inner loop (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one NES generation of GTN_Master: noise draw, ONE fused-kernel launch evaluating this rank's share of the
@@ -601,6 +601,34 @@ def timed_generations(master, steps, warmup, barrier, world, use_events):
     return dt, kernel_ms
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_outputs(master):
+    """--dump-outputs: what the last timed generation handed its caller, as host arrays in float32 / float64.  `fitness` = the
+    gathered records of every worker (score_best, score_orig, mirrored-sampling sign, status), `theta` = the SE parameters after the
+    generation's NES update, `noise` = the generation's eps rows, `chain_*` = the fused inner loop's per-chain results on this rank."""
+    arrays = {"fitness": master._gathered, "theta": master.theta, "noise": master.eps}
+    for name in ("score", "stats", "status", "episode_test_mean", "episode_len", "final_returns"):
+        t = getattr(master.inner, name, None)
+        if t is not None:
+            arrays["chain_" + name] = t
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)    # counters and statuses: exact in float64
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    return out
+
+
+def write_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def run_rank(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -658,6 +686,7 @@ def run_rank(args):
         assert master.cfg.grad_chunk == cpu_grad_chunk      # CPU baseline and kernel use the same canonical summation order
     t_start = time.perf_counter()
     dt, kernel_ms = timed_generations(master, args.steps, args.warmup, barrier, world, use_events)
+    dumped = last_step_outputs(master) if args.dump_outputs and rank == 0 else None
     strong = None
     if world > 1:
         smaster, _ = build_master(POP, engine, bool(plumbing))
@@ -746,6 +775,8 @@ def run_rank(args):
             line["next_rows"] = next_rows
         if cpu is not None:
             line["cpu_baseline"] = cpu
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
         print(json.dumps(line), flush=True)
 
     if grouped:
@@ -766,7 +797,11 @@ def main():
                     help="run only the shard of BASELINE configs[N] (profiling aid; prints its record alone)")
     ap.add_argument("--team-size", type=int, default=0,
                     help="with --only-config: workgroups per chain (lenv_*_cfg::team_size; 0 = automatic, the shipped launch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed generation computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.only_config is not None:
         # profiling aid: one shard of one of the other BASELINE configurations, nothing else
         torch.cuda.set_device(0)

@@ -47,6 +47,26 @@ def test_bench_single_rank_line_shape():
         assert k in line
 
 
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs DIR: the last timed generation's arrays as DIR/<name>.npy in float32 / float64, 64 MB at most, identical for
+    identical arguments; one more timed step (--steps) moves theta one more NES update on."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b", tmp_path / "c"]
+    _run_bench(["--dump-outputs", str(dirs[0])], {})
+    _run_bench(["--dump-outputs", str(dirs[1])], {})
+    line = _run_bench(["--dump-outputs", str(dirs[2]), "--steps", "3"], {})
+    assert line["steps"] == 3
+    a, b, c = ({p.stem: np.load(p) for p in d.glob("*.npy")} for d in dirs)
+    assert {"fitness", "theta", "noise"} <= set(a) and set(a) == set(b) == set(c)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["fitness"].shape == (64, 4) and a["noise"].shape == (64, a["theta"].size)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert not np.array_equal(a["theta"], c["theta"])
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_driver_command_rehearsed_with_two_ranks_on_one_gpu():
