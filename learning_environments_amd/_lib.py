@@ -46,12 +46,20 @@ class DdqnCfg(C.Structure):
                 ("q_layer_norm", C.c_int32), ("test_mode", C.c_int32), ("early_out_virtual_diff", C.c_double)]
 
 
+def _tape_fields(keys):
+    """A tapes struct's fields: one (device pointer, row stride) pair per tape, in `keys` order."""
+    return [f for k in keys for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))]
+
+
+TAPE_KEYS = ("eps_uniform", "rand_action", "replay_idx", "train_reset", "test_reset")
+TD3_TAPE_KEYS = ("rand_action", "act_noise", "test_noise", "policy_noise", "replay_idx", "train_reset", "test_reset")
+TD3D_TAPE_KEYS = ("rand_action", "act_noise", "test_noise", "policy_noise", "gumbel_act", "gumbel_test", "gumbel_target", "gumbel_actor",
+                  "replay_idx", "train_reset", "test_reset")
+
+
 class Tapes(C.Structure):
-    _fields_ = [("eps_uniform", C.c_void_p), ("eps_uniform_stride", C.c_int64),
-                ("rand_action", C.c_void_p), ("rand_action_stride", C.c_int64),
-                ("replay_idx", C.c_void_p), ("replay_idx_stride", C.c_int64),
-                ("train_reset", C.c_void_p), ("train_reset_stride", C.c_int64),
-                ("test_reset", C.c_void_p), ("test_reset_stride", C.c_int64)]
+    keys = TAPE_KEYS
+    _fields_ = _tape_fields(TAPE_KEYS)
 
 
 class InnerOut(C.Structure):
@@ -103,10 +111,8 @@ class Td3Cfg(C.Structure):
 
 
 class Td3Tapes(C.Structure):
-    _fields_ = [("rand_action", C.c_void_p), ("rand_action_stride", C.c_int64), ("act_noise", C.c_void_p), ("act_noise_stride", C.c_int64),
-                ("test_noise", C.c_void_p), ("test_noise_stride", C.c_int64), ("policy_noise", C.c_void_p), ("policy_noise_stride", C.c_int64),
-                ("replay_idx", C.c_void_p), ("replay_idx_stride", C.c_int64), ("train_reset", C.c_void_p), ("train_reset_stride", C.c_int64),
-                ("test_reset", C.c_void_p), ("test_reset_stride", C.c_int64)]
+    keys = TD3_TAPE_KEYS
+    _fields_ = _tape_fields(TD3_TAPE_KEYS)
 
 
 class Td3dCfg(C.Structure):
@@ -123,12 +129,9 @@ class Td3dCfg(C.Structure):
                 ("step_budget", C.c_int64), ("se_layer_norm", C.c_int32), ("test_mode", C.c_int32), ("early_out_virtual_diff", C.c_double)]
 
 
-TD3D_TAPE_KEYS = ("rand_action", "act_noise", "test_noise", "policy_noise", "gumbel_act", "gumbel_test", "gumbel_target", "gumbel_actor",
-                  "replay_idx", "train_reset", "test_reset")
-
-
 class Td3dTapes(C.Structure):
-    _fields_ = [f for k in TD3D_TAPE_KEYS for f in ((k, C.c_void_p), (k + "_stride", C.c_int64))]
+    keys = TD3D_TAPE_KEYS
+    _fields_ = _tape_fields(TD3D_TAPE_KEYS)
 
 
 class Td3Out(C.Structure):
@@ -140,13 +143,72 @@ class Td3Out(C.Structure):
 # lenv_struct_size(which) order (include/lenv_hip.h)
 ABI_STRUCTS = [MlpDesc, DdqnCfg, QlCfg, Td3Cfg, Td3dCfg, Tapes, InnerOut, QlOut, Td3Tapes, Td3Out, Td3dTapes, ChainHp, IcmIo]
 
-EXPORTS = ["lenv_abi_version", "lenv_error_string", "lenv_mlp_num_params", "lenv_se_step_population",
-           "lenv_qnet_td_forward", "lenv_ddqn_se_workspace_bytes", "lenv_ddqn_se_lds_bytes", "lenv_ddqn_se_forward_split", "lenv_ddqn_se_team_size", "lenv_ddqn_se_inner_loop",
-           "lenv_chain_key", "lenv_nes_worker_best", "lenv_nes_rank_update", "lenv_real_env_reset", "lenv_real_env_step", "lenv_ql_rn_inner_loop", "lenv_rn_shape_population", "lenv_dueling_se_workspace_bytes",
-           "lenv_dueling_num_params", "lenv_dueling_se_inner_loop", "lenv_dueling_se_inner_loop_hp", "lenv_dueling_agent_init_hp", "lenv_rng_unit", "lenv_td3_rn_inner_loop_hp", "lenv_td3_agent_init_hp", "lenv_icm_num_params", "lenv_dueling_se_inner_loop_icm", "lenv_chain_uniform_init", "lenv_td3_icm_num_params", "lenv_td3_rn_inner_loop_icm", "lenv_td3_rn_workspace_bytes", "lenv_td3_num_params",
-           "lenv_td3_rn_inner_loop", "lenv_mlp_forward", "lenv_cheetah_standin_reset", "lenv_cheetah_standin_step", "lenv_cont_env_reset", "lenv_cont_env_step",
-           "lenv_rn_num_params", "lenv_rn_shape_rows", "lenv_nes_worker_best_multi", "lenv_nes_draw", "lenv_nes_status_fold", "lenv_nes_draw_dev", "lenv_nes_rank_update_keep",
-           "lenv_td3d_workspace_bytes", "lenv_td3d_num_params", "lenv_td3d_se_num_params", "lenv_td3d_inner_loop", "lenv_td3d_agent_init", "lenv_td3_rn_team_size", "lenv_dueling_team_size", "lenv_struct_size"]
+_vp, _i32, _i64, _f64, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.POINTER
+# what follows the cfg (and hp / icm) of an inner-loop launch: theta, eps, worker, sign, agent_init, rng_keys, tapes, chains,
+# workspace, workspace_bytes, out, stream
+_DDQN_RUN = [_vp] * 6 + [_P(Tapes), _i64, _vp, C.c_size_t, _P(InnerOut), _vp]
+_TD3_RUN = [_vp] * 6 + [_P(Td3Tapes), _i64, _vp, C.c_size_t, _P(Td3Out), _vp]
+_NES_DRAW_TAIL = [_i64, _i64, C.c_float, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp]
+_NES_RANK_HEAD = [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _f64, _i32, _f64, _vp]
+
+# name -> (restype, argtypes) of every C-ABI entry point the package binds (include/lenv_hip.h)
+SIGNATURES = {
+    "lenv_abi_version": (C.c_int, []),
+    "lenv_error_string": (C.c_char_p, [C.c_int]),
+    "lenv_struct_size": (_i64, [_i32]),
+    "lenv_mlp_num_params": (_i64, [_P(MlpDesc)]),
+    "lenv_mlp_forward": (C.c_int, [_P(MlpDesc), _vp, _vp, _i64, _vp, _vp]),
+    "lenv_se_step_population": (C.c_int, [_P(MlpDesc)] * 3 + [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lenv_qnet_td_forward": (C.c_int, [_P(MlpDesc), _vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),
+    "lenv_chain_key": (C.c_uint64, [C.c_uint64] * 4),
+    "lenv_rng_unit": (_f64, [C.c_uint64, C.c_uint32, C.c_uint64]),
+    "lenv_chain_uniform_init": (C.c_int, [_vp, _i64, C.c_uint32, _i64, _vp, _vp, _vp]),
+    "lenv_ddqn_se_workspace_bytes": (C.c_size_t, [_P(DdqnCfg), _i64]),
+    "lenv_ddqn_se_lds_bytes": (_i64, [_P(DdqnCfg)]),
+    "lenv_ddqn_se_team_size": (C.c_int, [_P(DdqnCfg), _i64]),
+    "lenv_ddqn_se_forward_split": (C.c_int, [_P(DdqnCfg), _P(_i32), _P(_i32)]),
+    "lenv_ddqn_se_inner_loop": (C.c_int, [_P(DdqnCfg)] + _DDQN_RUN),
+    "lenv_dueling_se_workspace_bytes": (C.c_size_t, [_P(DdqnCfg), _i64]),
+    "lenv_dueling_num_params": (_i64, [_P(DdqnCfg)]),
+    "lenv_dueling_team_size": (C.c_int, [_P(DdqnCfg), _i64]),
+    "lenv_dueling_se_inner_loop": (C.c_int, [_P(DdqnCfg)] + _DDQN_RUN),
+    "lenv_dueling_se_inner_loop_hp": (C.c_int, [_P(DdqnCfg), _P(ChainHp)] + _DDQN_RUN),
+    "lenv_dueling_se_inner_loop_icm": (C.c_int, [_P(DdqnCfg), _P(ChainHp), _P(IcmIo)] + _DDQN_RUN),
+    "lenv_dueling_agent_init_hp": (C.c_int, [_P(DdqnCfg), _P(ChainHp), _vp, _i64, _vp, _vp]),
+    "lenv_icm_num_params": (_i64, [_P(DdqnCfg)]),
+    "lenv_real_env_reset": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "lenv_real_env_step": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lenv_cheetah_standin_reset": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "lenv_cheetah_standin_step": (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lenv_cont_env_reset": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "lenv_cont_env_step": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lenv_ql_rn_inner_loop": (C.c_int, [_P(QlCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(Tapes), _i64, _P(QlOut), _vp]),
+    "lenv_rn_shape_population": (C.c_int, [_P(QlCfg), _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "lenv_rn_num_params": (_i64, [_i32] * 5),
+    "lenv_rn_shape_rows": (C.c_int, [_i32, _P(MlpDesc), _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "lenv_td3_rn_workspace_bytes": (C.c_size_t, [_P(Td3Cfg), _i64]),
+    "lenv_td3_num_params": (_i64, [_P(Td3Cfg), _P(_i64), _P(_i64)]),
+    "lenv_td3_rn_team_size": (C.c_int, [_P(Td3Cfg), _i64]),
+    "lenv_td3_rn_inner_loop": (C.c_int, [_P(Td3Cfg)] + _TD3_RUN),
+    "lenv_td3_rn_inner_loop_hp": (C.c_int, [_P(Td3Cfg), _P(ChainHp)] + _TD3_RUN),
+    "lenv_td3_rn_inner_loop_icm": (C.c_int, [_P(Td3Cfg), _P(ChainHp), _P(IcmIo)] + _TD3_RUN),
+    "lenv_td3_agent_init_hp": (C.c_int, [_P(Td3Cfg), _P(ChainHp), _vp, _i64, _vp, _vp]),
+    "lenv_td3_icm_num_params": (_i64, [_P(Td3Cfg)]),
+    "lenv_td3d_workspace_bytes": (C.c_size_t, [_P(Td3dCfg), _i64]),
+    "lenv_td3d_num_params": (_i64, [_P(Td3dCfg), _P(_i64), _P(_i64)]),
+    "lenv_td3d_se_num_params": (_i64, [_P(Td3dCfg)]),
+    "lenv_td3d_inner_loop": (C.c_int, [_P(Td3dCfg), _P(ChainHp), _vp, _vp, _vp, _vp, _vp, _vp, _P(Td3dTapes), _i64, _vp, C.c_size_t,
+                                       _P(Td3Out), _vp]),
+    "lenv_td3d_agent_init": (C.c_int, [_P(Td3dCfg), _P(ChainHp), _vp, _i64, _vp, _vp]),
+    "lenv_nes_worker_best": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
+    "lenv_nes_worker_best_multi": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "lenv_nes_draw": (C.c_int, [C.c_uint64, C.c_uint64] + _NES_DRAW_TAIL),
+    "lenv_nes_draw_dev": (C.c_int, [C.c_uint64, _vp] + _NES_DRAW_TAIL),
+    "lenv_nes_status_fold": (C.c_int, [_vp, _i64, _vp, _i64, _vp]),
+    "lenv_nes_rank_update": (C.c_int, _NES_RANK_HEAD + [_vp]),
+    "lenv_nes_rank_update_keep": (C.c_int, _NES_RANK_HEAD + [_vp, _vp, _vp]),
+}
+EXPORTS = list(SIGNATURES)
 
 
 def build(force=False):
@@ -168,123 +230,11 @@ def lib():
             raise LenvError("liblenv_hip.so is missing (%s). Build it with `python -c 'import __graft_entry__ as g; "
                             "g.build()'` or `make -C learning_environments_amd/csrc`; there is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        L.lenv_abi_version.restype = C.c_int
-        L.lenv_error_string.restype = C.c_char_p
-        L.lenv_error_string.argtypes = [C.c_int]
-        L.lenv_mlp_num_params.restype = C.c_int64
-        L.lenv_mlp_num_params.argtypes = [C.POINTER(MlpDesc)]
-        L.lenv_chain_key.restype = C.c_uint64
-        L.lenv_chain_key.argtypes = [C.c_uint64] * 4
-        L.lenv_ddqn_se_workspace_bytes.restype = C.c_size_t
-        L.lenv_ddqn_se_workspace_bytes.argtypes = [C.POINTER(DdqnCfg), C.c_int64]
-        vp = C.c_void_p
-        L.lenv_se_step_population.restype = C.c_int
-        L.lenv_se_step_population.argtypes = [C.POINTER(MlpDesc)] * 3 + [vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp]
-        L.lenv_qnet_td_forward.restype = C.c_int
-        L.lenv_qnet_td_forward.argtypes = [C.POINTER(MlpDesc), vp, vp, vp, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32,
-                                           C.c_double, vp, vp, vp]
-        L.lenv_ddqn_se_inner_loop.restype = C.c_int
-        L.lenv_ddqn_se_inner_loop.argtypes = [C.POINTER(DdqnCfg), vp, vp, vp, vp, vp, vp, C.POINTER(Tapes), C.c_int64, vp,
-                                              C.c_size_t, C.POINTER(InnerOut), vp]
-        L.lenv_ddqn_se_lds_bytes.restype = C.c_int64
-        L.lenv_ddqn_se_lds_bytes.argtypes = [C.POINTER(DdqnCfg)]
-        L.lenv_ddqn_se_team_size.restype = C.c_int
-        L.lenv_ddqn_se_team_size.argtypes = [C.POINTER(DdqnCfg), C.c_int64]
-        L.lenv_ddqn_se_forward_split.restype = C.c_int
-        L.lenv_ddqn_se_forward_split.argtypes = [C.POINTER(DdqnCfg), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.lenv_real_env_reset.restype = C.c_int
-        L.lenv_real_env_reset.argtypes = [C.c_int32, vp, vp, C.c_int64, vp, vp, vp, vp]
-        L.lenv_real_env_step.restype = C.c_int
-        L.lenv_real_env_step.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
-        L.lenv_ql_rn_inner_loop.restype = C.c_int
-        L.lenv_ql_rn_inner_loop.argtypes = [C.POINTER(QlCfg), vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Tapes), C.c_int64,
-                                            C.POINTER(QlOut), vp]
-        L.lenv_dueling_se_workspace_bytes.restype = C.c_size_t
-        L.lenv_dueling_se_workspace_bytes.argtypes = [C.POINTER(DdqnCfg), C.c_int64]
-        L.lenv_dueling_num_params.restype = C.c_int64
-        L.lenv_dueling_num_params.argtypes = [C.POINTER(DdqnCfg)]
-        L.lenv_dueling_se_inner_loop.restype = C.c_int
-        L.lenv_dueling_se_inner_loop.argtypes = L.lenv_ddqn_se_inner_loop.argtypes
-        L.lenv_dueling_se_inner_loop_hp.restype = C.c_int
-        L.lenv_dueling_se_inner_loop_hp.argtypes = [L.lenv_ddqn_se_inner_loop.argtypes[0], C.POINTER(ChainHp)] + list(L.lenv_ddqn_se_inner_loop.argtypes[1:])
-        L.lenv_dueling_agent_init_hp.restype = C.c_int
-        L.lenv_dueling_agent_init_hp.argtypes = [C.POINTER(DdqnCfg), C.POINTER(ChainHp), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        L.lenv_icm_num_params.restype = C.c_int64
-        L.lenv_icm_num_params.argtypes = [C.POINTER(DdqnCfg)]
-        L.lenv_dueling_se_inner_loop_icm.restype = C.c_int
-        L.lenv_dueling_se_inner_loop_icm.argtypes = [L.lenv_ddqn_se_inner_loop.argtypes[0], C.POINTER(ChainHp), C.POINTER(IcmIo)] + list(L.lenv_ddqn_se_inner_loop.argtypes[1:])
-        L.lenv_chain_uniform_init.restype = C.c_int
-        L.lenv_chain_uniform_init.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.lenv_rng_unit.restype = C.c_double
-        L.lenv_rng_unit.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64]
-        L.lenv_td3_rn_workspace_bytes.restype = C.c_size_t
-        L.lenv_td3_rn_workspace_bytes.argtypes = [C.POINTER(Td3Cfg), C.c_int64]
-        L.lenv_td3_num_params.restype = C.c_int64
-        L.lenv_td3_num_params.argtypes = [C.POINTER(Td3Cfg), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.lenv_td3_rn_inner_loop.restype = C.c_int
-        L.lenv_td3_rn_inner_loop.argtypes = [C.POINTER(Td3Cfg), vp, vp, vp, vp, vp, vp, C.POINTER(Td3Tapes), C.c_int64, vp, C.c_size_t,
-                                             C.POINTER(Td3Out), vp]
-        L.lenv_td3_rn_inner_loop_hp.restype = C.c_int
-        L.lenv_td3_rn_inner_loop_hp.argtypes = [C.POINTER(Td3Cfg), C.POINTER(ChainHp)] + list(L.lenv_td3_rn_inner_loop.argtypes[1:])
-        L.lenv_td3_icm_num_params.restype = C.c_int64
-        L.lenv_td3_icm_num_params.argtypes = [C.POINTER(Td3Cfg)]
-        L.lenv_td3_rn_inner_loop_icm.restype = C.c_int
-        L.lenv_td3_rn_inner_loop_icm.argtypes = [C.POINTER(Td3Cfg), C.POINTER(ChainHp), C.POINTER(IcmIo)] + list(L.lenv_td3_rn_inner_loop.argtypes[1:])
-        L.lenv_td3_agent_init_hp.restype = C.c_int
-        L.lenv_td3_agent_init_hp.argtypes = [C.POINTER(Td3Cfg), C.POINTER(ChainHp), vp, C.c_int64, vp, vp]
-        L.lenv_rn_num_params.restype = C.c_int64
-        L.lenv_rn_num_params.argtypes = [C.c_int32] * 5
-        L.lenv_rn_shape_rows.restype = C.c_int
-        L.lenv_rn_shape_rows.argtypes = [C.c_int32, C.POINTER(MlpDesc), C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, C.c_int64, vp, vp]
-        L.lenv_mlp_forward.restype = C.c_int
-        L.lenv_mlp_forward.argtypes = [C.POINTER(MlpDesc), vp, vp, C.c_int64, vp, vp]
-        L.lenv_cheetah_standin_reset.restype = C.c_int
-        L.lenv_cheetah_standin_reset.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp]
-        L.lenv_cheetah_standin_step.restype = C.c_int
-        L.lenv_cheetah_standin_step.argtypes = [C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
-        L.lenv_cont_env_reset.restype = C.c_int
-        L.lenv_cont_env_reset.argtypes = [C.c_int32, vp, vp, C.c_int64, vp, vp, vp, vp]
-        L.lenv_cont_env_step.restype = C.c_int
-        L.lenv_cont_env_step.argtypes = [C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
-        L.lenv_rn_shape_population.restype = C.c_int
-        L.lenv_rn_shape_population.argtypes = [C.POINTER(QlCfg), vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
-        L.lenv_nes_worker_best_multi.restype = C.c_int
-        L.lenv_nes_worker_best_multi.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp]
-        L.lenv_nes_worker_best.restype = C.c_int
-        L.lenv_nes_worker_best.argtypes = [vp, C.c_int64, C.c_int32, vp, vp]
-        L.lenv_nes_rank_update.restype = C.c_int
-        L.lenv_nes_rank_update.argtypes = [C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_double, C.c_int32,
-                                           C.c_double, vp, vp]
-        L.lenv_nes_draw.restype = C.c_int
-        L.lenv_nes_draw.argtypes = [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_float, vp, C.c_int64, C.c_int32, C.c_int64,
-                                    C.c_int64, vp, vp, vp, vp]
-        L.lenv_nes_status_fold.restype = C.c_int
-        L.lenv_nes_status_fold.argtypes = [vp, C.c_int64, vp, C.c_int64, vp]
-        L.lenv_nes_draw_dev.restype = C.c_int
-        L.lenv_nes_draw_dev.argtypes = [C.c_uint64, vp, C.c_int64, C.c_int64, C.c_float, vp, C.c_int64, C.c_int32, C.c_int64,
-                                        C.c_int64, vp, vp, vp, vp]
-        L.lenv_nes_rank_update_keep.restype = C.c_int
-        L.lenv_nes_rank_update_keep.argtypes = [C.c_int32, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_double, C.c_int32,
-                                                C.c_double, vp, vp, vp, vp]
-        L.lenv_dueling_team_size.restype = C.c_int
-        L.lenv_dueling_team_size.argtypes = [C.POINTER(DdqnCfg), C.c_int64]
-        L.lenv_td3_rn_team_size.restype = C.c_int
-        L.lenv_td3_rn_team_size.argtypes = [C.POINTER(Td3Cfg), C.c_int64]
-        L.lenv_td3d_workspace_bytes.restype = C.c_size_t
-        L.lenv_td3d_workspace_bytes.argtypes = [C.POINTER(Td3dCfg), C.c_int64]
-        L.lenv_td3d_num_params.restype = C.c_int64
-        L.lenv_td3d_num_params.argtypes = [C.POINTER(Td3dCfg), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.lenv_td3d_se_num_params.restype = C.c_int64
-        L.lenv_td3d_se_num_params.argtypes = [C.POINTER(Td3dCfg)]
-        L.lenv_td3d_inner_loop.restype = C.c_int
-        L.lenv_td3d_inner_loop.argtypes = [C.POINTER(Td3dCfg), C.POINTER(ChainHp), vp, vp, vp, vp, vp, vp, C.POINTER(Td3dTapes), C.c_int64, vp,
-                                           C.c_size_t, C.POINTER(Td3Out), vp]
-        L.lenv_td3d_agent_init.restype = C.c_int
-        L.lenv_td3d_agent_init.argtypes = [C.POINTER(Td3dCfg), C.POINTER(ChainHp), vp, C.c_int64, vp, vp]
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if L.lenv_abi_version() != 7:
             raise LenvError("liblenv_hip.so ABI version mismatch")
-        L.lenv_struct_size.restype = C.c_int64
-        L.lenv_struct_size.argtypes = [C.c_int32]
         for which, cls in enumerate(ABI_STRUCTS):     # the ctypes mirrors must have the library's layout
             if L.lenv_struct_size(which) != C.sizeof(cls):
                 raise LenvError("ctypes mirror of %s has %d bytes, the library's struct %d" % (cls.__name__, C.sizeof(cls), L.lenv_struct_size(which)))

@@ -10,88 +10,121 @@ combination owns one fused kernel:
     TD3  on a RewardEnv over the HalfCheetah stand-in -> lenv_td3_rn_inner_loop (BASELINE config 5)
     TD3_discrete_vary on a VirtualEnv (CartPole / Acrobot / MountainCar) -> lenv_td3d_inner_loop
 Anything else raises NotImplementedError, like the reference does for unknown agents."""
+import copy
+
 import numpy as np
 import torch
 
 from ..config import (TABULAR_AGENTS, TD3_DISCRETE_ENVS, agent_layer_dims, agent_layer_norm_slice, ddqn_cfg_from_config, icm_layer_dims, ql_cfg_from_config,
                       td3_cfg_from_config, td3_layer_dims, td3_layer_norm_slices, td3d_cfg_from_config)
-from .nes_common import chain_keys, fresh_agent_init, linear_init_bounds, set_layer_norm_init, with_layer_norm_block
+from . import vary
+from .nes_common import linear_init_bounds, set_layer_norm_init, with_layer_norm_block
 
 
-class DdqnSeTask(object):
+def _device_bounds(engine, layer_dims, ln_slice=None):
+    """nn.Linear default-init bounds of a flat parameter vector (LayerNorm blocks at ln_slice: bound 0) on the engine's device."""
+    return torch.from_numpy(with_layer_norm_block(linear_init_bounds(layer_dims), ln_slice)).to(engine.device)
+
+
+def _max_config(config, section):
+    """A copy of config whose agent section carries the largest batch_size / hidden_size / hidden_layer agents/vary.py can draw:
+    the launch is sized for it (workspace / LDS / row strides)."""
+    bd = vary.hp_bounds(config["agents"][section])
+    big = copy.deepcopy(config)
+    big["agents"][section].update(batch_size=bd["batch_size"][1], hidden_size=bd["hidden_size"][1], hidden_layer=bd["hidden_layer"][1])
+    return big
+
+
+def _icm_bounds(engine, cfg):
+    """ICM agents ("ddqn_icm", "td3_icm", ...: the agent carries an Intrinsic Curiosity Module, agents/DDQN.py:40-58): the bounds of the
+    fresh ICM (nn.Linear default init) every chain draws from its own counter-RNG stream on the GPU; None without one."""
+    return _device_bounds(engine, icm_layer_dims(cfg)) if engine.name == "hip" and cfg.icm_enabled else None
+
+
+class _FixedShapeAgents(object):
+    """Every chain at cfg's shapes: a fresh agent from the generation's draw with agent_bounds (use_layer_norm: the LayerNorm blocks at
+    ln_slice get weight 1 / bias 0)."""
+
+    def _init_bounds(self, layer_dims, ln_slice):
+        self.ln_slice = ln_slice
+        self.agent_bounds = _device_bounds(self.engine, layer_dims, ln_slice)
+        self.icm_bounds = _icm_bounds(self.engine, self.cfg)
+
+    def _fresh_agents(self, inner, keys_t, agent_init):
+        if self.icm_bounds is not None:
+            inner.draw_icm_init(keys_t, self.icm_bounds)
+        set_layer_norm_init(agent_init, self.ln_slice)
+
+
+class _VaryAgents(object):
+    """The *_vary tasks: every chain draws its own lr / batch_size / hidden_size / hidden_layer (agents/vary.py) from its key and gets a
+    fresh agent at those shapes inside scores() (draw_hp is host work between the kernels: such a task is not captured into a graph,
+    GTN_master.py)."""
+    icm_bounds = None
+
+    def _init_vary(self, base):
+        self.base = base                  # the config's agent section the draws start from
+        self.agent_bounds = None
+        self.last_hp = None
+        self.fixed_hp = None
+
+    def draw_hp(self, keys):
+        if self.fixed_hp is not None:     # a recorded draw replayed (parity tests against the reference's runs)
+            return list(self.fixed_hp)
+        return [vary.vary_hyperparameters(self.base, vary.chain_units(k)) for k in keys]
+
+    def _fresh_agents(self, inner, keys_t, draw_hp=True):
+        # the draws are a host function of the chain keys (ConfigSpace's role in the reference); reading the keys back waits only
+        # for the generation's draw kernel
+        if draw_hp:
+            hp = self.last_hp = self.draw_hp(keys_t.cpu().numpy().view(np.uint64))
+            inner.set_hp([h["lr"] for h in hp], [h["batch_size"] for h in hp], [h["hidden_size"] for h in hp],
+                         [h["hidden_layer"] for h in hp])
+        inner.draw_agent_init(keys_t)
+        if self.icm_bounds is not None:
+            inner.draw_icm_init(keys_t, self.icm_bounds)
+
+
+class DdqnSeTask(_FixedShapeAgents):
     name = "ddqn_se"
 
     def __init__(self, config, engine, test_mode=0):
         self.engine = engine
         self.cfg = ddqn_cfg_from_config(config, test_mode=test_mode) if engine.name == "hip" else engine.cfg_from_config(config)
-        dims = agent_layer_dims(self.cfg)
-        self.ln_slice = agent_layer_norm_slice(self.cfg)      # use_layer_norm: the shared LayerNorm's block in the flat parameter vector
-        self.agent_bounds = torch.from_numpy(with_layer_norm_block(linear_init_bounds(dims), self.ln_slice)).to(engine.device)
-        # "ddqn_icm" / "duelingddqn_icm": the agent carries an Intrinsic Curiosity Module (agents/DDQN.py:40-58); every chain
-        # gets a fresh one (nn.Linear default init), drawn from its own counter-RNG stream
-        self.icm_bounds = None
-        if engine.name == "hip" and self.cfg.icm_enabled:
-            self.icm_bounds = torch.from_numpy(linear_init_bounds(icm_layer_dims(self.cfg))).to(engine.device)
+        self._init_bounds(agent_layer_dims(self.cfg), agent_layer_norm_slice(self.cfg))
 
     def make_inner(self, chains, want_episode_stats=True):
         return self.engine.make_inner(self.cfg, chains, want_episode_stats=want_episode_stats)
 
     def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
-        if self.icm_bounds is not None:
-            inner.draw_icm_init(keys_t, self.icm_bounds)
-        set_layer_norm_init(agent_init, self.ln_slice)
+        self._fresh_agents(inner, keys_t, agent_init)
         return self.engine.inner_scores(inner, theta, eps, chain_worker, chain_sign, agent_init, keys_t)
 
     def needs_agent_init(self):
         return True
 
 
-class DdqnVaryTask(object):
+class DdqnVaryTask(_VaryAgents):
     """DDQN_vary / DuelingDDQN_vary on a VirtualEnv (agents/DDQN_vary.py, agents/DuelingDDQN_vary.py): every chain draws its
     own lr / batch_size / hidden_size / hidden_layer (agents/vary.py) and the whole heterogeneous population still runs as ONE
     launch of the GEMM-tiled kernel (per-chain hyper-parameter arrays, workspace sized for the largest draw)."""
     name = "ddqn_vary_se"
 
     def __init__(self, config, engine, test_mode=0):
-        import copy
-        from . import vary
         self.engine = engine              # HipNesEngine, or the test suite's oracle-backed stand-in (CPU tensors)
         self.agent_key = config["agents"]["gtn"]["agent_name"].lower()[:-5]
         if self.agent_key.endswith("_icm"):               # "ddqn_icm_vary": DDQN_vary(icm=True), agents/agent_utils.py:43-44
             self.agent_key = self.agent_key[:-4]
-        self.base = config["agents"][self.agent_key]
-        bd = vary.hp_bounds(self.base)
-        big = copy.deepcopy(config)
-        big["agents"][self.agent_key].update(batch_size=bd["batch_size"][1], hidden_size=bd["hidden_size"][1],
-                                             hidden_layer=bd["hidden_layer"][1])
-        self.cfg = ddqn_cfg_from_config(big, test_mode=test_mode)      # the maxima: workspace / LDS / row strides
+        self.cfg = ddqn_cfg_from_config(_max_config(config, self.agent_key), test_mode=test_mode)
         self.cfg.grad_chunk = 0                           # one sequential batch gradient (GEMM-tiled kernel)
-        self.agent_bounds = None
-        self.last_hp = None
-        self.fixed_hp = None
-        self.icm_bounds = None
-        if engine.name == "hip" and self.cfg.icm_enabled:
-            self.icm_bounds = torch.from_numpy(linear_init_bounds(icm_layer_dims(self.cfg))).to(engine.device)
+        self._init_vary(config["agents"][self.agent_key])
+        self.icm_bounds = _icm_bounds(engine, self.cfg)
 
     def make_inner(self, chains, want_episode_stats=True):
         return self.engine.make_inner(self.cfg, chains, want_episode_stats=want_episode_stats, vary=True)
 
-    def draw_hp(self, keys):
-        from . import vary
-        if self.fixed_hp is not None:     # a recorded draw replayed (parity tests against the reference's runs)
-            return list(self.fixed_hp)
-        return [vary.vary_hyperparameters(self.base, vary.chain_units(k)) for k in keys]
-
     def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
-        # the draws are a host function of the chain keys (ConfigSpace's role in the reference); reading the keys back
-        # waits only for the generation's draw kernel
-        keys = keys_t.cpu().numpy().view(np.uint64)
-        hp = self.last_hp = self.draw_hp(keys)
-        inner.set_hp([h["lr"] for h in hp], [h["batch_size"] for h in hp], [h["hidden_size"] for h in hp],
-                     [h["hidden_layer"] for h in hp])
-        inner.draw_agent_init(keys_t)
-        if self.icm_bounds is not None:
-            inner.draw_icm_init(keys_t, self.icm_bounds)
+        self._fresh_agents(inner, keys_t)
         return self.engine.inner_scores(inner, theta, eps, chain_worker, chain_sign, None, keys_t)
 
     def needs_agent_init(self):
@@ -117,78 +150,51 @@ class QlRnTask(object):
         return False          # a fresh QL agent is an all-zero table (QL.py:25)
 
 
-class Td3RnTask(object):
+class Td3RnTask(_FixedShapeAgents):
     name = "td3_rn"
 
     def __init__(self, config, engine, test_mode=0):
         self.engine = engine
         self.cfg = td3_cfg_from_config(config, test_mode=test_mode)
-        self.ln_slice = td3_layer_norm_slices(self.cfg)       # use_layer_norm: the three nets' LayerNorm blocks in the flat parameter vector
-        self.agent_bounds = torch.from_numpy(with_layer_norm_block(linear_init_bounds(td3_layer_dims(self.cfg)), self.ln_slice)).to(engine.device)
-        self.icm_bounds = None                    # "td3_icm": TD3(icm=True), a fresh ICM per chain
-        if self.cfg.icm_enabled:
-            self.icm_bounds = torch.from_numpy(linear_init_bounds(icm_layer_dims(self.cfg))).to(engine.device)
+        # use_layer_norm: the three nets' LayerNorm blocks in the flat parameter vector; "td3_icm": TD3(icm=True), a fresh ICM per chain
+        self._init_bounds(td3_layer_dims(self.cfg), td3_layer_norm_slices(self.cfg))
 
     def make_inner(self, chains, want_episode_stats=False):
         return self.engine.make_inner_td3(self.cfg, chains, want_episode_stats=want_episode_stats)
 
     def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
-        if self.icm_bounds is not None:
-            inner.draw_icm_init(keys_t, self.icm_bounds)
-        set_layer_norm_init(agent_init, self.ln_slice)
+        self._fresh_agents(inner, keys_t, agent_init)
         return self.engine.inner_scores_td3(inner, theta, eps, chain_worker, chain_sign, agent_init, keys_t)
 
     def needs_agent_init(self):
         return True
 
 
-class Td3VaryTask(object):
+class Td3VaryTask(_VaryAgents):
     """TD3_vary on the stand-in RewardEnv (agents/TD3_vary.py:24-58): per-chain lr / batch_size / hidden_size / hidden_layer in
     one launch of the TD3 kernel (lenv_td3_rn_inner_loop_hp), like DdqnVaryTask."""
     name = "td3_vary_rn"
 
     def __init__(self, config, engine, test_mode=0):
-        import copy
-        from . import vary
         if engine.name != "hip":
             raise NotImplementedError("the *_vary agents need the HIP engine")
         self.engine = engine
-        self.base = config["agents"]["td3"]
-        bd = vary.hp_bounds(self.base)
-        big = copy.deepcopy(config)
-        big["agents"]["td3"].update(batch_size=bd["batch_size"][1], hidden_size=bd["hidden_size"][1], hidden_layer=bd["hidden_layer"][1])
-        self.cfg = td3_cfg_from_config(big, test_mode=test_mode)
-        self.agent_bounds = None
-        self.last_hp = None
-        self.fixed_hp = None
-        self.icm_bounds = None
-        if self.cfg.icm_enabled:
-            self.icm_bounds = torch.from_numpy(linear_init_bounds(icm_layer_dims(self.cfg))).to(engine.device)
+        self.cfg = td3_cfg_from_config(_max_config(config, "td3"), test_mode=test_mode)
+        self._init_vary(config["agents"]["td3"])
+        self.icm_bounds = _icm_bounds(engine, self.cfg)
 
     def make_inner(self, chains, want_episode_stats=False):
         return self.engine.make_inner_td3(self.cfg, chains, want_episode_stats=want_episode_stats, vary=True)
 
-    def draw_hp(self, keys):
-        from . import vary
-        if self.fixed_hp is not None:     # a recorded draw replayed (parity tests against the reference's runs)
-            return list(self.fixed_hp)
-        return [vary.vary_hyperparameters(self.base, vary.chain_units(k)) for k in keys]
-
     def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
-        keys = keys_t.cpu().numpy().view(np.uint64)
-        hp = self.last_hp = self.draw_hp(keys)
-        inner.set_hp([h["lr"] for h in hp], [h["batch_size"] for h in hp], [h["hidden_size"] for h in hp],
-                     [h["hidden_layer"] for h in hp])
-        inner.draw_agent_init(keys_t)
-        if self.icm_bounds is not None:
-            inner.draw_icm_init(keys_t, self.icm_bounds)
+        self._fresh_agents(inner, keys_t)
         return self.engine.inner_scores_td3(inner, theta, eps, chain_worker, chain_sign, None, keys_t)
 
     def needs_agent_init(self):
         return False
 
 
-class Td3DiscreteTask(object):
+class Td3DiscreteTask(_VaryAgents):
     """TD3_discrete_vary on a VirtualEnv (agents/TD3_discrete_vary.py): one launch of lenv_td3d_inner_loop per generation.  With
     vary_hp (:21-26,119-157) every chain draws its own lr / batch_size / hidden_size / hidden_layer (agents/vary.py) and the launch is
     sized for the largest possible draw, like Td3VaryTask.  The fresh agents (nn.Linear default init, LayerNorm 1 / 0) are drawn on
@@ -196,40 +202,19 @@ class Td3DiscreteTask(object):
     name = "td3_discrete_se"
 
     def __init__(self, config, engine, test_mode=0):
-        import copy
-        from . import vary
         if engine.name != "hip":
             raise NotImplementedError("TD3_discrete_vary needs the HIP engine")
         self.engine = engine
-        self.base = config["agents"]["td3_discrete_vary"]
-        self.vary = bool(self.base["vary_hp"])
-        big = config
-        if self.vary:
-            bd = vary.hp_bounds(self.base)
-            big = copy.deepcopy(config)
-            big["agents"]["td3_discrete_vary"].update(batch_size=bd["batch_size"][1], hidden_size=bd["hidden_size"][1],
-                                                      hidden_layer=bd["hidden_layer"][1])
-        self.cfg = td3d_cfg_from_config(big, test_mode=test_mode)
-        self.agent_bounds = None
-        self.last_hp = None
-        self.fixed_hp = None
+        base = config["agents"]["td3_discrete_vary"]
+        self.vary = bool(base["vary_hp"])
+        self.cfg = td3d_cfg_from_config(_max_config(config, "td3_discrete_vary") if self.vary else config, test_mode=test_mode)
+        self._init_vary(base)
 
     def make_inner(self, chains, want_episode_stats=False):
         return self.engine.make_inner_td3d(self.cfg, chains, want_episode_stats=want_episode_stats, vary=self.vary)
 
-    def draw_hp(self, keys):
-        from . import vary
-        if self.fixed_hp is not None:     # a recorded draw replayed (parity tests against the reference's runs)
-            return list(self.fixed_hp)
-        return [vary.vary_hyperparameters(self.base, vary.chain_units(k)) for k in keys]
-
     def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
-        if self.vary:
-            keys = keys_t.cpu().numpy().view(np.uint64)
-            hp = self.last_hp = self.draw_hp(keys)
-            inner.set_hp([h["lr"] for h in hp], [h["batch_size"] for h in hp], [h["hidden_size"] for h in hp],
-                         [h["hidden_layer"] for h in hp])
-        inner.draw_agent_init(keys_t)
+        self._fresh_agents(inner, keys_t, draw_hp=self.vary)
         return self.engine.inner_scores_td3(inner, theta, eps, chain_worker, chain_sign, None, keys_t)
 
     def needs_agent_init(self):

@@ -1748,24 +1748,36 @@ static int64_t inner_team_stride(const lenv_ddqn_cfg *cfg)
     return (16 + 4 * (int64_t)t.L.n_chunks4 * t.L.P_q + 63) & ~(int64_t)63;
 }
 
+typedef void (*InnerKern)(const InnerArgs);
+
+// the generic (SHAPE 0) instantiation with the template flags TEAM / TWIDE / RENV for this cfg's env, P_q <= NT and Q-net activation.
+// There is no PReLU case: inner_check refuses q_act == LENV_ACT_PRELU before any dispatch.
+template <int ENV, int S, int A, int PPT, bool TEAM, bool TWIDE, bool RENV>
+static InnerKern ddqn_act_kernel(int q_act)
+{
+    switch (q_act) {
+    case LENV_ACT_RELU: return ddqn_se_inner_kernel<ENV, S, A, LENV_ACT_RELU, PPT, 0, TEAM, TWIDE, RENV>;
+    case LENV_ACT_LEAKYRELU: return ddqn_se_inner_kernel<ENV, S, A, LENV_ACT_LEAKYRELU, PPT, 0, TEAM, TWIDE, RENV>;
+    case LENV_ACT_TANH: return ddqn_se_inner_kernel<ENV, S, A, LENV_ACT_TANH, PPT, 0, TEAM, TWIDE, RENV>;
+    default: return ddqn_se_inner_kernel<ENV, S, A, LENV_ACT_IDENTITY, PPT, 0, TEAM, TWIDE, RENV>;
+    }
+}
+template <bool TEAM, bool TWIDE, bool RENV>
+static InnerKern ddqn_generic_kernel(const lenv_ddqn_cfg *cfg, const InnerLayout &L)
+{
+    if (cfg->env_id == LENV_ENV_CARTPOLE)
+        return L.P_q <= NT ? ddqn_act_kernel<LENV_ENV_CARTPOLE, 4, 2, 1, TEAM, TWIDE, RENV>(cfg->q_act)
+                           : ddqn_act_kernel<LENV_ENV_CARTPOLE, 4, 2, 2, TEAM, TWIDE, RENV>(cfg->q_act);
+    return L.P_q <= NT ? ddqn_act_kernel<LENV_ENV_ACROBOT, 6, 3, 1, TEAM, TWIDE, RENV>(cfg->q_act)
+                       : ddqn_act_kernel<LENV_ENV_ACROBOT, 6, 3, 2, TEAM, TWIDE, RENV>(cfg->q_act);
+}
+
 // the TEAM instantiation that runs this cfg (a chain on a team of workgroups: the generic instantiation with the exchange code, or the
 // published CartPole shape's)
-typedef void (*InnerKern)(const InnerArgs);
 static InnerKern ddqn_team_kernel(const lenv_ddqn_cfg *cfg, const InnerLayout &L)
 {
-    InnerKern kern = nullptr;
-#define LENV_PICK2(ENVID, SS, AA, PP)                                                                              \
-    switch (cfg->q_act) {                                                                                      \
-    case LENV_ACT_RELU: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_RELU, PP, 0, true>; break;            \
-    case LENV_ACT_LEAKYRELU: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_LEAKYRELU, PP, 0, true>; break;  \
-    case LENV_ACT_TANH: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_TANH, PP, 0, true>; break;            \
-    default: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_IDENTITY, PP, 0, true>; break;                   \
-    }
-    if (cfg->env_id == LENV_ENV_CARTPOLE) { if (L.P_q <= NT) { LENV_PICK2(LENV_ENV_CARTPOLE, 4, 2, 1) } else { LENV_PICK2(LENV_ENV_CARTPOLE, 4, 2, 2) } }
-    else { if (L.P_q <= NT) { LENV_PICK2(LENV_ENV_ACROBOT, 6, 3, 1) } else { LENV_PICK2(LENV_ENV_ACROBOT, 6, 3, 2) } }
-#undef LENV_PICK2
-    if (!cfg_disables_fixed_shape(cfg) && published_shape(cfg, L) == 1) kern = ddqn_se_inner_kernel<LENV_ENV_CARTPOLE, 4, 2, LENV_ACT_TANH, 1, 1, true>;
-    return kern;
+    if (!cfg_disables_fixed_shape(cfg) && published_shape(cfg, L) == 1) return ddqn_se_inner_kernel<LENV_ENV_CARTPOLE, 4, 2, LENV_ACT_TANH, 1, 1, true>;
+    return ddqn_generic_kernel<true, false, false>(cfg, L);
 }
 
 // TWIDE launches (teams of four and six at B = 199): every member's items cut six or three ways must fit the waves next to the env wave,
@@ -1784,19 +1796,8 @@ static bool ddqn_team_wide_ok(const lenv_ddqn_cfg *cfg, const InnerLayout &L, in
 }
 static InnerKern ddqn_team_wide_kernel(const lenv_ddqn_cfg *cfg, const InnerLayout &L)
 {
-    InnerKern kern = nullptr;
-#define LENV_PICK2(ENVID, SS, AA, PP)                                                                                      \
-    switch (cfg->q_act) {                                                                                                  \
-    case LENV_ACT_RELU: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_RELU, PP, 0, true, true>; break;            \
-    case LENV_ACT_LEAKYRELU: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_LEAKYRELU, PP, 0, true, true>; break;  \
-    case LENV_ACT_TANH: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_TANH, PP, 0, true, true>; break;            \
-    default: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_IDENTITY, PP, 0, true, true>; break;                   \
-    }
-    if (cfg->env_id == LENV_ENV_CARTPOLE) { if (L.P_q <= NT) { LENV_PICK2(LENV_ENV_CARTPOLE, 4, 2, 1) } else { LENV_PICK2(LENV_ENV_CARTPOLE, 4, 2, 2) } }
-    else { if (L.P_q <= NT) { LENV_PICK2(LENV_ENV_ACROBOT, 6, 3, 1) } else { LENV_PICK2(LENV_ENV_ACROBOT, 6, 3, 2) } }
-#undef LENV_PICK2
-    if (!cfg_disables_fixed_shape(cfg) && published_shape(cfg, L) == 1) kern = ddqn_se_inner_kernel<LENV_ENV_CARTPOLE, 4, 2, LENV_ACT_TANH, 1, 1, true, true>;
-    return kern;
+    if (!cfg_disables_fixed_shape(cfg) && published_shape(cfg, L) == 1) return ddqn_se_inner_kernel<LENV_ENV_CARTPOLE, 4, 2, LENV_ACT_TANH, 1, 1, true, true>;
+    return ddqn_generic_kernel<true, true, false>(cfg, L);
 }
 
 // Workgroups per chain of a launch with `chains` chains: G > 1 when the chains leave enough of the GPU idle for every member of every
@@ -1887,33 +1888,8 @@ extern "C" int lenv_ddqn_se_inner_loop(const lenv_ddqn_cfg *cfg, const float *th
     a.team_G = ddqn_pick_team(cfg, chains, cfg->rng_mode == LENV_RNG_COUNTER && !out->trace_action);
     if (a.team_G > 1 && workspace_bytes < replay_bytes + meter_bytes + sched_bytes + (size_t)chains * (size_t)a.team_stride * sizeof(float)) return LENV_ERR_WORKSPACE;
 
-    void (*kern)(const InnerArgs) = nullptr;
-#define LENV_PICK2(ENVID, SS, AA, PP)                                                                              \
-    switch (cfg->q_act) {                                                                                          \
-    case LENV_ACT_RELU: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_RELU, PP>; break;                      \
-    case LENV_ACT_LEAKYRELU: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_LEAKYRELU, PP>; break;            \
-    case LENV_ACT_TANH: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_TANH, PP>; break;                      \
-    case LENV_ACT_PRELU: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_PRELU, PP>; break;                    \
-    default: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_IDENTITY, PP>; break;                             \
-    }
-#define LENV_PICK(ENVID, SS, AA) if (a.L.P_q <= NT) { LENV_PICK2(ENVID, SS, AA, 1) } else { LENV_PICK2(ENVID, SS, AA, 2) }
-    if (cfg->env_id == LENV_ENV_CARTPOLE) { LENV_PICK(LENV_ENV_CARTPOLE, 4, 2) }
-    else { LENV_PICK(LENV_ENV_ACROBOT, 6, 3) }
-#undef LENV_PICK2
-    if (cfg->synthetic_env_type == 1) {
-        // the RENV instantiations (RewardEnv over the real env / the real env itself as the training env)
-#define LENV_PICK2(ENVID, SS, AA, PP)                                                                                                   \
-        switch (cfg->q_act) {                                                                                                           \
-        case LENV_ACT_RELU: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_RELU, PP, 0, false, false, true>; break;                \
-        case LENV_ACT_LEAKYRELU: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_LEAKYRELU, PP, 0, false, false, true>; break;      \
-        case LENV_ACT_TANH: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_TANH, PP, 0, false, false, true>; break;                \
-        default: kern = ddqn_se_inner_kernel<ENVID, SS, AA, LENV_ACT_IDENTITY, PP, 0, false, false, true>; break;                       \
-        }
-        if (cfg->env_id == LENV_ENV_CARTPOLE) { LENV_PICK(LENV_ENV_CARTPOLE, 4, 2) }
-        else { LENV_PICK(LENV_ENV_ACROBOT, 6, 3) }
-#undef LENV_PICK2
-    }
-#undef LENV_PICK
+    // the RENV instantiations: RewardEnv over the real env / the real env itself as the training env
+    InnerKern kern = cfg->synthetic_env_type == 1 ? ddqn_generic_kernel<false, false, true>(cfg, a.L) : ddqn_generic_kernel<false, false, false>(cfg, a.L);
     if (cfg->rng_mode == LENV_RNG_COUNTER && !out->trace_action && !cfg_disables_fixed_shape(cfg)) {
         switch (published_shape(cfg, a.L)) {
         case 1: kern = ddqn_se_inner_kernel<LENV_ENV_CARTPOLE, 4, 2, LENV_ACT_TANH, 1, 1>; break;

@@ -7,7 +7,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import DdqnCfg, InnerOut, MlpDesc, QlCfg, QlOut, Tapes, Td3Cfg, Td3Out, Td3Tapes
+from ._lib import DdqnCfg, InnerOut, MlpDesc, QlOut, Tapes, Td3Cfg, Td3dCfg, Td3dTapes, Td3Out, Td3Tapes
 
 
 def require_device():
@@ -122,390 +122,294 @@ def chain_key(seed, generation, worker, kind):
     return int(_lib.lib().lenv_chain_key(seed, generation, worker, kind))
 
 
-def _alloc_chain_hp(obj):
-    """Device arrays of include/lenv_hip.h's lenv_chain_hp for obj.chains chains + the struct that points at them."""
-    dev, n = obj.dev, obj.chains
-    obj.hp = dict(lr=torch.zeros(n, dtype=torch.float64, device=dev), batch_size=torch.zeros(n, dtype=torch.int32, device=dev),
-                  q_hidden=torch.zeros(n, dtype=torch.int32, device=dev), q_layers=torch.zeros(n, dtype=torch.int32, device=dev))
-    obj.hp_struct = _lib.ChainHp(_ptr(obj.hp["lr"]), _ptr(obj.hp["batch_size"]), _ptr(obj.hp["q_hidden"]), _ptr(obj.hp["q_layers"]))
-    obj.agent_init = torch.zeros((n, obj.p_agent), dtype=torch.float32, device=dev)
+def _count(name, *args):
+    """A non-negative count from a C entry point (a negative one is its error code)."""
+    n = int(getattr(_lib.lib(), name)(*args))
+    _lib.check(min(n, 0), name)
+    return n
 
 
-def _set_chain_hp(obj, lr, batch_size, hidden_size, hidden_layer, max_batch, max_hidden, max_layers):
-    if not obj.vary:
-        raise ValueError("the inner loop was built without vary=True")
-    n = obj.chains
-    if not (len(lr) == len(batch_size) == len(hidden_size) == len(hidden_layer) == n):
-        raise ValueError("set_hp: need %d values per hyper-parameter" % n)
-    layers = [max(1, int(v)) for v in hidden_layer]
-    if max(batch_size) > max_batch or max(hidden_size) > max_hidden or max(layers) > max_layers or min(batch_size) < 1 \
-            or min(hidden_size) < 1:
-        raise ValueError("set_hp: a chain's hyper-parameters exceed the maxima the inner loop was sized for")
-    obj.hp["lr"].copy_(torch.tensor([float(v) for v in lr], dtype=torch.float64))
-    obj.hp["batch_size"].copy_(torch.tensor([int(v) for v in batch_size], dtype=torch.int32))
-    obj.hp["q_hidden"].copy_(torch.tensor([int(v) for v in hidden_size], dtype=torch.int32))
-    obj.hp["q_layers"].copy_(torch.tensor(layers, dtype=torch.int32))
+class _InnerLoopBase(object):
+    """What the four fused inner-loop owners share for a fixed (cfg, chains): the workspace and outputs, the *Out and tapes structs
+    that point at them, run()'s argument checks and the *_vary agents' per-chain hyper-parameters.  A family states its structs
+    (Out, Tapes, the tapes its kernel reads), the name of its final-parameter buffer, its step trace as (name, trailing shape, dtype)
+    with cfg field names for dimensions, and, for set_hp / draw_agent_init / chain_num_params, its cfg class, the cfg fields of the
+    maximal batch / width / depth and its *_num_params / *_agent_init* entry points."""
+    Out = Tapes = None
+    tape_keys = None                      # the tapes the kernel reads (None: every one of Tapes.keys)
+    final = None                          # "final_online" / "final_params"
+    trace_spec = ()
+    cfg_type = hp_fields = num_params_fn = agent_init_fn = None
+    p_agent = None                        # QL: a table, no parameter vector
 
-
-def _draw_icm_init(obj, rng_keys, bounds):
-    """Fresh ICMModel parameters per chain into obj.icm_init (nn.Linear default init with `bounds` [p_icm], counter-RNG stream
-    12 of every chain key)."""
-    _chk(rng_keys, torch.int64, "rng_keys"); _chk(bounds, torch.float32, "bounds")
-    rc = _lib.lib().lenv_chain_uniform_init(_ptr(rng_keys), obj.chains, 12, obj.p_icm, _ptr(bounds), _ptr(obj.icm_init), _stream())
-    _lib.check(rc, "lenv_chain_uniform_init")
-    return obj.icm_init
-
-
-class InnerLoop(object):
-    """Owns the workspace/outputs of lenv_ddqn_se_inner_loop for a fixed (cfg, chains)."""
-
-    def __init__(self, cfg, chains, want_episode_stats=True, want_final_online=False, trace_cap=0, vary=False):
-        """vary=True: the *_vary agents -- cfg carries the MAXIMAL batch_size / q_hidden / q_layers, every chain runs with its
-        own lr / batch_size / hidden_size / hidden_layer (set_hp) in the GEMM-tiled kernel (lenv_dueling_se_inner_loop_hp)."""
+    def __init__(self, cfg, chains):
         self.dev = require_device()
         self.cfg, self.chains = cfg, int(chains)
-        L = _lib.lib()
-        E, T, S = cfg.train_episodes, cfg.test_episodes, cfg.state_dim
+
+    def _num_params(self, cfg, *outs):
+        """the agent's parameter count at cfg's shapes (the TD3 counters also take optional actor / critic out-pointers)"""
+        fn = getattr(_lib.lib(), self.num_params_fn)
+        return _count(self.num_params_fn, C.byref(cfg), *(outs or (None,) * (len(fn.argtypes) - 1)))
+
+    def _init_vary(self, vary):
+        """Device arrays of include/lenv_hip.h's lenv_chain_hp for the chains + the struct that points at them."""
         self.vary = bool(vary)
         self.hp = self.hp_struct = self.agent_init = None
-        # DuelingDDQN, and DDQN whose Critic_DQN the register-resident kernel refuses (hidden_layer >= 2 / wide layers),
-        # run in the GEMM-tiled kernel; `dueling` keeps its name from the first of the two
-        self.icm = bool(cfg.icm_enabled)               # ICM agents (ddqn_icm / duelingddqn_icm): GEMM-tiled kernel only
+        if self.vary:
+            dev, n = self.dev, self.chains
+            self.hp = dict(lr=torch.zeros(n, dtype=torch.float64, device=dev), batch_size=torch.zeros(n, dtype=torch.int32, device=dev),
+                           q_hidden=torch.zeros(n, dtype=torch.int32, device=dev), q_layers=torch.zeros(n, dtype=torch.int32, device=dev))
+            self.hp_struct = _lib.ChainHp(_ptr(self.hp["lr"]), _ptr(self.hp["batch_size"]), _ptr(self.hp["q_hidden"]), _ptr(self.hp["q_layers"]))
+            self.agent_init = torch.zeros((n, self.p_agent), dtype=torch.float32, device=dev)
+
+    def _hp_arg(self):
+        return C.byref(self.hp_struct) if self.vary else None
+
+    def _init_icm(self, num_params_fn):
+        self.icm = bool(self.cfg.icm_enabled)
         self.icm_init = self.icm_final = self.icm_io = None
-        # (a RewardEnv / real-env cfg with an explicit micro-chunk takes the register-resident kernel's RENV instantiations; with grad_chunk 0 --
-        # one sequential batch gradient -- the probe refuses it and the GEMM-tiled kernel runs it)
-        self.dueling = self.vary or self.icm or cfg.agent_kind == 1 or (cfg.agent_kind == 0 and L.lenv_ddqn_se_lds_bytes(C.byref(cfg)) <= 0
-                                                                        and L.lenv_dueling_num_params(C.byref(cfg)) > 0)
-        if self.dueling:
-            self.p_agent = int(L.lenv_dueling_num_params(C.byref(cfg)))
-            _lib.check(min(self.p_agent, 0), "lenv_dueling_num_params")
-            self.ws_bytes = int(L.lenv_dueling_se_workspace_bytes(C.byref(cfg), self.chains))
-            self._fn = L.lenv_dueling_se_inner_loop
-            if self.vary:
-                _alloc_chain_hp(self)
-            if self.icm:
-                self.p_icm = int(L.lenv_icm_num_params(C.byref(cfg)))
-                _lib.check(min(self.p_icm, 0), "lenv_icm_num_params")
-                self.icm_init = torch.zeros((self.chains, self.p_icm), dtype=torch.float32, device=self.dev)
-                self.icm_final = torch.zeros((self.chains, self.p_icm), dtype=torch.float32, device=self.dev)
-                self.icm_io = _lib.IcmIo(_ptr(self.icm_init), _ptr(self.icm_final))
-        else:
-            self.ws_bytes = int(L.lenv_ddqn_se_workspace_bytes(C.byref(cfg), self.chains))
-            qd = mlp_desc(S, cfg.q_hidden, cfg.q_layers, cfg.num_actions, cfg.q_act)
-            self.p_agent = mlp_num_params(qd)
-            self._fn = L.lenv_ddqn_se_inner_loop
-        self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.dev)
-        self.score = torch.zeros(self.chains, dtype=torch.float64, device=self.dev)
-        self.stats = torch.zeros((self.chains, 4), dtype=torch.int64, device=self.dev)
-        self.status = torch.zeros(self.chains, dtype=torch.int32, device=self.dev)
-        self.episode_test_mean = self.episode_len = self.final_returns = self.final_online = None
+        if self.icm:
+            self.p_icm = _count(num_params_fn, C.byref(self.cfg))
+            self.icm_init = torch.zeros((self.chains, self.p_icm), dtype=torch.float32, device=self.dev)
+            self.icm_final = torch.zeros((self.chains, self.p_icm), dtype=torch.float32, device=self.dev)
+            self.icm_io = _lib.IcmIo(_ptr(self.icm_init), _ptr(self.icm_final))
+
+    def _icm_arg(self):
+        return C.byref(self.icm_io) if self.icm else None
+
+    def _alloc_outputs(self, ws_bytes, want_episode_stats, want_final, trace_cap):
+        """The workspace (ws_bytes None: the kernel needs none), the common outputs, the optional final-parameter buffer and step
+        trace, and self.out built in the Out struct's field order from the attributes / trace entries of those names."""
+        dev, n, cfg = self.dev, self.chains, self.cfg
+        if ws_bytes is not None:
+            self.ws_bytes = int(ws_bytes)
+            self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        self.score = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.stats = torch.zeros((n, 4), dtype=torch.int64, device=dev)
+        self.status = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.episode_test_mean = self.episode_len = self.final_returns = None
         if want_episode_stats:
-            self.episode_test_mean = torch.zeros((self.chains, max(E, 1)), dtype=torch.float64, device=self.dev)
-            self.episode_len = torch.zeros((self.chains, max(E, 1)), dtype=torch.int32, device=self.dev)
-            self.final_returns = torch.zeros((self.chains, T), dtype=torch.float64, device=self.dev)
-        if want_final_online:
-            self.final_online = torch.zeros((self.chains, self.p_agent), dtype=torch.float32, device=self.dev)
+            E = max(cfg.train_episodes, 1)
+            self.episode_test_mean = torch.zeros((n, E), dtype=torch.float64, device=dev)
+            self.episode_len = torch.zeros((n, E), dtype=torch.int32, device=dev)
+            self.final_returns = torch.zeros((n, cfg.test_episodes), dtype=torch.float64, device=dev)
+        if self.final:
+            setattr(self, self.final, torch.zeros((n, self.p_agent), dtype=torch.float32, device=dev) if want_final else None)
         self.trace_cap = int(trace_cap)
         self.trace = None
         if trace_cap:
-            self.trace = dict(action=torch.zeros((self.chains, trace_cap), dtype=torch.int32, device=self.dev),
-                              state=torch.zeros((self.chains, trace_cap, S), dtype=torch.float32, device=self.dev),
-                              next_state=torch.zeros((self.chains, trace_cap, S), dtype=torch.float32, device=self.dev),
-                              reward_done=torch.zeros((self.chains, trace_cap, 2), dtype=torch.float32, device=self.dev))
-        tr = self.trace or {}
-        self.out = InnerOut(_ptr(self.score), _ptr(self.stats), _ptr(self.status), _ptr(self.episode_test_mean),
-                            _ptr(self.episode_len), _ptr(self.final_returns), _ptr(self.final_online), self.trace_cap,
-                            _ptr(tr.get("action")), _ptr(tr.get("state")), _ptr(tr.get("next_state")),
-                            _ptr(tr.get("reward_done")))
+            self.trace = {name: torch.zeros((n, self.trace_cap) + tuple(getattr(cfg, d) if isinstance(d, str) else d for d in shape),
+                                            dtype=dtype, device=dev) for name, shape, dtype in self.trace_spec}
+        tr, vals = self.trace or {}, []
+        for f, _ in self.Out._fields_:
+            if f == "trace_cap":
+                vals.append(self.trace_cap)
+            elif f.startswith("trace_"):
+                vals.append(_ptr(tr.get(f[len("trace_"):])))
+            else:
+                vals.append(_ptr(getattr(self, f)))
+        self.out = self.Out(*vals)
+
+    def _tapes_arg(self, tapes):
+        """byref of a Tapes struct over the tape tensors [chains, stride] the kernel reads (the other pairs (None, 0)), or None"""
+        if tapes is None:
+            return None
+        keys = self.Tapes.keys if self.tape_keys is None else self.tape_keys
+        vals = []
+        for k in self.Tapes.keys:
+            vals += [_ptr(tapes[k]), tapes[k].shape[1]] if k in keys else [None, 0]
+        return C.byref(self.Tapes(*vals))
+
+    def _check_run(self, theta, eps, worker, sign, rng_keys, agent_init=None):
+        _chk(theta, torch.float32, "theta"); _chk(eps, torch.float32, "eps"); _chk(worker, torch.int32, "worker")
+        _chk(sign, torch.float32, "sign"); _chk(rng_keys, torch.int64, "rng_keys")
+        if self.p_agent is not None:
+            _chk(agent_init, torch.float32, "agent_init")
+            if agent_init.shape != (self.chains, self.p_agent):
+                raise ValueError("agent_init must be [chains, %d]" % self.p_agent)
+
+    def _run_args(self, theta, eps, worker, sign, agent_init, rng_keys, tapes):
+        """run()'s checks, then what follows the cfg (and hp / icm) of the C launch"""
+        self._check_run(theta, eps, worker, sign, rng_keys, agent_init)
+        return (_ptr(theta), _ptr(eps), _ptr(worker), _ptr(sign), _ptr(agent_init), _ptr(rng_keys), self._tapes_arg(tapes), self.chains,
+                _ptr(self.workspace), self.ws_bytes, C.byref(self.out), _stream())
 
     def set_hp(self, lr, batch_size, hidden_size, hidden_layer):
         """The chains' own hyper-parameters (host sequences of length `chains`; hidden_layer as the config writes it: the
         network has max(1, hidden_layer) hidden layers, models/model_utils.py:33-37)."""
-        _set_chain_hp(self, lr, batch_size, hidden_size, hidden_layer, self.cfg.batch_size, self.cfg.q_hidden, self.cfg.q_layers)
+        if not self.vary:
+            raise ValueError("the inner loop was built without vary=True")
+        n = self.chains
+        if not (len(lr) == len(batch_size) == len(hidden_size) == len(hidden_layer) == n):
+            raise ValueError("set_hp: need %d values per hyper-parameter" % n)
+        max_batch, max_hidden, max_layers = (getattr(self.cfg, f) for f in self.hp_fields)
+        layers = [max(1, int(v)) for v in hidden_layer]
+        if max(batch_size) > max_batch or max(hidden_size) > max_hidden or max(layers) > max_layers or min(batch_size) < 1 \
+                or min(hidden_size) < 1:
+            raise ValueError("set_hp: a chain's hyper-parameters exceed the maxima the inner loop was sized for")
+        self.hp["lr"].copy_(torch.tensor([float(v) for v in lr], dtype=torch.float64))
+        self.hp["batch_size"].copy_(torch.tensor([int(v) for v in batch_size], dtype=torch.int32))
+        self.hp["q_hidden"].copy_(torch.tensor([int(v) for v in hidden_size], dtype=torch.int32))
+        self.hp["q_layers"].copy_(torch.tensor(layers, dtype=torch.int32))
 
     def chain_num_params(self, hidden_size, hidden_layer):
-        """Parameter count of one chain's agent at its own shapes (the used prefix of its agent_init / final_online row)."""
-        probe = _lib.DdqnCfg.from_buffer_copy(self.cfg)
-        probe.q_hidden, probe.q_layers = int(hidden_size), max(1, int(hidden_layer))
-        n = int(_lib.lib().lenv_dueling_num_params(C.byref(probe)))
-        _lib.check(min(n, 0), "lenv_dueling_num_params")
-        return n
-
-    def draw_icm_init(self, rng_keys, bounds):
-        return _draw_icm_init(self, rng_keys, bounds)
+        """Parameter count of one chain's agent at its own shapes (the used prefix of its agent_init / final-parameter row)."""
+        probe = self.cfg_type.from_buffer_copy(self.cfg)
+        _, width, depth = self.hp_fields
+        setattr(probe, width, int(hidden_size))
+        setattr(probe, depth, max(1, int(hidden_layer)))
+        return self._num_params(probe)
 
     def draw_agent_init(self, rng_keys):
-        """Fresh agents at every chain's own shapes into self.agent_init (nn.Linear default init, keyed by the chain keys)."""
+        """Fresh agents at every chain's own shapes into self.agent_init (nn.Linear default init -- LayerNorm 1 / 0 --, keyed by the
+        chain keys)."""
         _chk(rng_keys, torch.int64, "rng_keys")
-        rc = _lib.lib().lenv_dueling_agent_init_hp(C.byref(self.cfg), C.byref(self.hp_struct), _ptr(rng_keys), self.chains,
-                                                   _ptr(self.agent_init), _stream())
-        _lib.check(rc, "lenv_dueling_agent_init_hp")
+        rc = getattr(_lib.lib(), self.agent_init_fn)(C.byref(self.cfg), self._hp_arg(), _ptr(rng_keys), self.chains, _ptr(self.agent_init),
+                                                     _stream())
+        _lib.check(rc, self.agent_init_fn)
         return self.agent_init
+
+    def draw_icm_init(self, rng_keys, bounds):
+        """Fresh ICMModel parameters per chain into self.icm_init (nn.Linear default init with `bounds` [p_icm], counter-RNG stream
+        12 of every chain key)."""
+        _chk(rng_keys, torch.int64, "rng_keys"); _chk(bounds, torch.float32, "bounds")
+        rc = _lib.lib().lenv_chain_uniform_init(_ptr(rng_keys), self.chains, 12, self.p_icm, _ptr(bounds), _ptr(self.icm_init), _stream())
+        _lib.check(rc, "lenv_chain_uniform_init")
+        return self.icm_init
+
+
+_TD3_TRACE = (("action", ("action_dim",), torch.float32), ("state", ("state_dim",), torch.float32),
+              ("next_state", ("state_dim",), torch.float32), ("reward", (), torch.float32))
+
+
+class InnerLoop(_InnerLoopBase):
+    """Owns the workspace/outputs of lenv_ddqn_se_inner_loop for a fixed (cfg, chains)."""
+    Out, Tapes, final = InnerOut, Tapes, "final_online"
+    trace_spec = (("action", (), torch.int32), ("state", ("state_dim",), torch.float32), ("next_state", ("state_dim",), torch.float32),
+                  ("reward_done", (2,), torch.float32))
+    cfg_type, hp_fields = DdqnCfg, ("batch_size", "q_hidden", "q_layers")
+    num_params_fn, agent_init_fn = "lenv_dueling_num_params", "lenv_dueling_agent_init_hp"
+
+    def __init__(self, cfg, chains, want_episode_stats=True, want_final_online=False, trace_cap=0, vary=False):
+        """vary=True: the *_vary agents -- cfg carries the MAXIMAL batch_size / q_hidden / q_layers, every chain runs with its
+        own lr / batch_size / hidden_size / hidden_layer (set_hp) in the GEMM-tiled kernel (lenv_dueling_se_inner_loop_icm)."""
+        super().__init__(cfg, chains)
+        L = _lib.lib()
+        # DuelingDDQN, and DDQN whose Critic_DQN the register-resident kernel refuses (hidden_layer >= 2 / wide layers),
+        # run in the GEMM-tiled kernel; `dueling` keeps its name from the first of the two
+        # (a RewardEnv / real-env cfg with an explicit micro-chunk takes the register-resident kernel's RENV instantiations; with grad_chunk 0 --
+        # one sequential batch gradient -- the probe refuses it and the GEMM-tiled kernel runs it)
+        icm = bool(cfg.icm_enabled)                    # ICM agents (ddqn_icm / duelingddqn_icm): GEMM-tiled kernel only
+        self.dueling = bool(vary) or icm or cfg.agent_kind == 1 or (cfg.agent_kind == 0 and L.lenv_ddqn_se_lds_bytes(C.byref(cfg)) <= 0
+                                                                    and L.lenv_dueling_num_params(C.byref(cfg)) > 0)
+        if self.dueling:
+            self.p_agent = self._num_params(cfg)
+            ws_bytes = L.lenv_dueling_se_workspace_bytes(C.byref(cfg), self.chains)
+        else:
+            self.p_agent = mlp_num_params(mlp_desc(cfg.state_dim, cfg.q_hidden, cfg.q_layers, cfg.num_actions, cfg.q_act))
+            ws_bytes = L.lenv_ddqn_se_workspace_bytes(C.byref(cfg), self.chains)
+        self._init_vary(vary)
+        self._init_icm("lenv_icm_num_params")
+        self._alloc_outputs(ws_bytes, want_episode_stats, want_final_online, trace_cap)
 
     def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None):
         """Enqueue one fused inner loop for all chains on the current stream (asynchronous)."""
         if agent_init is None and self.vary:
             agent_init = self.agent_init
-        _chk(theta, torch.float32, "theta"); _chk(eps, torch.float32, "eps"); _chk(worker, torch.int32, "worker")
-        _chk(sign, torch.float32, "sign"); _chk(agent_init, torch.float32, "agent_init")
-        if agent_init.shape != (self.chains, self.p_agent):
-            raise ValueError("agent_init must be [chains, %d]" % self.p_agent)
-        t = None
-        if tapes is not None:
-            t = Tapes(_ptr(tapes["eps_uniform"]), tapes["eps_uniform"].shape[1],
-                      _ptr(tapes["rand_action"]), tapes["rand_action"].shape[1],
-                      _ptr(tapes["replay_idx"]), tapes["replay_idx"].shape[1],
-                      _ptr(tapes["train_reset"]), tapes["train_reset"].shape[1],
-                      _ptr(tapes["test_reset"]), tapes["test_reset"].shape[1])
-        if rng_keys is not None:
-            _chk(rng_keys, torch.int64, "rng_keys")
-        args = (_ptr(theta), _ptr(eps), _ptr(worker), _ptr(sign), _ptr(agent_init), _ptr(rng_keys),
-                C.byref(t) if t is not None else None, self.chains, _ptr(self.workspace), self.ws_bytes, C.byref(self.out), _stream())
-        if self.icm:
-            rc = _lib.lib().lenv_dueling_se_inner_loop_icm(C.byref(self.cfg), C.byref(self.hp_struct) if self.vary else None,
-                                                           C.byref(self.icm_io), *args)
-        elif self.vary:
-            rc = _lib.lib().lenv_dueling_se_inner_loop_hp(C.byref(self.cfg), C.byref(self.hp_struct), *args)
-        else:
-            rc = self._fn(C.byref(self.cfg), *args)
+        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+        if self.dueling:       # the GEMM-tiled kernel: per-chain hyper-parameters and the ICM may be NULL
+            args = (self._hp_arg(), self._icm_arg()) + args
+        fn = "lenv_dueling_se_inner_loop_icm" if self.dueling else "lenv_ddqn_se_inner_loop"
+        rc = getattr(_lib.lib(), fn)(C.byref(self.cfg), *args)
         _lib.check(rc, "lenv_dueling_se_inner_loop" if self.dueling else "lenv_ddqn_se_inner_loop")
         return self.score
 
 
-class QlInnerLoop(object):
+class QlInnerLoop(_InnerLoopBase):
     """Owns the outputs of lenv_ql_rn_inner_loop for a fixed (cfg, chains, grid MDP)."""
+    Out, Tapes, tape_keys = QlOut, Tapes, ("eps_uniform", "rand_action")
+    trace_spec = (("action", (), torch.int32), ("state", (2,), torch.int32), ("reward_done", (2,), torch.float32))
 
     def __init__(self, cfg, chains, tables, want_episode_stats=True, trace_cap=0):
-        self.dev = require_device()
-        self.cfg, self.chains = cfg, int(chains)
-        N, A, E, T = cfg.n_states, cfg.n_actions, cfg.train_episodes, cfg.test_episodes
+        super().__init__(cfg, chains)
+        N, A = cfg.n_states, cfg.n_actions
         self.next_state = torch.from_numpy(tables["next_state"].astype("int32")).contiguous().to(self.dev)
         self.reward = torch.from_numpy(tables["reward"].astype("float64")).contiguous().to(self.dev)
         self.done = torch.from_numpy(tables["done"].astype("uint8")).contiguous().to(self.dev)
         H = cfg.rn_hidden            # Linear(N, H) | (layers - 1) x Linear(H, H) | Linear(H, 1)
         self.p_theta = N * H + H + (max(1, cfg.rn_layers) - 1) * (H * H + H) + H + 1
-        self.score = torch.zeros(self.chains, dtype=torch.float64, device=self.dev)
-        self.stats = torch.zeros((self.chains, 4), dtype=torch.int64, device=self.dev)
-        self.status = torch.zeros(self.chains, dtype=torch.int32, device=self.dev)
-        self.episode_test_mean = self.episode_len = self.final_returns = self.q_table = self.shaped = None
+        self.q_table = self.shaped = None
         if want_episode_stats:
-            self.episode_test_mean = torch.zeros((self.chains, max(E, 1)), dtype=torch.float64, device=self.dev)
-            self.episode_len = torch.zeros((self.chains, max(E, 1)), dtype=torch.int32, device=self.dev)
-            self.final_returns = torch.zeros((self.chains, T), dtype=torch.float64, device=self.dev)
             self.q_table = torch.zeros((self.chains, N * A), dtype=torch.float64, device=self.dev)
             self.shaped = torch.zeros((self.chains, N * A), dtype=torch.float32, device=self.dev)
-        self.trace_cap = int(trace_cap)
-        self.trace = None
-        if trace_cap:
-            self.trace = dict(action=torch.zeros((self.chains, trace_cap), dtype=torch.int32, device=self.dev),
-                              state=torch.zeros((self.chains, trace_cap, 2), dtype=torch.int32, device=self.dev),
-                              reward_done=torch.zeros((self.chains, trace_cap, 2), dtype=torch.float32, device=self.dev))
-        tr = self.trace or {}
-        self.out = QlOut(_ptr(self.score), _ptr(self.stats), _ptr(self.status), _ptr(self.episode_test_mean),
-                         _ptr(self.episode_len), _ptr(self.final_returns), _ptr(self.q_table), _ptr(self.shaped),
-                         self.trace_cap, _ptr(tr.get("action")), _ptr(tr.get("state")), _ptr(tr.get("reward_done")))
+        self._alloc_outputs(None, want_episode_stats, False, trace_cap)
 
     def run(self, theta, eps, worker, sign, rng_keys=None, tapes=None, shaped_override=None):
-        _chk(theta, torch.float32, "theta"); _chk(eps, torch.float32, "eps"); _chk(worker, torch.int32, "worker")
-        _chk(sign, torch.float32, "sign"); _chk(shaped_override, torch.float32, "shaped_override")
+        self._check_run(theta, eps, worker, sign, rng_keys)
+        _chk(shaped_override, torch.float32, "shaped_override")
         if theta is not None and theta.numel() != self.p_theta and self.cfg.reward_env_type != 0:
             raise ValueError("theta must hold %d reward-net parameters" % self.p_theta)
-        t = None
-        if tapes is not None:
-            t = Tapes(_ptr(tapes["eps_uniform"]), tapes["eps_uniform"].shape[1], _ptr(tapes["rand_action"]),
-                      tapes["rand_action"].shape[1], None, 0, None, 0, None, 0)
-        if rng_keys is not None:
-            _chk(rng_keys, torch.int64, "rng_keys")
         rc = _lib.lib().lenv_ql_rn_inner_loop(C.byref(self.cfg), _ptr(theta), _ptr(eps), _ptr(worker), _ptr(sign),
                                               _ptr(shaped_override), _ptr(self.next_state), _ptr(self.reward), _ptr(self.done),
-                                              _ptr(rng_keys), C.byref(t) if t is not None else None, self.chains,
-                                              C.byref(self.out), _stream())
+                                              _ptr(rng_keys), self._tapes_arg(tapes), self.chains, C.byref(self.out), _stream())
         _lib.check(rc, "lenv_ql_rn_inner_loop")
         return self.score
 
 
-class Td3InnerLoop(object):
+class Td3InnerLoop(_InnerLoopBase):
     """Owns the workspace/outputs of lenv_td3_rn_inner_loop for a fixed (cfg, chains)."""
+    Out, Tapes, final, trace_spec = Td3Out, Td3Tapes, "final_params", _TD3_TRACE
+    cfg_type, hp_fields = Td3Cfg, ("batch_size", "hidden", "layers")
+    num_params_fn, agent_init_fn = "lenv_td3_num_params", "lenv_td3_agent_init_hp"
 
     def __init__(self, cfg, chains, want_episode_stats=True, want_final_params=False, trace_cap=0, vary=False):
         """vary=True: TD3_vary -- cfg carries the maximal batch_size / hidden / layers, every chain runs with its own
-        hyper-parameters (set_hp) through lenv_td3_rn_inner_loop_hp."""
-        self.dev = require_device()
-        self.cfg, self.chains = cfg, int(chains)
-        self.vary = bool(vary)
-        self.hp = self.hp_struct = self.agent_init = None
-        L = _lib.lib()
+        hyper-parameters (set_hp) through lenv_td3_rn_inner_loop_icm."""
+        super().__init__(cfg, chains)
         pa, pc = C.c_int64(), C.c_int64()
-        self.p_agent = int(L.lenv_td3_num_params(C.byref(cfg), C.byref(pa), C.byref(pc)))
-        _lib.check(min(self.p_agent, 0), "lenv_td3_num_params")
-        if self.vary:
-            _alloc_chain_hp(self)
-        self.icm = bool(cfg.icm_enabled)               # TD3(icm=True): select_agent "td3_icm" / "td3_icm_vary"
-        self.icm_init = self.icm_final = self.icm_io = None
-        if self.icm:
-            self.p_icm = int(L.lenv_td3_icm_num_params(C.byref(cfg)))
-            _lib.check(min(self.p_icm, 0), "lenv_td3_icm_num_params")
-            self.icm_init = torch.zeros((self.chains, self.p_icm), dtype=torch.float32, device=self.dev)
-            self.icm_final = torch.zeros((self.chains, self.p_icm), dtype=torch.float32, device=self.dev)
-            self.icm_io = _lib.IcmIo(_ptr(self.icm_init), _ptr(self.icm_final))
+        self.p_agent = self._num_params(cfg, C.byref(pa), C.byref(pc))
         self.p_actor, self.p_critic = pa.value, pc.value
+        self._init_vary(vary)
+        self._init_icm("lenv_td3_icm_num_params")       # TD3(icm=True): select_agent "td3_icm" / "td3_icm_vary"
         self.p_theta = cfg.state_dim * cfg.rn_hidden + 2 * cfg.rn_hidden + 1
-        self.ws_bytes = int(L.lenv_td3_rn_workspace_bytes(C.byref(cfg), self.chains))
-        self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.dev)
-        E, T, S, A = cfg.train_episodes, cfg.test_episodes, cfg.state_dim, cfg.action_dim
-        self.score = torch.zeros(self.chains, dtype=torch.float64, device=self.dev)
-        self.stats = torch.zeros((self.chains, 4), dtype=torch.int64, device=self.dev)
-        self.status = torch.zeros(self.chains, dtype=torch.int32, device=self.dev)
-        self.episode_test_mean = self.episode_len = self.final_returns = self.final_params = None
-        if want_episode_stats:
-            self.episode_test_mean = torch.zeros((self.chains, max(E, 1)), dtype=torch.float64, device=self.dev)
-            self.episode_len = torch.zeros((self.chains, max(E, 1)), dtype=torch.int32, device=self.dev)
-            self.final_returns = torch.zeros((self.chains, T), dtype=torch.float64, device=self.dev)
-        if want_final_params:
-            self.final_params = torch.zeros((self.chains, self.p_agent), dtype=torch.float32, device=self.dev)
-        self.trace_cap = int(trace_cap)
-        self.trace = None
-        if trace_cap:
-            self.trace = dict(action=torch.zeros((self.chains, trace_cap, A), dtype=torch.float32, device=self.dev),
-                              state=torch.zeros((self.chains, trace_cap, S), dtype=torch.float32, device=self.dev),
-                              next_state=torch.zeros((self.chains, trace_cap, S), dtype=torch.float32, device=self.dev),
-                              reward=torch.zeros((self.chains, trace_cap), dtype=torch.float32, device=self.dev))
-        tr = self.trace or {}
-        self.out = Td3Out(_ptr(self.score), _ptr(self.stats), _ptr(self.status), _ptr(self.episode_test_mean), _ptr(self.episode_len),
-                          _ptr(self.final_returns), _ptr(self.final_params), self.trace_cap, _ptr(tr.get("action")),
-                          _ptr(tr.get("state")), _ptr(tr.get("next_state")), _ptr(tr.get("reward")))
-
-    def set_hp(self, lr, batch_size, hidden_size, hidden_layer):
-        _set_chain_hp(self, lr, batch_size, hidden_size, hidden_layer, self.cfg.batch_size, self.cfg.hidden, self.cfg.layers)
-
-    def chain_num_params(self, hidden_size, hidden_layer):
-        probe = _lib.Td3Cfg.from_buffer_copy(self.cfg)
-        probe.hidden, probe.layers = int(hidden_size), max(1, int(hidden_layer))
-        n = int(_lib.lib().lenv_td3_num_params(C.byref(probe), None, None))
-        _lib.check(min(n, 0), "lenv_td3_num_params")
-        return n
-
-    def draw_icm_init(self, rng_keys, bounds):
-        return _draw_icm_init(self, rng_keys, bounds)
-
-    def draw_agent_init(self, rng_keys):
-        """Fresh actor | critic_1 | critic_2 at every chain's own shapes into self.agent_init."""
-        _chk(rng_keys, torch.int64, "rng_keys")
-        rc = _lib.lib().lenv_td3_agent_init_hp(C.byref(self.cfg), C.byref(self.hp_struct), _ptr(rng_keys), self.chains,
-                                               _ptr(self.agent_init), _stream())
-        _lib.check(rc, "lenv_td3_agent_init_hp")
-        return self.agent_init
+        self._alloc_outputs(_lib.lib().lenv_td3_rn_workspace_bytes(C.byref(cfg), self.chains), want_episode_stats, want_final_params,
+                            trace_cap)
 
     def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None):
         if agent_init is None and self.vary:
             agent_init = self.agent_init
-        _chk(theta, torch.float32, "theta"); _chk(eps, torch.float32, "eps"); _chk(worker, torch.int32, "worker")
-        _chk(sign, torch.float32, "sign"); _chk(agent_init, torch.float32, "agent_init")
-        if agent_init.shape != (self.chains, self.p_agent):
-            raise ValueError("agent_init must be [chains, %d]" % self.p_agent)
-        t = None
-        if tapes is not None:
-            t = Td3Tapes(_ptr(tapes["rand_action"]), tapes["rand_action"].shape[1], _ptr(tapes["act_noise"]), tapes["act_noise"].shape[1],
-                         _ptr(tapes["test_noise"]), tapes["test_noise"].shape[1], _ptr(tapes["policy_noise"]), tapes["policy_noise"].shape[1],
-                         _ptr(tapes["replay_idx"]), tapes["replay_idx"].shape[1], _ptr(tapes["train_reset"]), tapes["train_reset"].shape[1],
-                         _ptr(tapes["test_reset"]), tapes["test_reset"].shape[1])
-        if rng_keys is not None:
-            _chk(rng_keys, torch.int64, "rng_keys")
-        args = (_ptr(theta), _ptr(eps), _ptr(worker), _ptr(sign), _ptr(agent_init), _ptr(rng_keys),
-                C.byref(t) if t is not None else None, self.chains, _ptr(self.workspace), self.ws_bytes, C.byref(self.out), _stream())
-        if self.icm:
-            rc = _lib.lib().lenv_td3_rn_inner_loop_icm(C.byref(self.cfg), C.byref(self.hp_struct) if self.vary else None,
-                                                       C.byref(self.icm_io), *args)
-        elif self.vary:
-            rc = _lib.lib().lenv_td3_rn_inner_loop_hp(C.byref(self.cfg), C.byref(self.hp_struct), *args)
-        else:
-            rc = _lib.lib().lenv_td3_rn_inner_loop(C.byref(self.cfg), *args)
+        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+        rc = _lib.lib().lenv_td3_rn_inner_loop_icm(C.byref(self.cfg), self._hp_arg(), self._icm_arg(), *args)
         _lib.check(rc, "lenv_td3_rn_inner_loop")
         return self.score
 
 
-class Td3DiscreteInnerLoop(object):
+class Td3DiscreteInnerLoop(_InnerLoopBase):
     """Owns the workspace/outputs of lenv_td3d_inner_loop (TD3_discrete_vary on a VirtualEnv) for a fixed (cfg, chains).
     vary=True: cfg carries the maximal batch_size / hidden / layers, every chain runs with its own draw (set_hp)."""
+    Out, Tapes, final, trace_spec = Td3Out, Td3dTapes, "final_params", _TD3_TRACE
+    cfg_type, hp_fields = Td3dCfg, ("batch_size", "hidden", "layers")
+    num_params_fn, agent_init_fn = "lenv_td3d_num_params", "lenv_td3d_agent_init"
 
     def __init__(self, cfg, chains, want_episode_stats=True, want_final_params=False, trace_cap=0, vary=False):
-        self.dev = require_device()
-        self.cfg, self.chains = cfg, int(chains)
-        self.vary = bool(vary)
-        self.hp = self.hp_struct = self.agent_init = None
+        super().__init__(cfg, chains)
         L = _lib.lib()
         pa, pc = C.c_int64(), C.c_int64()
-        self.p_agent = int(L.lenv_td3d_num_params(C.byref(cfg), C.byref(pa), C.byref(pc)))
-        _lib.check(min(self.p_agent, 0), "lenv_td3d_num_params")
+        self.p_agent = self._num_params(cfg, C.byref(pa), C.byref(pc))
         self.p_actor, self.p_critic = pa.value, pc.value
         self.p_theta = int(L.lenv_td3d_se_num_params(C.byref(cfg)))
-        if self.vary:
-            _alloc_chain_hp(self)
-        else:
+        self._init_vary(vary)
+        if not self.vary:
             self.agent_init = torch.zeros((self.chains, self.p_agent), dtype=torch.float32, device=self.dev)
-        self.ws_bytes = int(L.lenv_td3d_workspace_bytes(C.byref(cfg), self.chains))
-        self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.dev)
-        E, T, S, A = cfg.train_episodes, cfg.test_episodes, cfg.state_dim, cfg.action_dim
-        self.score = torch.zeros(self.chains, dtype=torch.float64, device=self.dev)
-        self.stats = torch.zeros((self.chains, 4), dtype=torch.int64, device=self.dev)
-        self.status = torch.zeros(self.chains, dtype=torch.int32, device=self.dev)
-        self.episode_test_mean = self.episode_len = self.final_returns = self.final_params = None
-        if want_episode_stats:
-            self.episode_test_mean = torch.zeros((self.chains, max(E, 1)), dtype=torch.float64, device=self.dev)
-            self.episode_len = torch.zeros((self.chains, max(E, 1)), dtype=torch.int32, device=self.dev)
-            self.final_returns = torch.zeros((self.chains, T), dtype=torch.float64, device=self.dev)
-        if want_final_params:
-            self.final_params = torch.zeros((self.chains, self.p_agent), dtype=torch.float32, device=self.dev)
-        self.trace_cap = int(trace_cap)
-        self.trace = None
-        if trace_cap:
-            self.trace = dict(action=torch.zeros((self.chains, trace_cap, A), dtype=torch.float32, device=self.dev),
-                              state=torch.zeros((self.chains, trace_cap, S), dtype=torch.float32, device=self.dev),
-                              next_state=torch.zeros((self.chains, trace_cap, S), dtype=torch.float32, device=self.dev),
-                              reward=torch.zeros((self.chains, trace_cap), dtype=torch.float32, device=self.dev))
-        tr = self.trace or {}
-        self.out = Td3Out(_ptr(self.score), _ptr(self.stats), _ptr(self.status), _ptr(self.episode_test_mean), _ptr(self.episode_len),
-                          _ptr(self.final_returns), _ptr(self.final_params), self.trace_cap, _ptr(tr.get("action")),
-                          _ptr(tr.get("state")), _ptr(tr.get("next_state")), _ptr(tr.get("reward")))
-
-    def set_hp(self, lr, batch_size, hidden_size, hidden_layer):
-        _set_chain_hp(self, lr, batch_size, hidden_size, hidden_layer, self.cfg.batch_size, self.cfg.hidden, self.cfg.layers)
-
-    def chain_num_params(self, hidden_size, hidden_layer):
-        probe = _lib.Td3dCfg.from_buffer_copy(self.cfg)
-        probe.hidden, probe.layers = int(hidden_size), max(1, int(hidden_layer))
-        n = int(_lib.lib().lenv_td3d_num_params(C.byref(probe), None, None))
-        _lib.check(min(n, 0), "lenv_td3d_num_params")
-        return n
-
-    def draw_agent_init(self, rng_keys):
-        """Fresh actor | critic_1 | critic_2 (nn.Linear default init, LayerNorm 1 / 0) at every chain's own shapes."""
-        _chk(rng_keys, torch.int64, "rng_keys")
-        rc = _lib.lib().lenv_td3d_agent_init(C.byref(self.cfg), C.byref(self.hp_struct) if self.vary else None, _ptr(rng_keys), self.chains,
-                                             _ptr(self.agent_init), _stream())
-        _lib.check(rc, "lenv_td3d_agent_init")
-        return self.agent_init
+        self._alloc_outputs(L.lenv_td3d_workspace_bytes(C.byref(cfg), self.chains), want_episode_stats, want_final_params, trace_cap)
 
     def run(self, theta, eps, worker, sign, agent_init=None, rng_keys=None, tapes=None):
         if agent_init is None:
             agent_init = self.agent_init
-        _chk(theta, torch.float32, "theta"); _chk(eps, torch.float32, "eps"); _chk(worker, torch.int32, "worker")
-        _chk(sign, torch.float32, "sign"); _chk(agent_init, torch.float32, "agent_init")
-        if agent_init.shape != (self.chains, self.p_agent):
-            raise ValueError("agent_init must be [chains, %d]" % self.p_agent)
+        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
         if theta.numel() != self.p_theta:
             raise ValueError("theta must hold %d SE parameters" % self.p_theta)
-        t = None
-        if tapes is not None:
-            vals = []
-            for k in _lib.TD3D_TAPE_KEYS:
-                vals += [_ptr(tapes[k]), tapes[k].shape[1]]
-            t = _lib.Td3dTapes(*vals)
-        if rng_keys is not None:
-            _chk(rng_keys, torch.int64, "rng_keys")
-        rc = _lib.lib().lenv_td3d_inner_loop(C.byref(self.cfg), C.byref(self.hp_struct) if self.vary else None, _ptr(theta), _ptr(eps),
-                                             _ptr(worker), _ptr(sign), _ptr(agent_init), _ptr(rng_keys), C.byref(t) if t is not None else None,
-                                             self.chains, _ptr(self.workspace), self.ws_bytes, C.byref(self.out), _stream())
+        rc = _lib.lib().lenv_td3d_inner_loop(C.byref(self.cfg), self._hp_arg(), *args)
         _lib.check(rc, "lenv_td3d_inner_loop")
         return self.score
 
