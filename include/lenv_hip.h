@@ -165,7 +165,7 @@ typedef struct {
 int lenv_abi_version(void);
 /* sizeof of the ABI structs as the library was compiled (a binding checks its mirror against it): which = 0 lenv_mlp_desc, 1 lenv_ddqn_cfg,
  * 2 lenv_ql_cfg, 3 lenv_td3_cfg, 4 lenv_td3d_cfg, 5 lenv_tapes, 6 lenv_inner_out, 7 lenv_ql_out, 8 lenv_td3_tapes, 9 lenv_td3_out,
- * 10 lenv_td3d_tapes, 11 lenv_chain_hp, 12 lenv_icm_io; anything else: LENV_ERR_INVALID.  HOST. */
+ * 10 lenv_td3d_tapes, 11 lenv_chain_hp, 12 lenv_icm_io, 13 lenv_td3d_rn_cfg; anything else: LENV_ERR_INVALID.  HOST. */
 int64_t lenv_struct_size(int32_t which);
 const char *lenv_error_string(int code);
 /* number of parameters of an MLP / of the three-net SE */
@@ -494,6 +494,30 @@ int lenv_td3d_inner_loop(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_chain_hp 
                          const float *theta, const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
                          const uint64_t *rng_keys, const lenv_td3d_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace,
                          size_t workspace_bytes, const lenv_td3_out *out /*HOST*/, void *stream);
+/*
+ * TD3_discrete_vary trained on RewardEnv(real env) (envs/reward_env.py:61-133), or on the real env itself (reward_env_type 0: the real
+ * reward passes through, syn_env_run_vary_hp.py mode 0): the chain steps the real env's fp64 physics (TimeLimit: done at max_steps) and
+ * shapes its reward with the perturbed reward net, as lenv_rn_shape_rows does.  The cfg's se_* fields are not read; theta / eps rows are the
+ * reward net's flat parameters (RewardEnv.build_reward_net: S -> rn_hidden x rn_layers -> 1, a 1-input dummy for type 0) in
+ * Module.parameters() order.  The early out is the real rule (also with test_mode 1).
+ */
+typedef struct {
+    int32_t synthetic_env_type;         /* 1 (RewardEnv); anything else: LENV_ERR_UNSUPPORTED */
+    int32_t reward_env_type;            /* 0, 1, 2, 5, 6; the info-vector types have no info here: LENV_ERR_UNSUPPORTED */
+    int32_t rn_hidden, rn_layers, rn_act;   /* the ENV section's hidden_size / hidden_layer / activation_fn */
+    float rn_prelu;                     /* the reward net's (never perturbed) nn.PReLU slope */
+    int32_t rn_layer_norm;              /* the ENV section's use_layer_norm: with rn_layers >= 2 and reward_env_type != 0 LENV_ERR_UNSUPPORTED */
+} lenv_td3d_rn_cfg;
+
+size_t lenv_td3d_rn_workspace_bytes(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_td3d_rn_cfg *rn /*HOST*/, int64_t chains);
+/* parameters of the reward net (the length of theta and of an eps row) */
+int64_t lenv_td3d_rn_num_params(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_td3d_rn_cfg *rn /*HOST*/);
+/* as lenv_td3d_inner_loop; tapes: train_reset rows are the real env's reset states */
+int lenv_td3d_rn_inner_loop(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_td3d_rn_cfg *rn /*HOST*/,
+                            const lenv_chain_hp *hp /*HOST struct of device arrays, may be NULL*/, const float *theta, const float *eps,
+                            const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                            const lenv_td3d_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace, size_t workspace_bytes,
+                            const lenv_td3_out *out /*HOST*/, void *stream);
 /* fresh agents: nn.Linear default init from the chain key's counter stream, LayerNorm weight 1 / bias 0 */
 int lenv_td3d_agent_init(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_chain_hp *hp /*may be NULL*/, const uint64_t *rng_keys,
                          int64_t chains, float *agent_init, void *stream);

@@ -129,6 +129,12 @@ class Td3dCfg(C.Structure):
                 ("step_budget", C.c_int64), ("se_layer_norm", C.c_int32), ("test_mode", C.c_int32), ("early_out_virtual_diff", C.c_double)]
 
 
+class Td3dRnCfg(C.Structure):
+    """lenv_td3d_rn_cfg: the RewardEnv (or, reward_env_type 0, the real env) that lenv_td3d_rn_inner_loop trains TD3_discrete_vary on."""
+    _fields_ = [("synthetic_env_type", C.c_int32), ("reward_env_type", C.c_int32), ("rn_hidden", C.c_int32), ("rn_layers", C.c_int32),
+                ("rn_act", C.c_int32), ("rn_prelu", C.c_float), ("rn_layer_norm", C.c_int32)]
+
+
 class Td3dTapes(C.Structure):
     keys = TD3D_TAPE_KEYS
     _fields_ = _tape_fields(TD3D_TAPE_KEYS)
@@ -141,7 +147,7 @@ class Td3Out(C.Structure):
 
 
 # lenv_struct_size(which) order (include/lenv_hip.h)
-ABI_STRUCTS = [MlpDesc, DdqnCfg, QlCfg, Td3Cfg, Td3dCfg, Tapes, InnerOut, QlOut, Td3Tapes, Td3Out, Td3dTapes, ChainHp, IcmIo]
+ABI_STRUCTS = [MlpDesc, DdqnCfg, QlCfg, Td3Cfg, Td3dCfg, Tapes, InnerOut, QlOut, Td3Tapes, Td3Out, Td3dTapes, ChainHp, IcmIo, Td3dRnCfg]
 
 _vp, _i32, _i64, _f64, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.POINTER
 # what follows the cfg (and hp / icm) of an inner-loop launch: theta, eps, worker, sign, agent_init, rng_keys, tapes, chains,
@@ -200,6 +206,10 @@ SIGNATURES = {
     "lenv_td3d_inner_loop": (C.c_int, [_P(Td3dCfg), _P(ChainHp), _vp, _vp, _vp, _vp, _vp, _vp, _P(Td3dTapes), _i64, _vp, C.c_size_t,
                                        _P(Td3Out), _vp]),
     "lenv_td3d_agent_init": (C.c_int, [_P(Td3dCfg), _P(ChainHp), _vp, _i64, _vp, _vp]),
+    "lenv_td3d_rn_workspace_bytes": (C.c_size_t, [_P(Td3dCfg), _P(Td3dRnCfg), _i64]),
+    "lenv_td3d_rn_num_params": (_i64, [_P(Td3dCfg), _P(Td3dRnCfg)]),
+    "lenv_td3d_rn_inner_loop": (C.c_int, [_P(Td3dCfg), _P(Td3dRnCfg), _P(ChainHp), _vp, _vp, _vp, _vp, _vp, _vp, _P(Td3dTapes), _i64, _vp,
+                                          C.c_size_t, _P(Td3Out), _vp]),
     "lenv_nes_worker_best": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "lenv_nes_worker_best_multi": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "lenv_nes_draw": (C.c_int, [C.c_uint64, C.c_uint64] + _NES_DRAW_TAIL),

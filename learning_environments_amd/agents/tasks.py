@@ -9,6 +9,7 @@ combination owns one fused kernel:
     QL / QL_cb / SARSA / SARSA_cb on a RewardEnv over a gridworld (type 1) -> lenv_ql_rn_inner_loop (BASELINE config 4)
     TD3  on a RewardEnv over the HalfCheetah stand-in -> lenv_td3_rn_inner_loop (BASELINE config 5)
     TD3_discrete_vary on a VirtualEnv (CartPole / Acrobot / MountainCar) -> lenv_td3d_inner_loop
+    TD3_discrete_vary on a RewardEnv over CartPole / Acrobot / MountainCar, or the real env itself (type 1) -> lenv_td3d_rn_inner_loop
 Anything else raises NotImplementedError, like the reference does for unknown agents."""
 import copy
 
@@ -16,7 +17,7 @@ import numpy as np
 import torch
 
 from ..config import (TABULAR_AGENTS, TD3_DISCRETE_ENVS, agent_layer_dims, agent_layer_norm_slice, ddqn_cfg_from_config, icm_layer_dims, ql_cfg_from_config,
-                      td3_cfg_from_config, td3_layer_dims, td3_layer_norm_slices, td3d_cfg_from_config)
+                      td3_cfg_from_config, td3_layer_dims, td3_layer_norm_slices, td3d_cfg_from_config, td3d_rn_cfg_from_config)
 from . import vary
 from .nes_common import linear_init_bounds, set_layer_norm_init, with_layer_norm_block
 
@@ -198,7 +199,8 @@ class Td3DiscreteTask(_VaryAgents):
     """TD3_discrete_vary on a VirtualEnv (agents/TD3_discrete_vary.py): one launch of lenv_td3d_inner_loop per generation.  With
     vary_hp (:21-26,119-157) every chain draws its own lr / batch_size / hidden_size / hidden_layer (agents/vary.py) and the launch is
     sized for the largest possible draw, like Td3VaryTask.  The fresh agents (nn.Linear default init, LayerNorm 1 / 0) are drawn on
-    the device from the chain keys."""
+    the device from the chain keys.  With synthetic_env_type 1 the chains train on a RewardEnv over the real env (or the real env
+    itself, reward_env_type 0) through lenv_td3d_rn_inner_loop; theta is then the reward net."""
     name = "td3_discrete_se"
 
     def __init__(self, config, engine, test_mode=0):
@@ -208,10 +210,13 @@ class Td3DiscreteTask(_VaryAgents):
         base = config["agents"]["td3_discrete_vary"]
         self.vary = bool(base["vary_hp"])
         self.cfg = td3d_cfg_from_config(_max_config(config, "td3_discrete_vary") if self.vary else config, test_mode=test_mode)
+        self.rn = td3d_rn_cfg_from_config(config)
+        if self.rn is not None:
+            self.name = "td3_discrete_rn"
         self._init_vary(base)
 
     def make_inner(self, chains, want_episode_stats=False):
-        return self.engine.make_inner_td3d(self.cfg, chains, want_episode_stats=want_episode_stats, vary=self.vary)
+        return self.engine.make_inner_td3d(self.cfg, chains, want_episode_stats=want_episode_stats, vary=self.vary, rn=self.rn)
 
     def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
         self._fresh_agents(inner, keys_t, draw_hp=self.vary)
@@ -253,6 +258,6 @@ def select_task(config, engine, synthetic_env, test_mode=0):
         return Td3RnTask(config, engine, **tm)
     if agent_name in ("td3_vary", "td3_icm_vary") and env_type in (0, 1) and config["env_name"] in TD3_ENVS:
         return Td3VaryTask(config, engine, **tm) if config["agents"]["td3_vary"]["vary_hp"] else Td3RnTask(config, engine, **tm)
-    if agent_name == "td3_discrete_vary" and env_type == 0 and config["env_name"] in TD3_DISCRETE_ENVS:
-        return Td3DiscreteTask(config, engine, **tm)
+    if agent_name == "td3_discrete_vary" and env_type in (0, 1) and config["env_name"] in TD3_DISCRETE_ENVS:
+        return Td3DiscreteTask(config, engine, **tm)           # type 1: RewardEnv over the real env / the real env itself (mode 0)
     raise NotImplementedError("inner agent '%s' on synthetic_env_type %s has no fused kernel yet" % (agent_name, env_type))

@@ -211,14 +211,14 @@ TD3_DISCRETE_ENVS = ("CartPole-v0", "Acrobot-v1", "MountainCar-v0")      # discr
 
 
 def td3d_cfg_from_config(config, rng_mode=_lib.RNG_COUNTER, **overrides):
-    """TD3_discrete_vary + VirtualEnv on CartPole-v0 / Acrobot-v1 / MountainCar-v0.  Fields read at reference
-    agents/TD3_discrete_vary.py:30-42, models/actor_critic.py:27-31 (gumbel_softmax_temp / _hard), models/model_utils.py:5-29
-    (use_layer_norm), agents/base_agent.py:9-26, envs/env_wrapper.py:106-110 (max_action 1 for these envs)."""
+    """TD3_discrete_vary + VirtualEnv (synthetic_env_type 0) or RewardEnv (1, see td3d_rn_cfg_from_config) on CartPole-v0 / Acrobot-v1 /
+    MountainCar-v0.  Fields read at reference agents/TD3_discrete_vary.py:30-42, models/actor_critic.py:27-31 (gumbel_softmax_temp / _hard),
+    models/model_utils.py:5-29 (use_layer_norm), agents/base_agent.py:9-26, envs/env_wrapper.py:106-110 (max_action 1 for these envs)."""
     env_name = config["env_name"]
     if env_name not in TD3_DISCRETE_ENVS:
         raise NotImplementedError("TD3_discrete_vary fused kernel: real env '%s'" % env_name)
-    if int(config["agents"]["gtn"].get("synthetic_env_type", 0)) != 0:
-        raise NotImplementedError("TD3_discrete_vary trains on a VirtualEnv here (synthetic_env_type 0)")
+    if int(config["agents"]["gtn"].get("synthetic_env_type", 0)) not in (0, 1):
+        raise NotImplementedError("TD3_discrete_vary trains on a VirtualEnv (synthetic_env_type 0) or a RewardEnv (1) here")
     S, A = ENV_DIMS[env_name]
     e = config["envs"][env_name]
     a = config["agents"]["td3_discrete_vary"]
@@ -244,6 +244,25 @@ def td3d_cfg_from_config(config, rng_mode=_lib.RNG_COUNTER, **overrides):
     for k, v in overrides.items():
         setattr(cfg, k, v)
     return cfg
+
+
+def td3d_rn_cfg_from_config(config):
+    """The RewardEnv of a TD3_discrete_vary config with synthetic_env_type 1 (lenv_td3d_rn_cfg; None for a VirtualEnv): the `envs` section
+    describes the reward network (envs/reward_env.py:8-59).  The info-vector reward types raise ValueError like RewardEnv._calc_reward on
+    an env whose info dict is empty (reward_env.py:90-92), as the classic-control envs' is."""
+    if int(config["agents"]["gtn"].get("synthetic_env_type", 0)) != 1:
+        return None
+    e = config["envs"][config["env_name"]]
+
+    def val(v):
+        return float(v[1]) if isinstance(v, list) else v
+    t = int(val(e["reward_env_type"]))
+    if t in (3, 4, 7, 8, 101, 102):
+        raise ValueError('No info dict provided by environment')
+    if t not in (0, 1, 2, 5, 6):
+        raise NotImplementedError('Unknown reward_env_type: ' + str(t))
+    return _lib.Td3dRnCfg(synthetic_env_type=1, reward_env_type=t, rn_hidden=int(val(e["hidden_size"])), rn_layers=max(1, int(val(e["hidden_layer"]))),
+                          rn_act=_lib.ACT[e["activation_fn"]], rn_prelu=0.25, rn_layer_norm=1 if e.get("use_layer_norm", False) else 0)
 
 
 def td3_layer_norm_slices(cfg):

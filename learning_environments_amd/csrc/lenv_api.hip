@@ -19,6 +19,7 @@ extern "C" int64_t lenv_struct_size(int32_t which)
     case 10: return sizeof(lenv_td3d_tapes);
     case 11: return sizeof(lenv_chain_hp);
     case 12: return sizeof(lenv_icm_io);
+    case 13: return sizeof(lenv_td3d_rn_cfg);
     default: return LENV_ERR_INVALID;
     }
 }

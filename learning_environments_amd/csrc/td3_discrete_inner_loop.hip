@@ -14,6 +14,10 @@
 // rows between a product and its activation (forward: one thread per row, sequential sums as the oracle; backward: column
 // sums for the shared weight / bias per LayerNorm position, then one thread per row), the Gumbel-softmax head with its
 // backward, the annealed temperature, and the argmax hand-over to the SE / the real env.
+//
+// RENV instantiations (lenv_td3d_rn_inner_loop): the training env is RewardEnv(real env) (envs/reward_env.py:61-133), or -- reward
+// type 0 -- the real env itself (experiments/syn_env_run_vary_hp.py:47-54, mode 0).  The chain steps the real env's fp64 physics
+// (TimeLimit: done at max_steps) and shapes the reward with its perturbed reward net, as the DDQN kernel's RENV path does.
 #include "lenv_gemm.cuh"
 #include "lenv_ln.cuh"
 
@@ -67,6 +71,7 @@ struct Td3dArgs {
     const double *hp_lr; const int32_t *hp_batch, *hp_hidden, *hp_layers;
     int64_t a_params, a_targets, a_m, a_v, a_grad, a_replay, a_xc, a_xn, a_xa, a_hc1[TD_MAXL], a_hc2[TD_MAXL], a_ha[TD_MAXL], a_ht[TD_MAXL],
         a_xh1[TD_MAXL], a_xh2[TD_MAXL], a_xha[TD_MAXL], a_rs1, a_rs2, a_rsa, a_d[2], a_dx, a_raw, a_ys, a_dz, a_meter, a_se;
+    lenv_td3d_rn_cfg rn;                       // RENV instantiations: the reward net (theta / P_se are its parameters)
 };
 
 // natural-log based Gumbel(0,1) draw from one counter value (oracle: orc_gumbel)
@@ -110,7 +115,7 @@ __device__ __forceinline__ void gumbel_softmax_row(const float *raw, const float
     if (ys) for (int k = 0; k < A; ++k) ys[k] = y[k];
 }
 
-template <int ENVD>
+template <int ENVD, bool RENV = false>
 __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs a)
 {
     extern __shared__ __align__(16) float lds[];
@@ -141,6 +146,10 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
     // cfg.se_layer_norm: the SE nets' own LayerNorm -- never perturbed by NES (nn.Linear modules only, GTN_worker.py:156-175), so no parameters
     // in theta: ln == 2 marks a position that normalises with the constructor's weight 1 / bias 0
     if (cfg.se_layer_norm != 0 && Lse >= 2) mo_se[0].ln = mo_se[1].ln = mo_se[2].ln = 2;
+    // RENV: RewardEnv.build_reward_net (reward_env.py:29-53): S -> hidden... -> 1, or the 1-input dummy of type 0 that is never evaluated
+    [[maybe_unused]] DMlpOff mo_rn;
+    [[maybe_unused]] const int rtype = a.rn.reward_env_type;
+    if constexpr (RENV) dmlp_off(mo_rn, rtype == 0 ? 1 : S, a.rn.rn_hidden, a.rn.rn_layers, 1, 0);
     const int Pa = mo_actor.P, Pc = mo_critic.P, P = Pa + 2 * Pc;
     const int act_id = cfg.act;
     const float prelu = cfg.prelu, ma = (float)cfg.max_action;
@@ -153,7 +162,7 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
     float *q1 = rowb + 2 * TD_MAXW;                                                     // [Bm] each
     float *q2 = q1 + Bm, *tq1 = q2 + Bm, *tq2 = tq1 + Bm, *rr = tq2 + Bm, *dd = rr + Bm, *dq1 = dd + Bm, *dq2 = dq1 + Bm;
     float *misc = dq2 + Bm;                                // [64]
-    double *xs_d = reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(misc + 64) + 7) & ~(uintptr_t)7);   // [4] train env state
+    double *xs_d = reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(misc + 64) + 7) & ~(uintptr_t)7);   // [4] train env state (RENV)
     double *xt_d = xs_d + 4;                              // [T][4] test env states
     double *ret = xt_d + 4 * T;                           // [T]
     float *ep_rew = reinterpret_cast<float *>(ret + T);   // [T]
@@ -162,7 +171,7 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
     float *state = reinterpret_cast<float *>(tflag + T);  // [8] current observation (fp32)
     float *action = state + 8;                            // [8]
     float *newrow = action + 8;                           // [32] replay row [s | a | s' | r | done]
-    float *xse = newrow + 32;                             // [16] SE input cat(one_hot, state)
+    float *xse = newrow + 32;                             // [16] SE input cat(one_hot, state); RENV: phi(s), phi(s')
     float *nse = xse + 16;                                // [16] SE outputs [s' | r | done]
     volatile float *ctrl = misc;
     volatile int *ictrl = reinterpret_cast<volatile int *>(misc + 32);
@@ -431,8 +440,11 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
             float ob[8];
             real_env_obs(ENVD, st4, ob);
             for (int i = 0; i < S; ++i) state[i] = ob[i];
+            if constexpr (RENV) for (int i = 0; i < 4; ++i) xs_d[i] = st4[i];     // RewardEnv.reset -> real_env.reset(): the env's own state
         }
         __syncthreads();
+        [[maybe_unused]] float phi_s = 0.0f;                     // RENV: phi(s) of the state the env is in, once evaluated
+        [[maybe_unused]] bool have_phi = false;
         int ep_len = 0;
         float tr_reward = 0.0f;                                  // base_agent.py:102,121 episode_reward += reward (fp32 tensors; uniform over the threads)
         for (int t = 0; t < cfg.max_steps; ++t) {
@@ -458,18 +470,54 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
                 ++n_actn;
             }
             TDP_MARK(0);                                   // select_train_action
-            // ---- env.step(action.argmax()) -> EnvWrapper.step: one-hot of the index -> VirtualEnv.step (virtual_env.py:43-54): the
-            // three SE nets on cat(one_hot, state); reward / done see the pre-transition state ----
-            if (tid == 0) {
-                const int a_idx = argmax_first(action, A);
-                for (int k = 0; k < A; ++k) xse[k] = k == a_idx ? 1.0f : 0.0f;
-                for (int i = 0; i < S; ++i) { xse[A + i] = state[i]; newrow[i] = state[i]; }
-                for (int k = 0; k < A; ++k) newrow[S + k] = action[k];
+            if constexpr (RENV) {
+                // ---- env.step(action.argmax()) -> RewardEnv.step (reward_env.py:61-66): the real transition (TimeLimit: done at
+                // max_steps), reward = _calc_reward(state, next_state, reward) with the perturbed reward net (:68-133; as lenv_rn_shape_rows) ----
+                if (tid == 0) {
+                    const int a_idx = argmax_first(action, A);
+                    for (int i = 0; i < S; ++i) newrow[i] = state[i];
+                    for (int k = 0; k < A; ++k) newrow[S + k] = action[k];
+                    double st4[4], rew; int dn;
+                    for (int i = 0; i < 4; ++i) st4[i] = xs_d[i];
+                    real_env_step(ENVD, st4, a_idx, rew, dn);
+                    if (t + 1 >= cfg.max_steps) dn = 1;
+                    for (int i = 0; i < 4; ++i) xs_d[i] = st4[i];
+                    float ob[8];
+                    real_env_obs(ENVD, st4, ob);
+                    for (int i = 0; i < S; ++i) nse[i] = ob[i];
+                    nse[S] = (float)rew; nse[S + 1] = dn ? 1.0f : 0.0f;
+                }
+                __syncthreads();
+                if (rtype != 0) {                                           // type 0: the real reward passes through
+                    if ((rtype == 1 || rtype == 2) && !have_phi) { mlp_row1(sep, mo_rn, state, xse, 0, a.rn.rn_act, a.rn.rn_prelu); phi_s = xse[0]; }
+                    mlp_row1(sep, mo_rn, nse, xse, 1, a.rn.rn_act, a.rn.rn_prelu);
+                    const float phi_s2 = xse[1], r32 = nse[S];
+                    float shaped;
+                    switch (rtype) {
+                    case 1: shaped = g32 * phi_s2 - phi_s; break;
+                    case 2: shaped = (r32 + g32 * phi_s2) - phi_s; break;
+                    case 5: shaped = phi_s2; break;
+                    default: shaped = r32 + phi_s2; break;                  // 6
+                    }
+                    phi_s = phi_s2; have_phi = true;
+                    __syncthreads();
+                    if (tid == 0) nse[S] = shaped;
+                    __syncthreads();
+                }
+            } else {
+                // ---- env.step(action.argmax()) -> EnvWrapper.step: one-hot of the index -> VirtualEnv.step (virtual_env.py:43-54): the
+                // three SE nets on cat(one_hot, state); reward / done see the pre-transition state ----
+                if (tid == 0) {
+                    const int a_idx = argmax_first(action, A);
+                    for (int k = 0; k < A; ++k) xse[k] = k == a_idx ? 1.0f : 0.0f;
+                    for (int i = 0; i < S; ++i) { xse[A + i] = state[i]; newrow[i] = state[i]; }
+                    for (int k = 0; k < A; ++k) newrow[S + k] = action[k];
+                }
+                __syncthreads();
+                mlp_row1(sep, mo_se[0], xse, nse, 0, se_act, cfg.se_prelu);
+                mlp_row1(sep + mo_se[0].P, mo_se[1], xse, nse, S, se_act, cfg.se_prelu);
+                mlp_row1(sep + mo_se[0].P + mo_se[1].P, mo_se[2], xse, nse, S + 1, se_act, cfg.se_prelu);
             }
-            __syncthreads();
-            mlp_row1(sep, mo_se[0], xse, nse, 0, se_act, cfg.se_prelu);
-            mlp_row1(sep + mo_se[0].P, mo_se[1], xse, nse, S, se_act, cfg.se_prelu);
-            mlp_row1(sep + mo_se[0].P + mo_se[1].P, mo_se[2], xse, nse, S + 1, se_act, cfg.se_prelu);
             if (tid < S) newrow[S + A + tid] = nse[tid];
             if (tid == 64) { newrow[2 * S + A] = nse[S]; newrow[2 * S + A + 1] = nse[S + 1]; }
             __syncthreads();
@@ -614,7 +662,8 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
             meter[episode] = tm;
             if (a.out.episode_test_mean) a.out.episode_test_mean[chain * cfg.train_episodes + episode] = tm;
             // early out (base_agent.py:49-62,141-148): break_env = the test env (real rule) or, without one, the training env itself
-            ictrl[3] = learning && meter_env_solved(meter, episode + 1, cfg.early_out_num, no_test_env && (true), cfg.solved_reward,
+            // (the virtual rule on a VirtualEnv, the real rule on a RewardEnv / the real env)
+            ictrl[3] = learning && meter_env_solved(meter, episode + 1, cfg.early_out_num, no_test_env && !RENV, cfg.solved_reward,
                                                     cfg.early_out_virtual_diff, episode, cfg.init_episodes);
         }
         __syncthreads();
@@ -708,7 +757,8 @@ __global__ void td3d_agent_init_kernel(lenv_td3d_cfg cfg, const int32_t *hp_hidd
 
 using namespace lenv;
 
-static int td3d_layout(const lenv_td3d_cfg *cfg, Td3dArgs &a, size_t *lds_bytes)
+// rn (may be null): the RENV launch -- the reward net takes the SE nets' place in theta and in the arena
+static int td3d_layout(const lenv_td3d_cfg *cfg, Td3dArgs &a, size_t *lds_bytes, const lenv_td3d_rn_cfg *rn = nullptr)
 {
     const int H = cfg->hidden, L = cfg->layers, B = cfg->batch_size, T = cfg->test_episodes, Hse = cfg->se_hidden;
     const int S = cfg->state_dim, A = cfg->action_dim, SA = S + A;
@@ -716,15 +766,27 @@ static int td3d_layout(const lenv_td3d_cfg *cfg, Td3dArgs &a, size_t *lds_bytes)
           (cfg->env_id == LENV_ENV_MOUNTAINCAR && S == 2 && A == 3)))
         return LENV_ERR_UNSUPPORTED;
     if (cfg->act == LENV_ACT_PRELU) return LENV_ERR_UNSUPPORTED;   // trained PReLU slope of the agent nets: not a parameter here
-    if (L < 1 || L > TD_MAXL || H < 1 || H > TD_MAXW || B < 1 || B > TD_MAXB || T < 1 || T > 64 || cfg->se_layers < 1 || cfg->se_layers > TD_MAXL ||
-        Hse > TD_MAXW || Hse < 1 || cfg->policy_delay < 1 || cfg->max_steps < 1 || cfg->train_episodes < 0 || !(cfg->gumbel_temp > 0.0))
+    if (L < 1 || L > TD_MAXL || H < 1 || H > TD_MAXW || B < 1 || B > TD_MAXB || T < 1 || T > 64 || cfg->policy_delay < 1 || cfg->max_steps < 1 ||
+        cfg->train_episodes < 0 || !(cfg->gumbel_temp > 0.0))
         return LENV_ERR_UNSUPPORTED;
     DMlpOff ma, mc, ms;
     dmlp_off(ma, S, H, L, A, cfg->use_layer_norm);
     dmlp_off(mc, SA, H, L, 1, cfg->use_layer_norm);
     a.P = ma.P + 2 * mc.P;
-    dmlp_off(ms, SA, Hse, cfg->se_layers, S, 0); a.P_se = ms.P;
-    dmlp_off(ms, SA, Hse, cfg->se_layers, 1, 0); a.P_se += 2 * ms.P;
+    if (rn) {
+        // RewardEnv over the real env: the reward types the classic-control envs can serve (their info dict is empty, reward_env.py:90-92),
+        // a reward net without LayerNorm (as the DDQN kernel's RENV path)
+        const int t = rn->reward_env_type;
+        if (rn->synthetic_env_type != 1 || !(t == 0 || t == 1 || t == 2 || t == 5 || t == 6)) return LENV_ERR_UNSUPPORTED;
+        if (rn->rn_layers < 1 || rn->rn_layers > TD_MAXL || rn->rn_hidden < 1 || rn->rn_hidden > TD_MAXW) return LENV_ERR_UNSUPPORTED;
+        if (rn->rn_layer_norm && rn->rn_layers >= 2 && t != 0) return LENV_ERR_UNSUPPORTED;
+        if (rn->rn_act < LENV_ACT_IDENTITY || rn->rn_act > LENV_ACT_PRELU) return LENV_ERR_UNSUPPORTED;
+        dmlp_off(ms, t == 0 ? 1 : S, rn->rn_hidden, rn->rn_layers, 1, 0); a.P_se = ms.P;
+    } else {
+        if (cfg->se_layers < 1 || cfg->se_layers > TD_MAXL || Hse > TD_MAXW || Hse < 1) return LENV_ERR_UNSUPPORTED;
+        dmlp_off(ms, SA, Hse, cfg->se_layers, S, 0); a.P_se = ms.P;
+        dmlp_off(ms, SA, Hse, cfg->se_layers, 1, 0); a.P_se += 2 * ms.P;
+    }
     a.RS = (2 * S + A + 2 + 3) & ~3;
     int64_t cap = (int64_t)cfg->train_episodes * cfg->max_steps;
     if (cap > cfg->rb_size) cap = cfg->rb_size;
@@ -802,10 +864,10 @@ extern "C" int lenv_td3d_agent_init(const lenv_td3d_cfg *cfg, const lenv_chain_h
     return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
 }
 
-extern "C" int lenv_td3d_inner_loop(const lenv_td3d_cfg *cfg, const lenv_chain_hp *hp, const float *theta, const float *eps,
-                                    const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
-                                    const lenv_td3d_tapes *tapes, int64_t chains, void *workspace, size_t workspace_bytes,
-                                    const lenv_td3_out *out, void *stream)
+static int td3d_launch(const lenv_td3d_cfg *cfg, const lenv_td3d_rn_cfg *rn, const lenv_chain_hp *hp, const float *theta, const float *eps,
+                       const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                       const lenv_td3d_tapes *tapes, int64_t chains, void *workspace, size_t workspace_bytes,
+                       const lenv_td3_out *out, void *stream)
 {
     if (hp && (!hp->lr || !hp->batch_size || !hp->q_hidden || !hp->q_layers)) return LENV_ERR_INVALID;
     if (!cfg || !theta || !agent_init || !out || !out->score || !workspace || chains < 0) return LENV_ERR_INVALID;
@@ -815,7 +877,7 @@ extern "C" int lenv_td3d_inner_loop(const lenv_td3d_cfg *cfg, const lenv_chain_h
     if (chains == 0) return LENV_OK;
     Td3dArgs a;
     size_t lds_bytes;
-    const int rc = td3d_layout(cfg, a, &lds_bytes);
+    const int rc = td3d_layout(cfg, a, &lds_bytes, rn);
     if (rc != LENV_OK) return rc;
     if (workspace_bytes < (size_t)chains * a.arena_stride * sizeof(float)) return LENV_ERR_WORKSPACE;
     a.cfg = *cfg;
@@ -825,14 +887,50 @@ extern "C" int lenv_td3d_inner_loop(const lenv_td3d_cfg *cfg, const lenv_chain_h
     a.out = *out;
     a.hp_lr = hp ? hp->lr : nullptr; a.hp_batch = hp ? hp->batch_size : nullptr;
     a.hp_hidden = hp ? hp->q_hidden : nullptr; a.hp_layers = hp ? hp->q_layers : nullptr;
+    a.rn = rn ? *rn : lenv_td3d_rn_cfg{};
     void (*kern)(const Td3dArgs) = nullptr;
-    if (cfg->env_id == LENV_ENV_CARTPOLE) kern = td3_discrete_inner_kernel<LENV_ENV_CARTPOLE>;
-    else if (cfg->env_id == LENV_ENV_ACROBOT) kern = td3_discrete_inner_kernel<LENV_ENV_ACROBOT>;
-    else kern = td3_discrete_inner_kernel<LENV_ENV_MOUNTAINCAR>;
+    if (cfg->env_id == LENV_ENV_CARTPOLE) kern = rn ? td3_discrete_inner_kernel<LENV_ENV_CARTPOLE, true> : td3_discrete_inner_kernel<LENV_ENV_CARTPOLE>;
+    else if (cfg->env_id == LENV_ENV_ACROBOT) kern = rn ? td3_discrete_inner_kernel<LENV_ENV_ACROBOT, true> : td3_discrete_inner_kernel<LENV_ENV_ACROBOT>;
+    else kern = rn ? td3_discrete_inner_kernel<LENV_ENV_MOUNTAINCAR, true> : td3_discrete_inner_kernel<LENV_ENV_MOUNTAINCAR>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return LENV_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+}
+
+extern "C" int lenv_td3d_inner_loop(const lenv_td3d_cfg *cfg, const lenv_chain_hp *hp, const float *theta, const float *eps,
+                                    const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                                    const lenv_td3d_tapes *tapes, int64_t chains, void *workspace, size_t workspace_bytes,
+                                    const lenv_td3_out *out, void *stream)
+{
+    return td3d_launch(cfg, nullptr, hp, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, stream);
+}
+
+extern "C" size_t lenv_td3d_rn_workspace_bytes(const lenv_td3d_cfg *cfg, const lenv_td3d_rn_cfg *rn, int64_t chains)
+{
+    if (!cfg || !rn || chains < 0) return 0;
+    Td3dArgs a;
+    size_t lds;
+    if (td3d_layout(cfg, a, &lds, rn) != LENV_OK) return 0;
+    return (size_t)chains * a.arena_stride * sizeof(float) + 256;
+}
+
+extern "C" int64_t lenv_td3d_rn_num_params(const lenv_td3d_cfg *cfg, const lenv_td3d_rn_cfg *rn)
+{
+    if (!cfg || !rn) return LENV_ERR_INVALID;
+    Td3dArgs a;
+    size_t lds;
+    const int rc = td3d_layout(cfg, a, &lds, rn);
+    return rc != LENV_OK ? rc : a.P_se;
+}
+
+extern "C" int lenv_td3d_rn_inner_loop(const lenv_td3d_cfg *cfg, const lenv_td3d_rn_cfg *rn, const lenv_chain_hp *hp, const float *theta,
+                                       const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
+                                       const uint64_t *rng_keys, const lenv_td3d_tapes *tapes, int64_t chains, void *workspace,
+                                       size_t workspace_bytes, const lenv_td3_out *out, void *stream)
+{
+    if (!rn) return LENV_ERR_INVALID;
+    return td3d_launch(cfg, rn, hp, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, stream);
 }
 
 #ifdef LENV_PHASE_TIMING

@@ -386,31 +386,43 @@ class Td3InnerLoop(_InnerLoopBase):
 
 class Td3DiscreteInnerLoop(_InnerLoopBase):
     """Owns the workspace/outputs of lenv_td3d_inner_loop (TD3_discrete_vary on a VirtualEnv) for a fixed (cfg, chains).
-    vary=True: cfg carries the maximal batch_size / hidden / layers, every chain runs with its own draw (set_hp)."""
+    vary=True: cfg carries the maximal batch_size / hidden / layers, every chain runs with its own draw (set_hp).
+    rn (a _lib.Td3dRnCfg): the chains train on RewardEnv(real env) / the real env instead, through lenv_td3d_rn_inner_loop; theta is the
+    reward net."""
     Out, Tapes, final, trace_spec = Td3Out, Td3dTapes, "final_params", _TD3_TRACE
     cfg_type, hp_fields = Td3dCfg, ("batch_size", "hidden", "layers")
     num_params_fn, agent_init_fn = "lenv_td3d_num_params", "lenv_td3d_agent_init"
 
-    def __init__(self, cfg, chains, want_episode_stats=True, want_final_params=False, trace_cap=0, vary=False):
+    def __init__(self, cfg, chains, want_episode_stats=True, want_final_params=False, trace_cap=0, vary=False, rn=None):
         super().__init__(cfg, chains)
         L = _lib.lib()
         pa, pc = C.c_int64(), C.c_int64()
         self.p_agent = self._num_params(cfg, C.byref(pa), C.byref(pc))
         self.p_actor, self.p_critic = pa.value, pc.value
-        self.p_theta = int(L.lenv_td3d_se_num_params(C.byref(cfg)))
+        self.rn = rn
+        if rn is None:
+            self.p_theta = int(L.lenv_td3d_se_num_params(C.byref(cfg)))
+            ws_bytes = L.lenv_td3d_workspace_bytes(C.byref(cfg), self.chains)
+        else:
+            self.p_theta = _count("lenv_td3d_rn_num_params", C.byref(cfg), C.byref(rn))
+            ws_bytes = L.lenv_td3d_rn_workspace_bytes(C.byref(cfg), C.byref(rn), self.chains)
         self._init_vary(vary)
         if not self.vary:
             self.agent_init = torch.zeros((self.chains, self.p_agent), dtype=torch.float32, device=self.dev)
-        self._alloc_outputs(L.lenv_td3d_workspace_bytes(C.byref(cfg), self.chains), want_episode_stats, want_final_params, trace_cap)
+        self._alloc_outputs(ws_bytes, want_episode_stats, want_final_params, trace_cap)
 
     def run(self, theta, eps, worker, sign, agent_init=None, rng_keys=None, tapes=None):
         if agent_init is None:
             agent_init = self.agent_init
         args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
         if theta.numel() != self.p_theta:
-            raise ValueError("theta must hold %d SE parameters" % self.p_theta)
-        rc = _lib.lib().lenv_td3d_inner_loop(C.byref(self.cfg), self._hp_arg(), *args)
-        _lib.check(rc, "lenv_td3d_inner_loop")
+            raise ValueError("theta must hold %d %s parameters" % (self.p_theta, "SE" if self.rn is None else "reward-net"))
+        if self.rn is None:
+            rc = _lib.lib().lenv_td3d_inner_loop(C.byref(self.cfg), self._hp_arg(), *args)
+            _lib.check(rc, "lenv_td3d_inner_loop")
+        else:
+            rc = _lib.lib().lenv_td3d_rn_inner_loop(C.byref(self.cfg), C.byref(self.rn), self._hp_arg(), *args)
+            _lib.check(rc, "lenv_td3d_rn_inner_loop")
         return self.score
 
 

@@ -170,6 +170,22 @@ if __name__ == "__main__":
         c = configs.fixed_work(configs.cartpole_syn_env_td3_discrete(32, hidden_size=128, batch_size=128, use_layer_norm=True, activation_fn="relu"), 3)
         c["envs"]["CartPole-v0"]["max_steps"] = 100
         run("TD3_discrete_vary + LayerNorm on a CartPole SE, pop 32 (128-wide relu nets, batch 128)", c, gens=1)
+    if "td3drn" in which:
+        # TD3_discrete_vary (the shipped section) on default_config_cartpole_reward_env.yaml's RewardEnv (PReLU 4-64-1, type 2) against the same
+        # agent on a CartPole SE, at 16 and 64 workers (48 / 192 chains); per-step cost = seconds per generation / mean env steps of a chain
+        per_step = lambda cfg, st, dt: dict(us_per_train_step_per_chain=1e6 * dt / max(1.0, st[:, 1].mean()))
+        for pop in (16, 64):
+            c = configs.cartpole_reward_env_ddqn(pop)
+            c["agents"]["gtn"]["agent_name"] = "TD3_discrete_vary"
+            c["agents"].pop("ddqn")
+            c["agents"]["td3_discrete_vary"] = configs._td3_discrete_section()
+            c = configs.fixed_work(c, 3)
+            c["envs"]["CartPole-v0"]["max_steps"] = 100
+            run("TD3_discrete_vary on a CartPole RewardEnv (type 2), pop %d (3 episodes x <= 100 steps, shipped 510-wide nets)" % pop, c, gens=1,
+                extra=per_step)
+            c = configs.fixed_work(configs.cartpole_syn_env_td3_discrete(pop), 3)
+            c["envs"]["CartPole-v0"]["max_steps"] = 100
+            run("TD3_discrete_vary on a CartPole SE, pop %d (3 episodes x 100 steps, shipped 510-wide nets)" % pop, c, gens=1, extra=per_step)
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1

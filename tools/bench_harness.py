@@ -1,7 +1,7 @@
 """The evaluation harness as an experiment runs it (reference experiments/syn_env_evaluate_cartpole_vary_hp_2.py __main__: 40 models x 10
 DDQN_vary agents per mode): run_vary_hp with all models in ONE fused launch against the model-by-model calls the reference's loop makes.
 Models: CartPole SEs of default_config_cartpole.yaml's shape whose reward net says ~1 per step (a stand-in for trained SEs: 200-step episodes,
-the virtual early-out after 20-30 episodes).  usage: python tools/bench_harness.py [model_num] [agents_num]"""
+the virtual early-out after 20-30 episodes).  usage: python tools/bench_harness.py [model_num] [agents_num] [agent] [mode]"""
 import json
 import os
 import sys
@@ -20,7 +20,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 def main():
     model_num = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     agents_num = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-    agent = sys.argv[3] if len(sys.argv) > 3 else None      # a sibling script's agent (DuelingDDQN_vary, td3_discrete_vary): mode 2, fused launch only
+    agent = sys.argv[3] if len(sys.argv) > 3 else None      # a sibling script's agent (DuelingDDQN_vary, td3_discrete_vary): fused launch only
+    agent_mode = int(sys.argv[4]) if len(sys.argv) > 4 else 2   # its run_vary_hp mode (0: the agents train on the real env)
     base = torch.load(os.path.join(HERE, "..", "tests", "golden", "ckpt_cartpole_se_reference_b.pt"), map_location="cpu", weights_only=False)
     d = tempfile.mkdtemp(prefix="lenv_harness_")
     gen = torch.Generator().manual_seed(1)
@@ -50,13 +51,13 @@ def main():
                 return v, r, c
         else:
             load = load_envs_and_config
-        rv.run_vary_hp(2, "warm", 1, agents_num, d, load, fn, "CartPole", out_dir=d)
+        rv.run_vary_hp(agent_mode, "warm", 1, agents_num, d, load, fn, "CartPole", out_dir=d)
         torch.cuda.synchronize()
         t0 = time.time()
-        rewards, steps, episodes = rv.run_vary_hp(2, "b", model_num, agents_num, d, load, fn, "CartPole", out_dir=d)
+        rewards, steps, episodes = rv.run_vary_hp(agent_mode, "b", model_num, agents_num, d, load, fn, "CartPole", out_dir=d)
         torch.cuda.synchronize()
         dt = time.time() - t0
-        print(json.dumps({"mode": 2, "agent": agent, "path": "one fused launch", "models": model_num, "agents": model_num * agents_num,
+        print(json.dumps({"mode": agent_mode, "agent": agent, "path": "one fused launch", "models": model_num, "agents": model_num * agents_num,
                           "seconds": round(dt, 3), "agents_per_s": round(model_num * agents_num / dt, 2), "train_steps": sum(s_[0] for s_ in steps),
                           "mean_episodes": round(sum(e[0] for e in episodes) / len(episodes), 1)}), flush=True)
         return
