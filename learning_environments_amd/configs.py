@@ -62,7 +62,7 @@ def acrobot_syn_env_ddqn(num_workers=256, max_iterations=50):
 def mountaincar_syn_env_ddqn(num_workers=16, max_iterations=50):
     """MountainCar-v0 SE (2+1 -> 128 -> 2/1/1, leakyrelu) + DDQN 2-256-256-3: the published values of
     default_config_mountaincar.yaml (gtn :5-26, ddqn :30-48, env :52-59).  100 random init episodes fill the replay buffer; the
-    two-hidden-layer Q-net runs in the GEMM-tiled kernel's plain-DQN mode."""
+    two-hidden-layer Q-net runs in the 256-wide wave-chain kernel (ddqn_wavechain_wide.hip; other modes: the GEMM-tiled kernel's plain-DQN mode)."""
     cfg = acrobot_syn_env_ddqn(num_workers, max_iterations)
     cfg["env_name"] = "MountainCar-v0"
     cfg["agents"]["gtn"].update(noise_std=0.05, step_size=1.0, time_max=300, score_transform_type=7, unsolved_weight=10000,

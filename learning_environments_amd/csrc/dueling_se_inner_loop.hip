@@ -948,6 +948,10 @@ static int dueling_layout(const lenv_ddqn_cfg *cfg, DuelArgs &a, size_t *lds_byt
             const int64_t wfl = lenv_wc_dueling_arena_floats(cfg, wshape, a.rb_cap, a.RS, a.P_se);
             if (wfl > a.arena_stride) a.arena_stride = wfl;
         }
+        if (lenv_wc_ddqn_wide_shape(cfg)) {            // ... and so does the 256-wide DDQN kernel (ddqn_wavechain_wide.hip)
+            const int64_t wfl = lenv_wc_ddqn_wide_arena_floats(cfg, a.rb_cap, a.RS);
+            if (wfl > a.arena_stride) a.arena_stride = wfl;
+        }
     }
     const size_t lds_floats = GemmShape<D_MAXI>::PS_FLOATS + GemmShape<D_MAXI>::QS_FLOATS + GEMM_QUEUE_MAX * sizeof(GemmCmd) / sizeof(float) +
                               3 * K * Hse + 3 * Hse + (S + 2) * Hse + 16 + 3 * Hse + (cfg->se_layers > 1 ? 3 * Hse : 0) + 3 * (size_t)(B > T ? B : T) * A + 3 * (size_t)(B > T ? B : T) * (1 + A) +
@@ -970,8 +974,10 @@ extern "C" int lenv_dueling_team_size(const lenv_ddqn_cfg *cfg, int64_t chains)
 {
     if (!cfg || chains < 1) return LENV_ERR_INVALID;
     if ((cfg->kernel_variant & (LENV_VARIANT_NO_WAVECHAIN | LENV_VARIANT_GENERIC)) || cfg->icm_enabled || cfg->rng_mode != LENV_RNG_COUNTER || cfg->synthetic_env_type != 0 ||
-        cfg->same_action_num > 1 || !lenv_wc_dueling_shape(cfg))
+        cfg->same_action_num > 1)
         return 1;
+    if (lenv_wc_ddqn_wide_shape(cfg)) return lenv_wc_ddqn_wide_team(cfg, chains);
+    if (!lenv_wc_dueling_shape(cfg)) return 1;
     return lenv_wc_dueling_team(cfg, lenv_wc_dueling_shape(cfg), chains);
 }
 
@@ -1056,6 +1062,9 @@ extern "C" int lenv_dueling_se_inner_loop_icm(const lenv_ddqn_cfg *cfg, const le
                 return lenv_wc_dueling_launch(wshape, cfg, theta, eps, worker, sign, agent_init, rng_keys, chains, a.arena, a.arena_stride, a.rb_cap,
                                               a.RS, a.P, a.P_se, a.se_net_size, out, static_cast<hipStream_t>(stream));
             }
+            if (lenv_wc_ddqn_wide_shape(cfg))           // default_config_mountaincar.yaml's DDQN 2-256-256-3 (ddqn_wavechain_wide.hip)
+                return lenv_wc_ddqn_wide_launch(cfg, theta, eps, worker, sign, agent_init, rng_keys, chains, a.arena, a.arena_stride, a.rb_cap,
+                                                a.RS, a.P, a.P_se, a.se_net_size, out, static_cast<hipStream_t>(stream));
         }
         if (!off && !cfg->icm_enabled && !hp && cfg->rng_mode == LENV_RNG_COUNTER && !out->trace_action && cfg->synthetic_env_type == 0) {
             if (matches(kDuelShapes[1])) kern = dueling_se_inner_kernel<false, 1>;

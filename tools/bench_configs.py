@@ -138,11 +138,16 @@ if __name__ == "__main__":
                 c["agents"]["gtn"]["kernel_variant"] = variant
                 run("%s + TD3 (B 256, policy_delay 2, ten test episodes) pop 16 (3 episodes x %d steps), %s" % (label0, steps, label), c, gens=2)
     if "mountaincar_ddqn" in which:
-        # default_config_mountaincar.yaml (DDQN 2-256-256-3 relu, B = 128, ten test episodes, 16 workers = 48 chains): GEMM-queue kernel, no wave-chain shape
-        c = configs.fixed_work(configs.mountaincar_syn_env_ddqn(16), 3)
-        c["agents"]["ddqn"]["init_episodes"] = 1
-        c["envs"]["MountainCar-v0"]["max_steps"] = 100
-        run("MountainCar SE + DDQN 2-256-256-3 pop 16 (3 episodes x 100 steps), GEMM-queue kernel", c, gens=2)
+        # default_config_mountaincar.yaml (DDQN 2-256-256-3 relu, B = 128, ten test episodes, 16 workers = 48 chains): the 256-wide wave-chain
+        # kernel (teams of 4 at 48 chains, 2 at 96), then the GEMM-queue kernel (gtn.kernel_variant = NO_WAVECHAIN)
+        from learning_environments_amd import _lib
+        for pop in (16, 32):
+            for variant, label in ((0, "wave-chain kernel"), (_lib.VARIANT_NO_WAVECHAIN, "GEMM-queue kernel")):
+                c = configs.fixed_work(configs.mountaincar_syn_env_ddqn(pop), 3)
+                c["agents"]["ddqn"]["init_episodes"] = 1
+                c["envs"]["MountainCar-v0"]["max_steps"] = 100
+                c["agents"]["gtn"]["kernel_variant"] = variant
+                run("MountainCar SE + DDQN 2-256-256-3 pop %d (3 episodes x 100 steps), %s" % (pop, label), c, gens=2)
     if "cartpole_rn_ddqn" in which:
         # default_config_cartpole_reward_env.yaml (DDQN 4-64-2 leakyrelu, B = 192, trained on the real CartPole with a learned reward, 16 workers)
         # round 6: the register-resident kernel's RENV instantiation (real-env training step + reward net on the env wave), then the GEMM-queue kernel
