@@ -165,7 +165,8 @@ typedef struct {
 int lenv_abi_version(void);
 /* sizeof of the ABI structs as the library was compiled (a binding checks its mirror against it): which = 0 lenv_mlp_desc, 1 lenv_ddqn_cfg,
  * 2 lenv_ql_cfg, 3 lenv_td3_cfg, 4 lenv_td3d_cfg, 5 lenv_tapes, 6 lenv_inner_out, 7 lenv_ql_out, 8 lenv_td3_tapes, 9 lenv_td3_out,
- * 10 lenv_td3d_tapes, 11 lenv_chain_hp, 12 lenv_icm_io, 13 lenv_td3d_rn_cfg; anything else: LENV_ERR_INVALID.  HOST. */
+ * 10 lenv_td3d_tapes, 11 lenv_chain_hp, 12 lenv_icm_io, 13 lenv_td3d_rn_cfg, 14 lenv_ppo_cfg, 15 lenv_ppo_tapes, 16 lenv_ppo_out; anything else:
+ * LENV_ERR_INVALID.  HOST. */
 int64_t lenv_struct_size(int32_t which);
 const char *lenv_error_string(int code);
 /* number of parameters of an MLP / of the three-net SE */
@@ -521,6 +522,86 @@ int lenv_td3d_rn_inner_loop(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_td3d_r
 /* fresh agents: nn.Linear default init from the chain key's counter stream, LayerNorm weight 1 / bias 0 */
 int lenv_td3d_agent_init(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_chain_hp *hp /*may be NULL*/, const uint64_t *rng_keys,
                          int64_t chains, float *agent_init, void *stream);
+
+/*
+ * PPO on a RewardEnv over a continuous real env (agents/PPO.py:14-188, models/actor_critic.py:38-61,74-81, envs/reward_env.py:61-133):
+ * one 512-thread workgroup per chain runs PPO.train(env=reward_env, test_env=real_env) and the final agent.test(real_env) of
+ * GTN_Worker.calc_score (agents/GTN_worker.py:187-221).  Real envs: the HalfCheetah-v3 STAND-IN, Pendulum-v0, MountainCarContinuous-v0
+ * (those of the TD3 cfg); reward_env_type as there, 0 = the real env itself: theta is not read.
+ *   - acting, train and test alike (actor_critic.py:45-49): a = tanh(net_old(s)) + std_old * z, z ~ N(0,1)^A, std_old clamped in place to
+ *     >= 0.001 first; the action is neither rescaled nor clipped;
+ *   - a row (s, a, r, done) per chosen action; PPO.learn runs once time_step / max_steps > update_episodes (a double comparison;
+ *     time_step += same_action_num per row) on ALL rows since the last call -- lenv_ppo_rows(cfg) of them, possibly in the middle of
+ *     an episode -- and time_step restarts at 0;
+ *   - learn: discounted returns by one backward scan that restarts only where done > 0.5, normalised with the unbiased std; ppo_epochs
+ *     full-batch Adam steps (one step counter over action_std, actor.net, critic.net) on the clipped surrogate + vf_coef * MSE -
+ *     ent_coef * entropy; Actor_PPO.evaluate clamps action_std to >= 0.01 AFTER the log-probabilities and BEFORE the entropy, and the
+ *     gradient sees the clamped value wherever autograd saved the parameter itself;
+ *   - no time-out (PPO.train never calls time_is_up), no init_episodes gate on acting or learning; after every episode test_episodes
+ *     real-env episodes feed the meter, early out by the real rule from init_episodes on.
+ * Flat agent parameters (agent_init, final_params, learn_params rows): action_std [A] | actor.net (S -> A) | critic.net (S -> 1), each net
+ * in the MLP layout above.  Supported: hidden <= 128, layers 1-2, lenv_ppo_rows(cfg) in [2, 2048], test_episodes <= 64, no agent PReLU, LDS within
+ * 160 KiB: anything else is LENV_ERR_UNSUPPORTED from every query below.  The cfg has no LayerNorm fields: the kernel normalises nowhere, and a
+ * binding refuses `use_layer_norm` in the ppo section, or in the ENV section of a reward net with two or more hidden layers, itself
+ * (config.ppo_cfg_from_config does).
+ */
+typedef struct {
+    int32_t env_id, state_dim, action_dim, max_steps;
+    int32_t rn_hidden, rn_layers, rn_act;
+    float rn_prelu;
+    int32_t reward_env_type, info_dim;
+    int32_t hidden, layers, act;             /* actor.net / critic.net (the ppo section's hidden_size, max(1, hidden_layer), activation_fn) */
+    float prelu;
+    int32_t train_episodes, test_episodes, init_episodes, early_out_num;
+    int32_t ppo_epochs, same_action_num, rng_mode;
+    int32_t reserved;                        /* 0 */
+    double solved_reward, gamma, lr, action_std, vf_coef, ent_coef, eps_clip, update_episodes;
+    double adam_beta1, adam_beta2, adam_eps;
+} lenv_ppo_cfg;
+
+/* RNG tapes (parity mode); per-chain rows, strides in ROWS */
+typedef struct {
+    const float *act_noise;    int64_t act_noise_stride;      /* rows of A: the _standard_normal draw of actor_old.forward while training */
+    const float *test_noise;   int64_t test_noise_stride;     /* rows of A: the same inside BaseAgent.test, episode by episode */
+    const double *train_reset; int64_t train_reset_stride;    /* rows of the env's own state (17 / 2 / 2 doubles) */
+    const double *test_reset;  int64_t test_reset_stride;
+} lenv_ppo_tapes;
+
+typedef struct {
+    double *score;              /* [chains] */
+    int64_t *stats;             /* [chains,4] episodes_run, rows collected, learn calls, test_steps */
+    int32_t *status;            /* [chains] 0 ok; -4 more rows than lenv_ppo_rows between two learn calls (an internal error: learn fires at that
+                                 * count), -5 reset tape underrun, -7 noise tape underrun */
+    double *episode_test_mean;  /* [chains,train_episodes] */
+    int32_t *episode_len;       /* [chains,train_episodes] */
+    double *final_returns;      /* [chains,test_episodes] */
+    float *final_params;        /* [chains,P] */
+    int64_t trace_cap;
+    float *trace_action;        /* [chains,trace_cap,A] */
+    float *trace_state;         /* [chains,trace_cap,S] */
+    float *trace_next_state;    /* [chains,trace_cap,S] */
+    float *trace_reward;        /* [chains,trace_cap] shaped reward of the row */
+    float *trace_done;          /* [chains,trace_cap] */
+    int64_t learn_cap;          /* learn calls recorded per chain */
+    int32_t *learn_step;        /* [chains,learn_cap] rows collected over the whole run when the call fired (0 = no such call) */
+    float *learn_params;        /* [chains,learn_cap,P] parameters after the call (may be NULL) */
+} lenv_ppo_out;
+
+/* rows one learn call sees, or a negative LENV_ERR_*.  HOST. */
+int64_t lenv_ppo_rows(const lenv_ppo_cfg *cfg /*HOST*/);
+/* P = A + actor_params + critic_params, or a negative LENV_ERR_*.  HOST. */
+int64_t lenv_ppo_num_params(const lenv_ppo_cfg *cfg /*HOST*/, int64_t *actor_params /*HOST out*/, int64_t *critic_params /*HOST out*/);
+/* parameters of the reward net (length of theta and of an eps row; 0 for reward_env_type 0), or a negative LENV_ERR_*.  HOST. */
+int64_t lenv_ppo_rn_num_params(const lenv_ppo_cfg *cfg /*HOST*/);
+/* dynamic LDS bytes one chain needs for this cfg (staging buffers, command queue, a one-hidden-layer reward net, the rollout's rows), or a
+ * negative LENV_ERR_* -- UNSUPPORTED when they exceed the 160 KiB of a CU (a wide reward net on many inputs).  HOST. */
+int64_t lenv_ppo_rn_lds_bytes(const lenv_ppo_cfg *cfg /*HOST*/);
+/* workspace bytes for `chains` chains, or a negative LENV_ERR_* (UNSUPPORTED: a shape or option outside the list above).  HOST. */
+int64_t lenv_ppo_rn_workspace_bytes(const lenv_ppo_cfg *cfg /*HOST*/, int64_t chains);
+int lenv_ppo_rn_inner_loop(const lenv_ppo_cfg *cfg /*HOST*/, const float *theta, const float *eps, const int32_t *worker,
+                           const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                           const lenv_ppo_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace,
+                           size_t workspace_bytes, const lenv_ppo_out *out /*HOST*/, void *stream);
 
 /*
  * Batched forward of one MLP in the flat layout above: y [rows,out] = net(x [rows,in]) (models/model_utils.py:31-39;

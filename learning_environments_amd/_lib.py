@@ -146,8 +146,37 @@ class Td3Out(C.Structure):
                 ("trace_action", C.c_void_p), ("trace_state", C.c_void_p), ("trace_next_state", C.c_void_p), ("trace_reward", C.c_void_p)]
 
 
+PPO_TAPE_KEYS = ("act_noise", "test_noise", "train_reset", "test_reset")
+
+
+class PpoCfg(C.Structure):
+    """lenv_ppo_cfg (include/lenv_hip.h): PPO on a RewardEnv (or, reward_env_type 0, the real env) over a continuous real env."""
+    _fields_ = [("env_id", C.c_int32), ("state_dim", C.c_int32), ("action_dim", C.c_int32), ("max_steps", C.c_int32),
+                ("rn_hidden", C.c_int32), ("rn_layers", C.c_int32), ("rn_act", C.c_int32), ("rn_prelu", C.c_float),
+                ("reward_env_type", C.c_int32), ("info_dim", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("act", C.c_int32),
+                ("prelu", C.c_float), ("train_episodes", C.c_int32), ("test_episodes", C.c_int32), ("init_episodes", C.c_int32),
+                ("early_out_num", C.c_int32), ("ppo_epochs", C.c_int32), ("same_action_num", C.c_int32), ("rng_mode", C.c_int32),
+                ("reserved", C.c_int32),
+                ("solved_reward", C.c_double), ("gamma", C.c_double), ("lr", C.c_double), ("action_std", C.c_double),
+                ("vf_coef", C.c_double), ("ent_coef", C.c_double), ("eps_clip", C.c_double), ("update_episodes", C.c_double),
+                ("adam_beta1", C.c_double), ("adam_beta2", C.c_double), ("adam_eps", C.c_double)]
+
+
+class PpoTapes(C.Structure):
+    keys = PPO_TAPE_KEYS
+    _fields_ = _tape_fields(PPO_TAPE_KEYS)
+
+
+class PpoOut(C.Structure):
+    _fields_ = [("score", C.c_void_p), ("stats", C.c_void_p), ("status", C.c_void_p), ("episode_test_mean", C.c_void_p),
+                ("episode_len", C.c_void_p), ("final_returns", C.c_void_p), ("final_params", C.c_void_p), ("trace_cap", C.c_int64),
+                ("trace_action", C.c_void_p), ("trace_state", C.c_void_p), ("trace_next_state", C.c_void_p), ("trace_reward", C.c_void_p),
+                ("trace_done", C.c_void_p), ("learn_cap", C.c_int64), ("learn_step", C.c_void_p), ("learn_params", C.c_void_p)]
+
+
 # lenv_struct_size(which) order (include/lenv_hip.h)
-ABI_STRUCTS = [MlpDesc, DdqnCfg, QlCfg, Td3Cfg, Td3dCfg, Tapes, InnerOut, QlOut, Td3Tapes, Td3Out, Td3dTapes, ChainHp, IcmIo, Td3dRnCfg]
+ABI_STRUCTS = [MlpDesc, DdqnCfg, QlCfg, Td3Cfg, Td3dCfg, Tapes, InnerOut, QlOut, Td3Tapes, Td3Out, Td3dTapes, ChainHp, IcmIo, Td3dRnCfg,
+               PpoCfg, PpoTapes, PpoOut]
 
 _vp, _i32, _i64, _f64, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.POINTER
 # what follows the cfg (and hp / icm) of an inner-loop launch: theta, eps, worker, sign, agent_init, rng_keys, tapes, chains,
@@ -210,6 +239,12 @@ SIGNATURES = {
     "lenv_td3d_rn_num_params": (_i64, [_P(Td3dCfg), _P(Td3dRnCfg)]),
     "lenv_td3d_rn_inner_loop": (C.c_int, [_P(Td3dCfg), _P(Td3dRnCfg), _P(ChainHp), _vp, _vp, _vp, _vp, _vp, _vp, _P(Td3dTapes), _i64, _vp,
                                           C.c_size_t, _P(Td3Out), _vp]),
+    "lenv_ppo_rows": (_i64, [_P(PpoCfg)]),
+    "lenv_ppo_num_params": (_i64, [_P(PpoCfg), _P(_i64), _P(_i64)]),
+    "lenv_ppo_rn_num_params": (_i64, [_P(PpoCfg)]),
+    "lenv_ppo_rn_lds_bytes": (_i64, [_P(PpoCfg)]),
+    "lenv_ppo_rn_workspace_bytes": (_i64, [_P(PpoCfg), _i64]),
+    "lenv_ppo_rn_inner_loop": (C.c_int, [_P(PpoCfg)] + [_vp] * 6 + [_P(PpoTapes), _i64, _vp, C.c_size_t, _P(PpoOut), _vp]),
     "lenv_nes_worker_best": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "lenv_nes_worker_best_multi": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "lenv_nes_draw": (C.c_int, [C.c_uint64, C.c_uint64] + _NES_DRAW_TAIL),

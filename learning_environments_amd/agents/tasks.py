@@ -10,14 +10,15 @@ combination owns one fused kernel:
     TD3  on a RewardEnv over the HalfCheetah stand-in -> lenv_td3_rn_inner_loop (BASELINE config 5)
     TD3_discrete_vary on a VirtualEnv (CartPole / Acrobot / MountainCar) -> lenv_td3d_inner_loop
     TD3_discrete_vary on a RewardEnv over CartPole / Acrobot / MountainCar, or the real env itself (type 1) -> lenv_td3d_rn_inner_loop
+    PPO on a RewardEnv over the HalfCheetah stand-in / Pendulum / MountainCarContinuous (synthetic_env_type 1; reward_env_type 0 = the real env itself) -> lenv_ppo_rn_inner_loop
 Anything else raises NotImplementedError, like the reference does for unknown agents."""
 import copy
 
 import numpy as np
 import torch
 
-from ..config import (TABULAR_AGENTS, TD3_DISCRETE_ENVS, agent_layer_dims, agent_layer_norm_slice, ddqn_cfg_from_config, icm_layer_dims, ql_cfg_from_config,
-                      td3_cfg_from_config, td3_layer_dims, td3_layer_norm_slices, td3d_cfg_from_config, td3d_rn_cfg_from_config)
+from ..config import (TABULAR_AGENTS, TD3_DISCRETE_ENVS, agent_layer_dims, agent_layer_norm_slice, ddqn_cfg_from_config, icm_layer_dims, ppo_cfg_from_config,
+                      ppo_layer_dims, ql_cfg_from_config, td3_cfg_from_config, td3_layer_dims, td3_layer_norm_slices, td3d_cfg_from_config, td3d_rn_cfg_from_config)
 from . import vary
 from .nes_common import linear_init_bounds, set_layer_norm_init, with_layer_norm_block
 
@@ -226,6 +227,34 @@ class Td3DiscreteTask(_VaryAgents):
         return False          # drawn inside scores() (the LayerNorm parameters are not uniform draws)
 
 
+class PpoRnTask(object):
+    """PPO (agents/PPO.py) on a RewardEnv over a continuous real env, or on the real env itself (reward_env_type 0): one launch of
+    lenv_ppo_rn_inner_loop per generation, theta = the reward net exactly as for TD3.  A fresh agent = action_std [A] at its configured
+    constant (bound 0 in the generation's draw, then written the way set_layer_norm_init writes LayerNorm blocks) | actor.net | critic.net
+    with nn.Linear's default init from the chain keys."""
+    name = "ppo_rn"
+
+    def __init__(self, config, engine, test_mode=0):
+        if engine.name != "hip":
+            raise NotImplementedError("the PPO inner agent needs the HIP engine")
+        if int(test_mode) != 0:
+            raise NotImplementedError("PPO with test_mode 1 (PPO.train without a test env) is not built")
+        self.engine = engine
+        self.cfg = ppo_cfg_from_config(config)
+        A = self.cfg.action_dim
+        self.agent_bounds = torch.from_numpy(np.concatenate([np.zeros(A, np.float32), linear_init_bounds(ppo_layer_dims(self.cfg))])).to(engine.device)
+
+    def make_inner(self, chains, want_episode_stats=False, **kw):
+        return self.engine.make_inner_ppo(self.cfg, chains, want_episode_stats=want_episode_stats, **kw)
+
+    def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
+        agent_init[:, :self.cfg.action_dim] = float(self.cfg.action_std)
+        return self.engine.inner_scores_ppo(inner, theta, eps, chain_worker, chain_sign, agent_init, keys_t)
+
+    def needs_agent_init(self):
+        return True
+
+
 TD3_ENVS = ("HalfCheetah-v3", "Pendulum-v0", "MountainCarContinuous-v0")       # continuous real envs of the TD3 kernel
 
 
@@ -260,4 +289,13 @@ def select_task(config, engine, synthetic_env, test_mode=0):
         return Td3VaryTask(config, engine, **tm) if config["agents"]["td3_vary"]["vary_hp"] else Td3RnTask(config, engine, **tm)
     if agent_name == "td3_discrete_vary" and env_type in (0, 1) and config["env_name"] in TD3_DISCRETE_ENVS:
         return Td3DiscreteTask(config, engine, **tm)           # type 1: RewardEnv over the real env / the real env itself (mode 0)
+    if agent_name == "ppo":
+        # the reference runs PPO as the unseen agent of the reward-net transfer experiments (experiments/GTNC_evaluate_*_transfer_algo.py)
+        if env_type != 1:
+            raise NotImplementedError("PPO on a VirtualEnv (synthetic_env_type %s) is not built: PPO trains on a RewardEnv (type 1)" % env_type)
+        if config["env_name"] not in TD3_ENVS:
+            raise NotImplementedError("PPO on '%s' is not built: the PPO kernel takes the continuous real envs %s" % (config["env_name"], ", ".join(TD3_ENVS)))
+        return PpoRnTask(config, engine, **tm)
+    if agent_name == "ppo_icm":
+        raise NotImplementedError("ppo_icm (PPO with an Intrinsic Curiosity Module) is not built")
     raise NotImplementedError("inner agent '%s' on synthetic_env_type %s has no fused kernel yet" % (agent_name, env_type))

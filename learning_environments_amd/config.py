@@ -282,3 +282,56 @@ def td3_layer_dims(cfg):
     actor = [(cfg.state_dim, H)] + [(H, H)] * (L - 1) + [(H, cfg.action_dim)]
     critic = [(cfg.state_dim + cfg.action_dim, H)] + [(H, H)] * (L - 1) + [(H, 1)]
     return actor + critic + critic
+
+
+def ppo_cfg_from_config(config, rng_mode=_lib.RNG_COUNTER, **overrides):
+    """PPO agent + RewardEnv (reward_env_type 0: the real env itself) on the HalfCheetah stand-in, Pendulum-v0 or MountainCarContinuous-v0.
+    Fields read at reference agents/PPO.py:15-44, agents/base_agent.py:9-26, models/actor_critic.py:38-43, envs/reward_env.py:8-27."""
+    env_name = config["env_name"]
+    if env_name not in TD3_MAX_ACTION:
+        raise NotImplementedError("PPO fused kernel: real env '%s' (PPO on discrete-action envs is not built)" % env_name)
+    if "gtn" in config["agents"] and int(config["agents"]["gtn"].get("synthetic_env_type", 1)) != 1:
+        raise NotImplementedError("PPO on a VirtualEnv (synthetic_env_type 0) is not built: PPO trains on a RewardEnv (type 1) here")
+    S, A = ENV_DIMS[env_name]
+    e = config["envs"][env_name]
+    a = config["agents"]["ppo"]
+
+    def val(v):
+        return float(v[1]) if isinstance(v, list) else v
+
+    cfg = _lib.PpoCfg(env_id=_lib.ENV[env_name], state_dim=S, action_dim=A, max_steps=int(val(e["max_steps"])),
+                      rn_hidden=int(val(e["hidden_size"])), rn_layers=max(1, int(val(e["hidden_layer"]))), rn_act=_lib.ACT[e["activation_fn"]],
+                      rn_prelu=0.25, reward_env_type=int(val(e["reward_env_type"])), info_dim=int(val(e.get("info_dim", 0))),
+                      hidden=int(a["hidden_size"]), layers=max(1, int(a["hidden_layer"])), act=_lib.ACT[a["activation_fn"]], prelu=0.25,
+                      train_episodes=int(a["train_episodes"]), test_episodes=int(a["test_episodes"]), init_episodes=int(a["init_episodes"]),
+                      early_out_num=int(a["early_out_num"]), ppo_epochs=int(a["ppo_epochs"]), same_action_num=int(a["same_action_num"]),
+                      rng_mode=int(rng_mode), solved_reward=float(val(e["solved_reward"])), gamma=float(a["gamma"]), lr=float(a["lr"]),
+                      action_std=float(a["action_std"]), vf_coef=float(a["vf_coef"]), ent_coef=float(a["ent_coef"]),
+                      eps_clip=float(a["eps_clip"]), update_episodes=float(a["update_episodes"]),
+                      adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8)
+    # the kernel has no LayerNorm: the ppo section's use_layer_norm and a reward net's LayerNorm with two or more hidden layers are refused
+    if a.get("use_layer_norm", False):
+        raise NotImplementedError("PPO fused kernel: use_layer_norm in the ppo section")
+    if e.get("use_layer_norm", False) and cfg.rn_layers >= 2 and cfg.reward_env_type != 0:
+        raise NotImplementedError("PPO fused kernel: use_layer_norm of a reward net with two or more hidden layers")
+    for k, v in overrides.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
+def ppo_rows(cfg):
+    """Rows one PPO.learn call sees (agents/PPO.py:84,100): the first n with n * same_action_num / max_steps > update_episodes, the float
+    comparison the reference makes; floor(update_episodes * max_steps / same_action_num) + 1 when update_episodes is integral."""
+    k = max(1, int(cfg.same_action_num))
+    if not (0.0 <= cfg.update_episodes < float("inf")) or cfg.max_steps < 1:       # (NaN included: the loop below would never end)
+        raise ValueError("ppo_rows: update_episodes must be a finite number >= 0 and max_steps >= 1")
+    n = 1
+    while not (float(n * k) / float(cfg.max_steps) > cfg.update_episodes):
+        n += 1
+    return n
+
+
+def ppo_layer_dims(cfg):
+    """[(fan_in, fan_out), ...] of the nn.Linear layers behind the action_std slot: actor.net, then critic.net."""
+    H, L = cfg.hidden, cfg.layers
+    return [(cfg.state_dim, H)] + [(H, H)] * (L - 1) + [(H, cfg.action_dim)] + [(cfg.state_dim, H)] + [(H, H)] * (L - 1) + [(H, 1)]

@@ -214,6 +214,19 @@ def cmc_reward_env_td3(num_workers=16, max_iterations=50):
     return cfg
 
 
+def pendulum_reward_env_ppo(num_workers=16, max_iterations=20, **ppo_over):
+    """Pendulum-v0 RewardEnv (default_config_pendulum_reward_env.yaml's gtn and env sections) with PPO as the inner agent.  The ppo section:
+    the agent of the reward-net transfer scripts (two 64-wide relu layers, one test episode, experiments/GTNC_evaluate_cmc_transfer_algo.py:83-105)
+    with a learn call every five 200-step episodes (1001 rows) of ten epochs."""
+    cfg = pendulum_reward_env_td3(num_workers, max_iterations)
+    cfg["agents"]["gtn"]["agent_name"] = "ppo"
+    cfg["agents"]["ppo"] = dict(train_episodes=100, test_episodes=1, init_episodes=0, update_episodes=5, ppo_epochs=10, gamma=0.99, lr=3e-4, vf_coef=1,
+                                ent_coef=0.01, eps_clip=0.2, rb_size=1000000, same_action_num=1, activation_fn="relu", hidden_size=64, hidden_layer=2,
+                                action_std=0.5, print_rate=100, early_out_num=10, early_out_virtual_diff=0.02)
+    cfg["agents"]["ppo"].update(ppo_over)
+    return cfg
+
+
 def _td3_discrete_section(**over):
     """The `td3_discrete_vary` section both syn-env YAMLs ship (default_config_cartpole_syn_env.yaml:79-102 =
     default_config_acrobot_syn_env.yaml:58-81): actor S-510-510-A / critics (S+A)-510-510-1, tanh, hard Gumbel softmax."""

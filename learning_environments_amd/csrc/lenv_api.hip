@@ -20,6 +20,9 @@ extern "C" int64_t lenv_struct_size(int32_t which)
     case 11: return sizeof(lenv_chain_hp);
     case 12: return sizeof(lenv_icm_io);
     case 13: return sizeof(lenv_td3d_rn_cfg);
+    case 14: return sizeof(lenv_ppo_cfg);
+    case 15: return sizeof(lenv_ppo_tapes);
+    case 16: return sizeof(lenv_ppo_out);
     default: return LENV_ERR_INVALID;
     }
 }

@@ -206,7 +206,8 @@ enum { STREAM_EPS = 0, STREAM_ACTION = 1, STREAM_REPLAY = 2, STREAM_TRAIN_RESET 
        STREAM_TD3_RAND_ACTION = 5, STREAM_TD3_ACT_NOISE = 6, STREAM_TD3_TEST_NOISE = 7, STREAM_TD3_POLICY_NOISE = 8,
        STREAM_NES_EPS = 9, STREAM_AGENT_INIT = 10,
        STREAM_VARY_HP = 11,     // host side only (agents/vary.py): the four hyper-parameter draws of a *_vary agent
-       STREAM_ICM_INIT = 12 };  // fresh ICMModel parameters of an ICM agent (lenv_chain_uniform_init)
+       STREAM_ICM_INIT = 12,    // fresh ICMModel parameters of an ICM agent (lenv_chain_uniform_init)
+       STREAM_PPO_ACT_NOISE = 13, STREAM_PPO_TEST_NOISE = 14 };   // PPO: the Normal draw of actor_old.forward while training / testing
 
 // natural log, same sequence as the oracle's orc_log (fdlibm scheme, fma Horner); used by the counter-mode Box-Muller
 __device__ __forceinline__ double det_log(double x)
@@ -233,7 +234,8 @@ __device__ __forceinline__ double det_log(double x)
 }
 
 // deterministic expf (oracle: orc_expf, the same sequence): 2^n * p(r), n = rint(x*log2e), r = x - n*ln2 (two constants),
-// p = degree-6 Horner in fmaf.  Used for the softmax of the ICM inverse model (arguments <= 0).
+// p = degree-6 Horner in fmaf.  Used for the softmax of the ICM inverse model (arguments <= 0) and for PPO's probability ratio
+// exp(logp - old_logp) (both signs: within 2 ulp of exp over [-20, 20], tests/test_ppo_reference.py).
 __device__ __forceinline__ float det_expf(float x)
 {
     if (x < -87.0f) return 0.0f;

@@ -7,7 +7,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import DdqnCfg, InnerOut, MlpDesc, QlOut, Tapes, Td3Cfg, Td3dCfg, Td3dTapes, Td3Out, Td3Tapes
+from ._lib import DdqnCfg, InnerOut, MlpDesc, PpoCfg, PpoOut, PpoTapes, QlOut, Tapes, Td3Cfg, Td3dCfg, Td3dTapes, Td3Out, Td3Tapes
 
 
 def require_device():
@@ -202,8 +202,8 @@ class _InnerLoopBase(object):
                                             dtype=dtype, device=dev) for name, shape, dtype in self.trace_spec}
         tr, vals = self.trace or {}, []
         for f, _ in self.Out._fields_:
-            if f == "trace_cap":
-                vals.append(self.trace_cap)
+            if f.endswith("_cap"):                    # trace_cap; a family's own capacities (PPO: learn_cap) are attributes set before
+                vals.append(int(getattr(self, f)))
             elif f.startswith("trace_"):
                 vals.append(_ptr(tr.get(f[len("trace_"):])))
             else:
@@ -426,6 +426,37 @@ class Td3DiscreteInnerLoop(_InnerLoopBase):
         return self.score
 
 
+class PpoInnerLoop(_InnerLoopBase):
+    """Owns the workspace/outputs of lenv_ppo_rn_inner_loop (PPO on a RewardEnv over a continuous real env) for a fixed (cfg, chains).
+    learn_cap > 0: the step at which each of the first learn_cap PPO.learn calls fired and the parameters after it are recorded
+    (learn_step [chains, learn_cap], learn_params [chains, learn_cap, P])."""
+    Out, Tapes, final = PpoOut, PpoTapes, "final_params"
+    trace_spec = _TD3_TRACE + (("done", (), torch.float32),)
+    cfg_type, num_params_fn = PpoCfg, "lenv_ppo_num_params"
+
+    def __init__(self, cfg, chains, want_episode_stats=True, want_final_params=False, trace_cap=0, learn_cap=0):
+        super().__init__(cfg, chains)
+        pa, pc = C.c_int64(), C.c_int64()
+        self.p_agent = self._num_params(cfg, C.byref(pa), C.byref(pc))       # action_std [A] | actor.net | critic.net
+        self.p_actor, self.p_critic = pa.value, pc.value
+        self.rows = _count("lenv_ppo_rows", C.byref(cfg))                    # rows of one learn call
+        self.p_theta = _count("lenv_ppo_rn_num_params", C.byref(cfg))
+        self.learn_cap = int(learn_cap)
+        self.learn_step = self.learn_params = None
+        if self.learn_cap:
+            self.learn_step = torch.zeros((self.chains, self.learn_cap), dtype=torch.int32, device=self.dev)
+            self.learn_params = torch.zeros((self.chains, self.learn_cap, self.p_agent), dtype=torch.float32, device=self.dev)
+        self._alloc_outputs(_count("lenv_ppo_rn_workspace_bytes", C.byref(cfg), self.chains), want_episode_stats, want_final_params, trace_cap)
+
+    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None):
+        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+        if theta is not None and self.cfg.reward_env_type != 0 and theta.numel() != self.p_theta:
+            raise ValueError("theta must hold %d reward-net parameters" % self.p_theta)
+        rc = _lib.lib().lenv_ppo_rn_inner_loop(C.byref(self.cfg), *args)
+        _lib.check(rc, "lenv_ppo_rn_inner_loop")
+        return self.score
+
+
 def rn_shape_population(cfg, theta, eps, worker, sign, next_state, reward, chains=1):
     """(phi [chains,N], shaped [chains,N,A]) of a population of perturbed reward networks on a grid MDP."""
     dev = require_device()
@@ -515,6 +546,12 @@ class HipNesEngine(object):
         return Td3DiscreteInnerLoop(cfg, chains, **kw)
 
     def inner_scores_td3(self, inner, theta, eps, worker, sign, agent_init, rng_keys):
+        return inner.run(theta, eps, worker, sign, agent_init, rng_keys=rng_keys)
+
+    def make_inner_ppo(self, cfg, chains, **kw):
+        return PpoInnerLoop(cfg, chains, **kw)
+
+    def inner_scores_ppo(self, inner, theta, eps, worker, sign, agent_init, rng_keys):
         return inner.run(theta, eps, worker, sign, agent_init, rng_keys=rng_keys)
 
     def make_inner_ql(self, cfg, chains, tables, **kw):

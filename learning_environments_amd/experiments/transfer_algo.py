@@ -1,0 +1,154 @@
+"""Reward-net transfer to an unseen agent: reward networks learned with TD3 are judged by how fast a PPO agent learns on them.
+
+Mirrors the two functions of experiments/GTNC_evaluate_cmc_transfer_algo.py:60-128 and its HalfCheetah sibling (same names, arguments in the
+same order plus the env name, same return shapes):
+
+    load_envs_and_config(model_file) -> (reward_env, real_env, config)
+        reads a reference-format reward-net checkpoint {'model': state_dict, 'config': dict}; solved_reward is raised so that the early
+        out never triggers, as the scripts do
+    train_test_agents(mode, env, real_env, config, env_name) -> (rewards, episode_lengths)
+        writes the script's "settings for comparability" block (PPO_SETTINGS, restated as data) into config['agents']['ppo'] IN PLACE like the
+        reference, then for each of MODEL_AGENTS fresh PPO agents:  reward, episode_length, _ = agent.train(env=env, test_env=real_env)
+
+Here all agents of a call -- and, through train_test_agents_models, all models of a mode -- are the chains of ONE launch of
+lenv_ppo_rn_inner_loop.  Modes: '0' = the real env (a RewardEnv of type 0: the real reward passes through), '1' / '2' / '5' / '6' = reward
+envs of that reward_env_type.  Mode '-1' (ppo_icm) is not built.  Reading hpbandster logs is out of scope: the caller passes model files."""
+import copy
+
+import numpy as np
+import torch
+
+from .. import configs
+from ..agents import tasks
+from ..agents.nes_common import chain_keys, fresh_agent_init
+from ..engine import HipNesEngine
+from ..envs.env_factory import EnvFactory
+from ..envs.reward_env import RewardEnv
+
+MODEL_AGENTS = 10          # agents per model (both scripts)
+MODES = ("0", "1", "2", "5", "6")
+
+# the "settings for comparability" blocks: GTNC_evaluate_cmc_transfer_algo.py:83-105, GTNC_evaluate_halfcheetah_transfer_algo.py:91-113
+PPO_SETTINGS = {
+    "MountainCarContinuous-v0": dict(test_episodes=1, train_episodes=3000, print_rate=100, init_episodes=0, update_episodes=10, ppo_epochs=80, gamma=0.99,
+                                     lr=3e-4, vf_coef=1, ent_coef=0.01, eps_clip=0.2, rb_size=1000000, same_action_num=5, activation_fn="relu",
+                                     hidden_size=64, hidden_layer=2, action_std=0.5, early_out_num=10, early_out_virtual_diff=0.02),
+    "HalfCheetah-v3": dict(test_episodes=1, train_episodes=5000, print_rate=100, init_episodes=0, update_episodes=1, ppo_epochs=10, gamma=0.99, lr=1e-5,
+                           vf_coef=1, ent_coef=0.001, eps_clip=0.2, rb_size=1000000, same_action_num=1, activation_fn="tanh", hidden_size=128,
+                           hidden_layer=2, action_std=0.1, early_out_num=50, early_out_virtual_diff=0.02),
+}
+# what the scripts set solved_reward to ("something big enough to prevent early out triggering")
+SOLVED_REWARD = {"MountainCarContinuous-v0": 100000, "HalfCheetah-v3": 100000}
+
+
+def base_config(env_name):
+    """The RewardEnv configuration of a continuous real env (the published reward-env YAML's values) with PPO as the inner agent; the `ppo`
+    section is the caller's to fill (train_test_agents writes PPO_SETTINGS there)."""
+    make = {"MountainCarContinuous-v0": configs.cmc_reward_env_td3, "HalfCheetah-v3": configs.halfcheetah_reward_env_td3,
+            "Pendulum-v0": configs.pendulum_reward_env_td3}
+    if env_name not in make:
+        raise NotImplementedError("transfer_algo: real env '%s'" % env_name)
+    cfg = make[env_name]()
+    cfg["agents"]["gtn"]["agent_name"] = "ppo"
+    return cfg
+
+
+def load_envs_and_config(model_file):
+    save_dict = torch.load(model_file, map_location="cpu")
+    config = save_dict['config']
+    config['device'] = 'cpu'
+    env_name = config['env_name']
+    config['envs'][env_name]['solved_reward'] = SOLVED_REWARD.get(env_name, 100000)
+    env_factory = EnvFactory(config=config)
+    reward_env = env_factory.generate_reward_env()
+    reward_env.load_state_dict(save_dict['model'])
+    real_env = env_factory.generate_real_env()
+    return reward_env, real_env, config
+
+
+def _task_config(mode, env, config):
+    """(config of the launch, theta): the caller's config with PPO as the inner agent on a RewardEnv; mode '0' / the real env itself = a
+    RewardEnv of type 0 whose network is never evaluated."""
+    cfg = copy.deepcopy(config)
+    cfg["agents"]["gtn"] = dict(cfg["agents"].get("gtn", {}), agent_name="ppo", synthetic_env_type=1)
+    e = cfg["envs"][cfg["env_name"]]
+    if str(mode) == "0" or not isinstance(env.env, RewardEnv):
+        e["reward_env_type"] = 0
+        return cfg, None
+    if int(e["reward_env_type"]) != int(mode):
+        raise ValueError("mode %s needs a reward env of reward_env_type %s, the model has %s" % (mode, mode, e["reward_env_type"]))
+    return cfg, env.env.flat_params()
+
+
+def train_test_agents(mode, env, real_env, config, env_name=None, agents_num=MODEL_AGENTS, seed=0, model_index=0, settings=None, details=False):
+    """Returns (rewards, episode_lengths): rewards[i] = the i-th agent's per-episode real-env test means (PPO.train's first return value),
+    episode_lengths[i] = its training episode lengths.  `settings` overrides entries of the script's block (a reduced episode budget);
+    `seed` / `model_index` key the agents' counter-RNG streams.  details=True: ((rewards, episode_lengths), launch) with launch = the dict of
+    what ran (inner, task, keys, agent_init, theta, eps, worker, sign) for tests and benchmarks."""
+    results, launch = _launch(mode, [env], real_env, config, env_name, agents_num, seed, [model_index], settings)
+    return (results[0], launch) if details else results[0]
+
+
+def train_test_agents_models(mode, envs, real_env, config, env_name=None, agents_num=MODEL_AGENTS, seed=0, model_indices=None, settings=None,
+                             details=False):
+    """All models of a mode as ONE launch: len(envs) * agents_num chains, chain (m, i) reading model m's reward net.  Returns
+    [train_test_agents(mode, envs[m], ..., model_index=model_indices[m]) for m], bit for bit (details=True: that list and the launch)."""
+    if model_indices is None:
+        model_indices = list(range(len(envs)))
+    results, launch = _launch(mode, list(envs), real_env, config, env_name, agents_num, seed, list(model_indices), settings)
+    return (results, launch) if details else results
+
+
+def _launch(mode, envs, real_env, config, env_name, agents_num, seed, model_indices, settings):
+    mode = str(mode)
+    if mode == "-1":
+        raise NotImplementedError("mode -1 (ppo_icm: PPO with an Intrinsic Curiosity Module) is not built")
+    if mode not in MODES:
+        raise NotImplementedError("transfer_algo: mode '%s' (built: %s)" % (mode, ", ".join(MODES)))
+    env_name = env_name or config["env_name"]
+    if env_name != config["env_name"]:
+        raise ValueError("env_name '%s' does not match the config's '%s'" % (env_name, config["env_name"]))
+    if env_name not in PPO_SETTINGS:
+        raise NotImplementedError("transfer_algo: no transfer script for '%s' (there are: %s)" % (env_name, ", ".join(sorted(PPO_SETTINGS))))
+    if real_env.is_virtual_env():
+        raise ValueError("real_env must be the real environment")
+    config['agents']['ppo'] = dict(PPO_SETTINGS[env_name], **(settings or {}))       # in place, like the scripts
+    M, n_ag = len(envs), int(agents_num)
+    cfg, theta = _task_config(mode, envs[0], config)
+    engine = HipNesEngine()
+    dev = engine.device
+    task = tasks.select_task(cfg, engine, envs[0])
+    chains = M * n_ag
+    inner = task.make_inner(chains, want_episode_stats=True)
+    keys = np.concatenate([chain_keys(int(seed), int(mi), np.arange(n_ag), np.zeros(n_ag, np.int64)) for mi in model_indices])
+    keys_t = torch.from_numpy(keys.view(np.int64)).to(dev)
+    p_theta = max(inner.p_theta, 1)
+    if theta is None or M == 1:
+        # the real env, or one model: its weights are theta itself, sign 0 (the unperturbed checkpoint)
+        theta = torch.zeros(p_theta, dtype=torch.float32, device=dev) if theta is None else theta.to(device=dev, dtype=torch.float32)
+        worker = torch.zeros(chains, dtype=torch.int32, device=dev)
+        sign = torch.zeros(chains, dtype=torch.float32, device=dev)
+        eps = torch.zeros((1, theta.numel()), dtype=torch.float32, device=dev)
+    else:
+        # several models: chain (m, i) reads 0 + 1 * weights[m] (exact; a stored -0.0 becomes +0.0, which no sum downstream can tell apart)
+        thetas = [theta] + [_task_config(mode, e, config)[1] for e in envs[1:]]
+        if any(t.numel() != theta.numel() for t in thetas):
+            raise ValueError("train_test_agents_models: the models of one launch must have the same shapes")
+        eps = torch.stack([t.to(device=dev, dtype=torch.float32) for t in thetas])
+        theta = torch.zeros_like(eps[0])
+        worker = torch.arange(chains, dtype=torch.int32, device=dev) // n_ag
+        sign = torch.ones(chains, dtype=torch.float32, device=dev)
+    rows = []
+    for mi in model_indices:
+        g = torch.Generator(device=dev)
+        g.manual_seed(int(seed) + 1000003 * int(mi))
+        rows.append(fresh_agent_init(task.agent_bounds, n_ag, g, dev))
+    agent_init = torch.cat(rows)
+    task.scores(inner, theta, eps, worker, sign, keys_t, agent_init)
+    engine.check_status(inner)
+    stats = inner.stats.cpu().numpy()
+    ep_mean, ep_len = inner.episode_test_mean.cpu().numpy(), inner.episode_len.cpu().numpy()
+    rewards = [ep_mean[i, :int(stats[i, 0])].tolist() for i in range(chains)]
+    lengths = [ep_len[i, :int(stats[i, 0])].tolist() for i in range(chains)]
+    launch = dict(inner=inner, task=task, keys=keys, agent_init=agent_init, theta=theta, eps=eps, worker=worker, sign=sign)
+    return [(rewards[m * n_ag:(m + 1) * n_ag], lengths[m * n_ag:(m + 1) * n_ag]) for m in range(M)], launch

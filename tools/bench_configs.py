@@ -17,7 +17,7 @@ from learning_environments_amd.agents.GTN import GTN_Master  # noqa: E402
 from learning_environments_amd import configs  # noqa: E402
 
 
-def run(name, cfg, gens=2, extra=None, force_gemm=False):
+def run(name, cfg, gens=2, extra=None, force_gemm=False, median=False):
     torch.manual_seed(0)
     m = GTN_Master(cfg, bohb_id=0, seed=7)
     if force_gemm:       # A/B aid: one sequential batch gradient (grad_chunk 0) = the GEMM-queue kernel instead of the register-resident one
@@ -26,17 +26,27 @@ def run(name, cfg, gens=2, extra=None, force_gemm=False):
         assert m.inner.dueling
     m.step(0)
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for it in range(1, 1 + gens):
-        m.step(it)
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / gens
+    if median:           # every generation timed on its own (a synchronise behind each), the median reported
+        times = []
+        for it in range(1, 1 + gens):
+            t0 = time.perf_counter()
+            m.step(it)
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        dt = sorted(times)[len(times) // 2]
+    else:
+        t0 = time.perf_counter()
+        for it in range(1, 1 + gens):
+            m.step(it)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / gens
     st = m.inner.stats.cpu().numpy()
     out = dict(config=name, pop=cfg["agents"]["gtn"]["num_workers"], chains=int(st.shape[0]), s_per_generation=dt,
                evals_per_s=cfg["agents"]["gtn"]["num_workers"] / dt, train_steps=int(st[:, 1].sum()), learn_steps=int(st[:, 2].sum()),
                test_steps=int(st[:, 3].sum()), us_per_learn_step_per_chain=1e6 * dt / max(1.0, st[:, 2].mean()))
     out.update(extra(cfg, st, dt) if extra else {})
     print(json.dumps(out))
+    return out
 
 
 import bench  # noqa: E402  (the byte / FLOP models live next to the contract line)
@@ -52,6 +62,20 @@ def _frac(model):
 
 
 dueling_model, td3_model = _frac(bench.dueling_model), _frac(bench.td3_model)
+
+
+def ppo_model(cfg, st, dt):
+    """PPO.learn's layer products: forward, input gradient and weight gradient of both nets over the N rows = 6 N W flops per epoch per chain
+    (W = weights of actor.net + critic.net); the rollout (one row at a time) is not counted.  The fraction is of the busy CUs' share of the peak."""
+    from learning_environments_amd.config import ppo_cfg_from_config, ppo_rows
+    c = ppo_cfg_from_config(cfg)
+    S, A, H, L = c.state_dim, c.action_dim, c.hidden, c.layers
+    W = 2 * (S * H + (L - 1) * H * H) + A * H + H
+    epochs = float(st[:, 2].sum()) * c.ppo_epochs
+    flops = 6.0 * ppo_rows(c) * W * epochs
+    busy = min(int(st.shape[0]), 256)
+    return dict(rows_per_learn=ppo_rows(c), learn_epochs=int(epochs), us_per_learn_epoch_per_chain=1e6 * dt / max(1.0, epochs / st.shape[0]),
+                fp32_TFLOPs=flops / dt / 1e12, mfma_f32_frac_of_busy_cus=flops / dt / 1e12 / (MFMA_F32_PEAK_TFLOPS * busy / 256.0), busy_cus=busy)
 
 
 if __name__ == "__main__":
@@ -191,6 +215,26 @@ if __name__ == "__main__":
             c = configs.fixed_work(configs.cartpole_syn_env_td3_discrete(pop), 3)
             c["envs"]["CartPole-v0"]["max_steps"] = 100
             run("TD3_discrete_vary on a CartPole SE, pop %d (3 episodes x 100 steps, shipped 510-wide nets)" % pop, c, gens=1, extra=per_step)
+    if "ppo" in which:
+        # PPO (two 64-wide relu layers, 1001 rows x 10 epochs per learn call) on default_config_pendulum_reward_env.yaml's RewardEnv at its own
+        # population (16 workers = 48 chains) and at 64 workers = 192 chains; 10 training episodes = 2000 rows = ONE learn call per chain; a warm-up
+        # generation, then the median of 7 generations timed one by one
+        # (Pendulum episodes never end early: the rollout is the same work whatever the policy, so the difference of two generations that differ
+        # in ppo_epochs only is the cost of the extra epochs -- us per learn epoch and the MFMA fraction are taken from it)
+        for pop in (16, 64):
+            res = {}
+            for epochs in (10, 30):
+                c = configs.fixed_work(configs.pendulum_reward_env_ppo(pop, train_episodes=10, ppo_epochs=epochs), 10)
+                c["agents"]["gtn"]["quit_when_solved"] = False
+                res[epochs] = run("Pendulum RN + PPO 64x2 pop %d (10 episodes x 200 steps, 1 learn call x %d epochs x 1001 rows)" % (pop, epochs), c, gens=7,
+                                  extra=ppo_model, median=True)
+            d_t = res[30]["s_per_generation"] - res[10]["s_per_generation"]
+            d_ep = (res[30]["learn_epochs"] - res[10]["learn_epochs"]) / float(res[10]["chains"])
+            W = 2 * (3 * 64 + 64 * 64) + 64 + 64
+            flops = 6.0 * 1001 * W * d_ep * res[10]["chains"]
+            print(json.dumps(dict(config="Pendulum RN + PPO 64x2 pop %d: the extra epochs alone" % pop, chains=res[10]["chains"], extra_epochs_per_chain=d_ep,
+                                  us_per_learn_epoch=1e6 * d_t / d_ep, rollout_and_rest_s=res[10]["s_per_generation"] - 10 * d_t / d_ep,
+                                  mfma_f32_frac_of_busy_cus=flops / d_t / 1e12 / (MFMA_F32_PEAK_TFLOPS * min(res[10]["chains"], 256) / 256.0))))
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1

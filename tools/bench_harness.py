@@ -1,7 +1,10 @@
 """The evaluation harness as an experiment runs it (reference experiments/syn_env_evaluate_cartpole_vary_hp_2.py __main__: 40 models x 10
 DDQN_vary agents per mode): run_vary_hp with all models in ONE fused launch against the model-by-model calls the reference's loop makes.
 Models: CartPole SEs of default_config_cartpole.yaml's shape whose reward net says ~1 per step (a stand-in for trained SEs: 200-step episodes,
-the virtual early-out after 20-30 episodes).  usage: python tools/bench_harness.py [model_num] [agents_num] [agent] [mode]"""
+the virtual early-out after 20-30 episodes).  usage: python tools/bench_harness.py [model_num] [agents_num] [agent] [mode]
+agent = ppo_transfer: the reward-net transfer experiment (experiments/GTNC_evaluate_cmc_transfer_algo.py: 10 models x 10 PPO agents per mode) at the
+script's PPO settings on a reduced episode budget ([mode] = training episodes per agent, default 40), all models in one launch; models =
+freshly initialised MountainCarContinuous reward nets of default_config_cmc_reward_env.yaml's shape (a stand-in for trained ones)."""
 import json
 import os
 import sys
@@ -17,7 +20,44 @@ from learning_environments_amd.experiments.syn_env_evaluate import load_envs_and
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
+def ppo_transfer(model_num, agents_num, episodes):
+    import copy
+    from learning_environments_amd.envs.env_factory import EnvFactory
+    from learning_environments_amd.experiments import transfer_algo as ta
+    env_name = "MountainCarContinuous-v0"
+    base = ta.base_config(env_name)
+    envs = []
+    for m in range(model_num):
+        torch.manual_seed(100 + m)
+        envs.append(EnvFactory(copy.deepcopy(base)).generate_reward_env())
+    real_env = EnvFactory(copy.deepcopy(base)).generate_real_env()
+    settings = dict(train_episodes=episodes)
+    ta.train_test_agents_models("2", envs[:1], real_env, copy.deepcopy(base), env_name, agents_num=1, settings=dict(train_episodes=11))       # warm-up
+    torch.cuda.synchronize()
+    times = []
+    for rep in range(3):
+        t0 = time.time()
+        _, launch = ta.train_test_agents_models("2", envs, real_env, copy.deepcopy(base), env_name, agents_num=agents_num, seed=rep, settings=settings,
+                                                details=True)
+        torch.cuda.synchronize()
+        times.append(time.time() - t0)
+    st = launch["inner"].stats.cpu().numpy()
+    dt = sorted(times)[1]
+    cfg = launch["task"].cfg
+    W = 2 * (cfg.state_dim * cfg.hidden + (cfg.layers - 1) * cfg.hidden * cfg.hidden) + cfg.action_dim * cfg.hidden + cfg.hidden
+    rows = launch["inner"].rows
+    epochs = float(st[:, 2].sum()) * cfg.ppo_epochs
+    import bench
+    busy = min(st.shape[0], 256)
+    print(json.dumps({"experiment": "ppo transfer, mode 2", "models": model_num, "agents": int(st.shape[0]), "train_episodes": episodes,
+                      "seconds_median_of_3": dt, "seconds_all": times, "agents_per_s": st.shape[0] / dt, "rows_per_learn": rows,
+                      "learn_calls": int(st[:, 2].sum()), "us_per_learn_epoch_per_chain": 1e6 * dt / max(1.0, epochs / st.shape[0]),
+                      "mfma_f32_frac_of_busy_cus": 6.0 * rows * W * epochs / dt / 1e12 / (bench.MFMA_F32_PEAK_TFLOPS * busy / 256.0)}))
+
+
 def main():
+    if len(sys.argv) > 3 and sys.argv[3] == "ppo_transfer":
+        return ppo_transfer(int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[4]) if len(sys.argv) > 4 else 40)
     model_num = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     agents_num = int(sys.argv[2]) if len(sys.argv) > 2 else 10
     agent = sys.argv[3] if len(sys.argv) > 3 else None      # a sibling script's agent (DuelingDDQN_vary, td3_discrete_vary): fused launch only
