@@ -243,7 +243,8 @@ typedef struct {
                                            reward sum); 0 and 1 both mean 1 */
     int32_t rn_layer_norm;              /* the ENV section's `use_layer_norm` with rn_layers >= 2, as lenv_ddqn_cfg::se_layer_norm (ABI 6; was padding) */
     int32_t test_mode;                  /* ABI 7: as lenv_ddqn_cfg::test_mode (1 = BaseAgent.train without a test env) */
-    double early_out_virtual_diff;      /* never read: a grid RewardEnv is not a VirtualEnv (the real rule applies) */
+    double early_out_virtual_diff;      /* read by lenv_ql_se_inner_loop with test_mode 1 (the virtual rule); lenv_ql_rn_inner_loop never reads it: a grid
+                                           RewardEnv is not a VirtualEnv (the real rule applies) */
 } lenv_ql_cfg;
 
 typedef struct {
@@ -265,6 +266,30 @@ int lenv_ql_rn_inner_loop(const lenv_ql_cfg *cfg /*HOST*/, const float *theta, c
                           const float *sign, const float *shaped_override, const int32_t *next_state, const double *reward,
                           const uint8_t *done, const uint64_t *rng_keys, const lenv_tapes *tapes /*HOST, may be NULL*/,
                           int64_t chains, const lenv_ql_out *out /*HOST struct of device ptrs*/, void *stream);
+
+/*
+ * The tabular agents on a gridworld VirtualEnv (synthetic_env_type 0): GTN_Worker.calc_score (agents/GTN_worker.py:187-221) with
+ * env = VirtualEnv over a Discrete observation space, one workgroup per chain.  theta = state_net | reward_net | done_net (the nn.Linear
+ * parameters only), each net Linear(n_actions + n_states, H) | [Linear(H, H)] | Linear(H, out) with the shape in cfg's rn_hidden / rn_layers
+ * (1 or 2) / rn_act / rn_prelu; perturbed per chain as theta + sign*eps[worker].  Every training step evaluates the three nets on
+ * [one_hot(action) | raw state vector] (envs/virtual_env.py:43-54; the raw state-net output is fed back, the agent sees its argmax: the first maximum, a NaN counting as the maximum as in torch.argmax),
+ * same_action_num steps per action regardless of done with an fp32 reward sum (envs/env_wrapper.py:17-49), no TimeLimit; reward and done
+ * reach the agent raw (bootstrap mask done < 0.5, episode end done > 0.5).  next_state / reward / done are the REAL grid's tables: the
+ * per-episode tests and the final test walk them.  test_mode 1: the SE's own episode reward feeds the meter and the virtual early-out rule
+ * (early_out_virtual_diff) applies.  reward_env_type is not read; rn_layer_norm with two hidden layers is refused.  lenv_ql_out as for
+ * lenv_ql_rn_inner_loop (trace_state: the agent-visible indices; trace_reward_done: the summed reward and the raw done; `shaped` is not
+ * written).  trace_se [chains, trace_cap, n_states + 2] (optional): raw next-state vector | reward | done of the LAST SE step of each agent
+ * step.  The staged theta lives in LDS while it fits (lenv_ql_se_lds_bytes <= 160 KiB), otherwise in `workspace`
+ * (lenv_ql_se_workspace_bytes; 0 when LDS holds it).  The three queries return LENV_ERR_UNSUPPORTED for a cfg the loop refuses.
+ * (Added under ABI 7: new entry points only, no struct changed -- a binding built against the earlier ABI 7 header keeps working.)
+ */
+int64_t lenv_ql_se_num_params(const lenv_ql_cfg *cfg /*HOST*/);
+int64_t lenv_ql_se_lds_bytes(const lenv_ql_cfg *cfg /*HOST*/);
+int64_t lenv_ql_se_workspace_bytes(const lenv_ql_cfg *cfg /*HOST*/, int64_t chains);
+int lenv_ql_se_inner_loop(const lenv_ql_cfg *cfg /*HOST*/, const float *theta, const float *eps, const int32_t *worker, const float *sign,
+                          const int32_t *next_state, const double *reward, const uint8_t *done, const uint64_t *rng_keys,
+                          const lenv_tapes *tapes /*HOST, may be NULL*/, int64_t chains, const lenv_ql_out *out /*HOST struct of device ptrs*/,
+                          float *trace_se, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * RewardEnv shaping for a population of perturbed reward networks on a grid MDP (envs/reward_env.py:67-133): phi_out

@@ -218,6 +218,10 @@ SIGNATURES = {
     "lenv_cont_env_reset": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "lenv_cont_env_step": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lenv_ql_rn_inner_loop": (C.c_int, [_P(QlCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(Tapes), _i64, _P(QlOut), _vp]),
+    "lenv_ql_se_num_params": (_i64, [_P(QlCfg)]),
+    "lenv_ql_se_lds_bytes": (_i64, [_P(QlCfg)]),
+    "lenv_ql_se_workspace_bytes": (_i64, [_P(QlCfg), _i64]),
+    "lenv_ql_se_inner_loop": (C.c_int, [_P(QlCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(Tapes), _i64, _P(QlOut), _vp, _vp, _i64, _vp]),
     "lenv_rn_shape_population": (C.c_int, [_P(QlCfg), _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "lenv_rn_num_params": (_i64, [_i32] * 5),
     "lenv_rn_shape_rows": (C.c_int, [_i32, _P(MlpDesc), _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),

@@ -7,6 +7,7 @@ combination owns one fused kernel:
     DDQN_vary / DuelingDDQN_vary on a VirtualEnv  -> lenv_dueling_se_inner_loop_hp (per-chain lr / batch / width / depth)
     TD3_vary on a RewardEnv over the stand-in     -> lenv_td3_rn_inner_loop_hp
     QL / QL_cb / SARSA / SARSA_cb on a RewardEnv over a gridworld (type 1) -> lenv_ql_rn_inner_loop (BASELINE config 4)
+    QL / QL_cb / SARSA / SARSA_cb on a VirtualEnv over a gridworld (type 0) -> lenv_ql_se_inner_loop
     TD3  on a RewardEnv over the HalfCheetah stand-in -> lenv_td3_rn_inner_loop (BASELINE config 5)
     TD3_discrete_vary on a VirtualEnv (CartPole / Acrobot / MountainCar) -> lenv_td3d_inner_loop
     TD3_discrete_vary on a RewardEnv over CartPole / Acrobot / MountainCar, or the real env itself (type 1) -> lenv_td3d_rn_inner_loop
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 
 from ..config import (TABULAR_AGENTS, TD3_DISCRETE_ENVS, agent_layer_dims, agent_layer_norm_slice, ddqn_cfg_from_config, icm_layer_dims, ppo_cfg_from_config,
-                      ppo_layer_dims, ql_cfg_from_config, td3_cfg_from_config, td3_layer_dims, td3_layer_norm_slices, td3d_cfg_from_config, td3d_rn_cfg_from_config)
+                      ppo_layer_dims, ql_cfg_from_config, ql_se_cfg_from_config, td3_cfg_from_config, td3_layer_dims, td3_layer_norm_slices, td3d_cfg_from_config, td3d_rn_cfg_from_config)
 from . import vary
 from .nes_common import linear_init_bounds, set_layer_norm_init, with_layer_norm_block
 
@@ -152,6 +153,30 @@ class QlRnTask(object):
         return False          # a fresh QL agent is an all-zero table (QL.py:25)
 
 
+class QlSeTask(object):
+    """QL / QL_cb / SARSA / SARSA_cb on a gridworld VirtualEnv (synthetic_env_type 0): one launch of lenv_ql_se_inner_loop per generation,
+    theta = state_net | reward_net | done_net.  `tables` are the REAL grid's (the per-episode tests and the final test walk them).  No
+    host-side draws: the task can be captured into a graph."""
+    name = "ql_se"
+
+    def __init__(self, config, engine, tables, test_mode=0):
+        if engine.name != "hip":
+            raise NotImplementedError("the tabular agents on a gridworld VirtualEnv need the HIP engine")
+        self.engine = engine
+        self.tables = tables
+        self.cfg = ql_se_cfg_from_config(config, tables, test_mode=test_mode)
+        self.agent_bounds = None
+
+    def make_inner(self, chains, want_episode_stats=False, **kw):
+        return self.engine.make_inner_ql_se(self.cfg, chains, self.tables, want_episode_stats=want_episode_stats, **kw)
+
+    def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
+        return self.engine.inner_scores_ql_se(inner, theta, eps, chain_worker, chain_sign, keys_t)
+
+    def needs_agent_init(self):
+        return False          # a fresh tabular agent is an all-zero table (QL.py:25)
+
+
 class Td3RnTask(_FixedShapeAgents):
     name = "td3_rn"
 
@@ -282,6 +307,11 @@ def select_task(config, engine, synthetic_env, test_mode=0):
         if not hasattr(real, "tables"):
             raise NotImplementedError("QL needs a discrete (gridworld) real env")
         return QlRnTask(config, engine, real.tables, **tm)
+    if agent_name in TABULAR_AGENTS and env_type == 0:
+        grid = getattr(getattr(getattr(synthetic_env, "env", None), "reset_env", None), "env", None)     # VirtualEnv.reset_env = EnvWrapper(GridEnv)
+        if not hasattr(grid, "tables"):
+            raise NotImplementedError("inner agent '%s' on a VirtualEnv needs a discrete (gridworld) env" % agent_name)
+        return QlSeTask(config, engine, grid.tables, **tm)
     # TD3 on the HalfCheetah stand-in / Pendulum-v0 / MountainCarContinuous-v0: RewardEnv (type 1, BASELINE config 5) or VirtualEnv (type 0, default_config_halfcheetah.yaml)
     if agent_name in ("td3", "td3_icm") and env_type in (0, 1) and config["env_name"] in TD3_ENVS:
         return Td3RnTask(config, engine, **tm)

@@ -164,6 +164,24 @@ def ql_cfg_from_config(config, tables, rng_mode=_lib.RNG_COUNTER, **overrides):
     return cfg
 
 
+def ql_se_cfg_from_config(config, tables, rng_mode=_lib.RNG_COUNTER, **overrides):
+    """A tabular agent + VirtualEnv on a gridworld (synthetic_env_type 0, lenv_ql_se_inner_loop).  The `envs` section describes the three SE
+    nets (envs/virtual_env.py:23-31 builds them from hidden_size / hidden_layer / activation_fn); they travel in lenv_ql_cfg's rn_* fields.  A
+    `reward_env_type` key is not required (the loop never reads it).  Agent fields as ql_cfg_from_config."""
+    e = dict(config["envs"][config["env_name"]])
+    e.setdefault("reward_env_type", 0)
+    layers = e["hidden_layer"]
+    layers = max(1, int(float(layers[1]) if isinstance(layers, list) else layers))     # build_nn_from_config: 0 builds the same net as 1
+    if e.get("use_layer_norm", False) and layers >= 2:
+        raise NotImplementedError("tabular agents on a gridworld VirtualEnv: use_layer_norm of SE nets with two or more hidden layers")
+    patched = dict(config, envs=dict(config["envs"], **{config["env_name"]: e}))
+    cfg = ql_cfg_from_config(patched, tables, rng_mode=rng_mode)
+    cfg.rn_layers, cfg.reward_env_type, cfg.rn_layer_norm = layers, 0, 0
+    for k, v in overrides.items():
+        setattr(cfg, k, v)
+    return cfg
+
+
 def td3_cfg_from_config(config, rng_mode=_lib.RNG_COUNTER, **overrides):
     """TD3 agent + RewardEnv / VirtualEnv on the HalfCheetah stand-in or Pendulum-v0.  Fields read at reference agents/TD3.py:13-29,
     agents/base_agent.py:9-26, envs/reward_env.py:8-27, envs/env_wrapper.py:106-110 (max_action)."""

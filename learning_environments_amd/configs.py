@@ -120,6 +120,17 @@ def cliff_reward_env_ql(num_workers=128, max_iterations=50):
     })
 
 
+def cliff_syn_env_ql(num_workers=16, max_iterations=50):
+    """Cliff gridworld VirtualEnv (three SE nets 52-32-{48,1,1}, leakyrelu) + tabular QL: the values of default_config_gridworld.yaml (gtn
+    :6-26, ql :28-43, Cliff :126-133) with synthetic_env_type 0 -- the combination the reference's `gtn` default config and its gridworld
+    visualisation script run."""
+    cfg = cliff_reward_env_ql(num_workers, max_iterations)
+    cfg["agents"]["gtn"].update(step_size=1.0, time_max=100, score_transform_type=7, synthetic_env_type=0, unsolved_weight=10000)
+    cfg["agents"]["ql"].update(eps_init=0.1, eps_min=0.1)
+    cfg["envs"]["Cliff"].update(activation_fn="leakyrelu")
+    return cfg
+
+
 def halfcheetah_reward_env_td3(num_workers=64, max_iterations=50):
     """BASELINE config 5: HalfCheetah-v3 RewardEnv (potential shaped, type 2) + TD3 (values = the published hyper-parameters of
     default_config_halfcheetah_reward_env.yaml: td3 :31-50, env :53-60; gtn as in the gridworld RN config).  The real env is

@@ -356,6 +356,37 @@ class QlInnerLoop(_InnerLoopBase):
         return self.score
 
 
+class QlSeInnerLoop(_InnerLoopBase):
+    """Owns the workspace/outputs of lenv_ql_se_inner_loop (the tabular agents on a gridworld VirtualEnv) for a fixed (cfg, chains, grid
+    MDP).  trace_cap > 0 also records trace_se [chains, trace_cap, n_states + 2]: the SE's raw next-state vector | reward | done of the last SE
+    step of every agent step."""
+    Out, Tapes, tape_keys = QlOut, Tapes, ("eps_uniform", "rand_action")
+    trace_spec = QlInnerLoop.trace_spec
+
+    def __init__(self, cfg, chains, tables, want_episode_stats=True, trace_cap=0):
+        super().__init__(cfg, chains)
+        N, A = cfg.n_states, cfg.n_actions
+        self.p_theta = _count("lenv_ql_se_num_params", C.byref(cfg))           # a refused cfg raises here, before any allocation
+        self.lds_bytes = _count("lenv_ql_se_lds_bytes", C.byref(cfg))
+        self.next_state = torch.from_numpy(tables["next_state"].astype("int32")).contiguous().to(self.dev)
+        self.reward = torch.from_numpy(tables["reward"].astype("float64")).contiguous().to(self.dev)
+        self.done = torch.from_numpy(tables["done"].astype("uint8")).contiguous().to(self.dev)
+        self.shaped = None
+        self.q_table = torch.zeros((self.chains, N * A), dtype=torch.float64, device=self.dev) if want_episode_stats else None
+        self._alloc_outputs(_count("lenv_ql_se_workspace_bytes", C.byref(cfg), self.chains), want_episode_stats, False, trace_cap)
+        self.trace_se = torch.zeros((self.chains, self.trace_cap, N + 2), dtype=torch.float32, device=self.dev) if trace_cap else None
+
+    def run(self, theta, eps, worker, sign, rng_keys=None, tapes=None):
+        self._check_run(theta, eps, worker, sign, rng_keys)
+        if theta is None or theta.numel() != self.p_theta:
+            raise ValueError("theta must hold %d SE parameters" % self.p_theta)
+        rc = _lib.lib().lenv_ql_se_inner_loop(C.byref(self.cfg), _ptr(theta), _ptr(eps), _ptr(worker), _ptr(sign), _ptr(self.next_state),
+                                              _ptr(self.reward), _ptr(self.done), _ptr(rng_keys), self._tapes_arg(tapes), self.chains,
+                                              C.byref(self.out), _ptr(self.trace_se), _ptr(self.workspace), self.ws_bytes, _stream())
+        _lib.check(rc, "lenv_ql_se_inner_loop")
+        return self.score
+
+
 class Td3InnerLoop(_InnerLoopBase):
     """Owns the workspace/outputs of lenv_td3_rn_inner_loop for a fixed (cfg, chains)."""
     Out, Tapes, final, trace_spec = Td3Out, Td3Tapes, "final_params", _TD3_TRACE
@@ -558,6 +589,12 @@ class HipNesEngine(object):
         return QlInnerLoop(cfg, chains, tables, **kw)
 
     def inner_scores_ql(self, inner, theta, eps, worker, sign, rng_keys):
+        return inner.run(theta, eps, worker, sign, rng_keys=rng_keys)
+
+    def make_inner_ql_se(self, cfg, chains, tables, **kw):
+        return QlSeInnerLoop(cfg, chains, tables, **kw)
+
+    def inner_scores_ql_se(self, inner, theta, eps, worker, sign, rng_keys):
         return inner.run(theta, eps, worker, sign, rng_keys=rng_keys)
 
     def inner_scores(self, inner, theta, eps, worker, sign, agent_init, rng_keys):

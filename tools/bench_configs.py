@@ -17,9 +17,12 @@ from learning_environments_amd.agents.GTN import GTN_Master  # noqa: E402
 from learning_environments_amd import configs  # noqa: E402
 
 
-def run(name, cfg, gens=2, extra=None, force_gemm=False, median=False):
+def run(name, cfg, gens=2, extra=None, force_gemm=False, median=False, theta=None):
     torch.manual_seed(0)
-    m = GTN_Master(cfg, bohb_id=0, seed=7)
+    m = GTN_Master(cfg, bohb_id=0, seed=7, graph=False if theta is not None else None)
+    if theta is not None:    # a given synthetic env, put back before every generation: each one is the same work up to its noise draw
+        theta = torch.from_numpy(theta).to(m.theta.device)
+        m.theta.copy_(theta)
     if force_gemm:       # A/B aid: one sequential batch gradient (grad_chunk 0) = the GEMM-queue kernel instead of the register-resident one
         m.cfg.grad_chunk = 0
         m.inner = m.task.make_inner(m.cpw * m.n_local)
@@ -29,6 +32,9 @@ def run(name, cfg, gens=2, extra=None, force_gemm=False, median=False):
     if median:           # every generation timed on its own (a synchronise behind each), the median reported
         times = []
         for it in range(1, 1 + gens):
+            if theta is not None:
+                m.theta.copy_(theta)
+                torch.cuda.synchronize()
             t0 = time.perf_counter()
             m.step(it)
             torch.cuda.synchronize()
@@ -235,6 +241,22 @@ if __name__ == "__main__":
             print(json.dumps(dict(config="Pendulum RN + PPO 64x2 pop %d: the extra epochs alone" % pop, chains=res[10]["chains"], extra_epochs_per_chain=d_ep,
                                   us_per_learn_epoch=1e6 * d_t / d_ep, rollout_and_rest_s=res[10]["s_per_generation"] - 10 * d_t / d_ep,
                                   mfma_f32_frac_of_busy_cus=flops / d_t / 1e12 / (MFMA_F32_PEAK_TFLOPS * min(res[10]["chains"], 256) / 256.0))))
+    if "ql_se" in which:
+        # default_config_gridworld.yaml with synthetic_env_type 0: tabular QL on a Cliff VirtualEnv (three 52-32-x leakyrelu nets), 128 workers = 384
+        # chains, 100 training episodes, no early-out; theta = the fitted SE of the g15a fixture so that episodes have realistic lengths.  A warm-up
+        # generation, then the median of 7 timed one by one; per-step cost = seconds per generation / mean training steps of a chain
+        import numpy as np
+        th = np.load(os.path.join(ROOT, "tests", "golden", "g15a_ql_se_cliff_ql.npz"))["theta"]
+        c = configs.fixed_work(configs.cliff_syn_env_ql(128), 100)
+        c["agents"]["gtn"]["quit_when_solved"] = False
+        run("Cliff SE + QL pop 128 = 384 chains (100 episodes, no early-out, fitted SE)", c, gens=7, median=True, theta=th,
+            extra=lambda cfg, st, dt: dict(us_per_train_step_per_chain=1e6 * dt / max(1.0, st[:, 1].mean()), train_steps_per_chain=float(st[:, 1].mean()),
+                                           test_steps_per_chain=float(st[:, 3].mean())))
+        # the same launch on the freshly initialised SE: its done output never passes 0.5, every episode runs its 50 steps (5 000 training steps per
+        # chain against about 250 on the fitted SE, the same 100 test episodes) -- the two rows together separate the cost of a training step (three
+        # nets + argmax + update) from the cost of a test step (a table walk)
+        run("Cliff SE + QL pop 128 = 384 chains (100 episodes x 50 steps, freshly initialised SE)", configs.fixed_work(configs.cliff_syn_env_ql(128), 100),
+            gens=7, median=True, extra=lambda cfg, st, dt: dict(train_steps_per_chain=float(st[:, 1].mean()), test_steps_per_chain=float(st[:, 3].mean())))
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
