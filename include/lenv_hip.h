@@ -342,7 +342,8 @@ int lenv_dueling_se_inner_loop(const lenv_ddqn_cfg *cfg /*HOST*/, const float *t
                                void *workspace, size_t workspace_bytes, const lenv_inner_out *out /*HOST*/, void *stream);
 /* Workgroups per chain a production launch (counter RNG, no trace, no hp, no ICM) of this cfg will use: the wave-chain kernel of the
  * published Acrobot SE + DuelingDDQN shape runs a chain on a TEAM of 2 workgroups when 8 * ceil(chains / 8) * 2 of them are resident at
- * once (one per CU); every other launch: 1.  cfg->team_size 1 forces 1.  Same bits either way. */
+ * once (one per CU), with test_mode 0 and 1 alike, and so does its plain-DQN Acrobot shape; every other launch: 1.  cfg->team_size 1
+ * forces 1.  Same bits either way. */
 int lenv_dueling_team_size(const lenv_ddqn_cfg *cfg /*HOST*/, int64_t chains);
 /* Fresh agents (nn.Linear default init, the draw of lenv_nes_draw) for chains with their own shapes: row c of agent_init
  * [chains, lenv_dueling_num_params(cfg)] gets the parameters of a (hp->q_hidden[c], hp->q_layers[c]) network, keyed by
@@ -463,7 +464,8 @@ int lenv_td3_rn_inner_loop_icm(const lenv_td3_cfg *cfg /*HOST*/, const lenv_chai
                                const lenv_td3_out *out /*HOST*/, void *stream);
 /* Workgroups per chain a production launch (counter RNG, no trace, no hp, no ICM) of this cfg will use: the wave-chain kernel of the
  * published HalfCheetah RewardEnv + TD3 shape runs a chain on a TEAM of 6, 3 or 2 workgroups when 8 * ceil(chains / 8) * G of them
- * are resident at once (one per CU); every other launch: 1.  cfg->team_size caps it.  Same bits for every G. */
+ * are resident at once (one per CU), with test_mode 0 and 1 alike, and so do its other shapes; every other launch: 1.  cfg->team_size
+ * caps it.  Same bits for every G. */
 int lenv_td3_rn_team_size(const lenv_td3_cfg *cfg /*HOST*/, int64_t chains);
 int lenv_td3_agent_init_hp(const lenv_td3_cfg *cfg /*HOST*/, const lenv_chain_hp *hp, const uint64_t *rng_keys, int64_t chains,
                            float *agent_init, void *stream);

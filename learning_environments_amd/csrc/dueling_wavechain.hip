@@ -1336,7 +1336,8 @@ __global__ __launch_bounds__(NT) void dueling_wavechain_kernel(const WcArgs a)
             float obs[8];
             real_env_obs(env_id, st0, obs);
             for (int i = 0; i < S; ++i) state[i] = obs[i];
-        }
+            ctrl[12] = 0.0f;                               // the episode's training return (base_agent.py:102,121 episode_reward += reward, fp32;
+        }                                                  // every member rolls the episode out itself, so each one holds the same bits)
         __syncthreads();
         int ep_len = 0;
         for (int t = 0; t < cfg.max_steps; ++t) {
@@ -1394,6 +1395,7 @@ __global__ __launch_bounds__(NT) void dueling_wavechain_kernel(const WcArgs a)
             const float done_now = newrow[2 * S + 2];
             __syncthreads();
             if (tid < S) state[tid] = newrow[S + 1 + tid];
+            if (tid == 0) ctrl[12] = ctrl[12] + newrow[2 * S + 1];
             ++ep_len; ++train_steps;
             __syncthreads();
             WPT_MARK(1);
@@ -1522,16 +1524,26 @@ __global__ __launch_bounds__(NT) void dueling_wavechain_kernel(const WcArgs a)
         if (tid == 0 && g == 0 && a.out.episode_len) a.out.episode_len[chain * cfg.train_episodes + episode] = ep_len;
         __syncthreads();
         WPT_MARK(9);
-        test_phase();
+        // test_mode 1 (BaseAgent.train(env, test_env=None), the evaluation harness's call): no per-episode test; the meter takes the training
+        // return and env_solved runs on the training env, a VirtualEnv in every shape of this kernel (base_agent.py:49-62,134-148).  Both
+        // members of a team write the same bits into the chain's meter and evaluate the rule themselves, so they leave in the same episode.
+        if (cfg.test_mode == 0) test_phase();
         WPT_MARK(8);
         if (tid == 0) {
-            double sm = 0.0;
-            for (int i = 0; i < T; ++i) sm += ret[i];
-            const double tm = sm / (double)T;
+            double tm;
+            if (cfg.test_mode != 0) tm = (double)ctrl[12];
+            else {
+                double sm = 0.0;
+                for (int i = 0; i < T; ++i) sm += ret[i];
+                tm = sm / (double)T;
+            }
             meter[episode] = tm;
             if (g == 0 && a.out.episode_test_mean) a.out.episode_test_mean[chain * cfg.train_episodes + episode] = tm;
             int brk = 0;
-            if (learning) {
+            if (cfg.test_mode != 0)
+                brk = learning && meter_env_solved_inl(meter, episode + 1, cfg.early_out_num, /*virtual_rule*/ true, cfg.solved_reward,
+                                                       cfg.early_out_virtual_diff, episode, cfg.init_episodes);
+            else if (learning) {
                 int lo = episode + 1 - cfg.early_out_num; if (lo < 0) lo = 0;
                 double s2 = 0.0;
                 for (int i = lo; i <= episode; ++i) s2 += meter[i];
@@ -1610,7 +1622,7 @@ int lenv_wc_dueling_shape(const lenv_ddqn_cfg *cfg)
         if (cfg->agent_kind == sp.kind && cfg->env_id == sp.env && cfg->state_dim == sp.S && cfg->num_actions == sp.A &&
             (sp.kind == 0 || cfg->feature_dim == WC_H) && cfg->q_hidden == WC_H && cfg->q_layers == 2 && cfg->batch_size == WC_B && cfg->se_hidden == sp.Hse && cfg->se_layers == 1 &&
             cfg->test_episodes == sp.T && cfg->q_act == sp.q_act && cfg->se_act == sp.se_act && cfg->synthetic_env_type == 0 && !cfg->icm_enabled &&
-            !cfg->q_layer_norm && cfg->test_mode == 0)      // (test_mode 1, the evaluation harness's training call: GEMM-queue kernel)
+            !cfg->q_layer_norm)      // (either test_mode: 1, the evaluation harness's training call, is a run-time branch of the kernel)
             return s;
     }
     return 0;

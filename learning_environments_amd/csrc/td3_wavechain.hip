@@ -1368,7 +1368,8 @@ __global__ __launch_bounds__(NT) void td3_wavechain_kernel(const T3wArgs a)
         if (tid < S) state[tid] = EnvT::obs(tid, xs_d);
         __syncthreads();
         if (!VENV && (rtype == 1 || rtype == 2)) rn_eval(state, 12);
-        int ep_len = 0, env_steps = 0;
+        if (tid == 0) ctrl[14] = 0.0f;                     // the episode's training return (base_agent.py:102,121 episode_reward += reward, fp32;
+        int ep_len = 0, env_steps = 0;                     // every member rolls the episode out itself, so each one holds the same bits)
         for (int t = 0; t < cfg.max_steps; t += VENV ? KREP : 1) {      // (base_agent.py:104 range(0, max_steps, same_action_num); a RewardEnv's TimeLimit ends its loop)
             const int size_after = train_steps + 1 < rb_cap ? train_steps + 1 : rb_cap;
             const int new_pos = train_steps % rb_cap;
@@ -1432,6 +1433,7 @@ __global__ __launch_bounds__(NT) void td3_wavechain_kernel(const T3wArgs a)
             const float done_now = newrow[2 * S + A + 1];
             __syncthreads();
             if (tid < S) state[tid] = newrow[S + A + tid];
+            if (tid == 0) ctrl[14] = ctrl[14] + newrow[2 * S + A];      // (the stored row's reward: summed over same_action_num)
             ep_len += KREP; ++train_steps;                 // base_agent.py:122: episode_length += same_action_num
             __syncthreads();
             TPT_MARK(0);
@@ -1560,16 +1562,26 @@ __global__ __launch_bounds__(NT) void td3_wavechain_kernel(const T3wArgs a)
         if (tid == 0 && g == 0 && a.out.episode_len) a.out.episode_len[chain * cfg.train_episodes + episode] = ep_len;
         __syncthreads();
         TPT_MARK(10);
-        test_phase();
+        // test_mode 1 (BaseAgent.train(env, test_env=None), the evaluation harness's call): no per-episode test; the meter takes the training
+        // return and env_solved runs on the training env: the virtual rule on a VirtualEnv, the real rule on a RewardEnv's shaped returns
+        // (base_agent.py:49-62,134-148).  Every member of a team writes the same bits into the chain's meter and evaluates the rule itself, so all leave in the same episode.
+        if (cfg.test_mode == 0) test_phase();
         TPT_MARK(9);
         if (tid == 0) {
-            double sm_ = 0.0;
-            for (int i = 0; i < T; ++i) sm_ += ret[i];
-            const double tm = sm_ / (double)T;
+            double tm;
+            if (cfg.test_mode != 0) tm = (double)ctrl[14];
+            else {
+                double sm_ = 0.0;
+                for (int i = 0; i < T; ++i) sm_ += ret[i];
+                tm = sm_ / (double)T;
+            }
             meter[episode] = tm;
             if (g == 0 && a.out.episode_test_mean) a.out.episode_test_mean[chain * cfg.train_episodes + episode] = tm;
             int brk = 0;
-            if (learning) {
+            if (cfg.test_mode != 0)
+                brk = learning && meter_env_solved_inl(meter, episode + 1, cfg.early_out_num, /*virtual_rule*/ cfg.virtual_env != 0, cfg.solved_reward,
+                                                       cfg.early_out_virtual_diff, episode, cfg.init_episodes);
+            else if (learning) {
                 int lo = episode + 1 - cfg.early_out_num; if (lo < 0) lo = 0;
                 double s2 = 0.0;
                 for (int i = lo; i <= episode; ++i) s2 += meter[i];
@@ -1649,7 +1661,7 @@ using namespace lenv;
 int lenv_wc_td3_shape(const lenv_td3_cfg *cfg)
 {
     const int k_rep = cfg->same_action_num > 1 ? cfg->same_action_num : 1;
-    if (cfg->test_mode != 0) return 0;      // BaseAgent.train without a test env (the evaluation harness's call): GEMM-queue kernel
+    // (either test_mode: 1, BaseAgent.train without a test env -- the evaluation harness's call --, is a run-time branch of the kernel)
     // default_config_cmc.yaml: TD3 on a VirtualEnv (three 3-96-96-x nets), batch 256, delayed policy updates
     if (cfg->hidden == 128 && cfg->layers == 2 && cfg->batch_size == 256 && cfg->virtual_env && cfg->rn_hidden == 96 && cfg->rn_layers == 2 && cfg->policy_delay == 2 &&
         !cfg->icm_enabled && !cfg->use_layer_norm && !cfg->rn_layer_norm && cfg->env_id == LENV_ENV_CMC && cfg->state_dim == 2 && cfg->action_dim == 1 &&

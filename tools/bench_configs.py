@@ -55,6 +55,51 @@ def run(name, cfg, gens=2, extra=None, force_gemm=False, median=False, theta=Non
     return out
 
 
+def run_test_mode1_ab(name, cfg, gens=7):
+    """One `test_mode` 1 launch (BaseAgent.train without a test env, the evaluation harness's training call) per generation, on the wave-chain
+    kernel and -- the same launch, gtn.kernel_variant = NO_WAVECHAIN -- on the GEMM-queue kernel: two masters with the same seed in one
+    process, a warm-up generation each, then `gens` generations each in alternation, every one timed on its own.  Reports the medians, the
+    spread (max - min) of the samples and whether the wave-chain median lies below the other by more than the larger spread; the two
+    masters' scores, counters and updated theta must agree bit for bit after every generation."""
+    import copy
+    import ctypes as C
+    from learning_environments_amd import _lib
+    masters = {}
+    for label, variant in (("wavechain", 0), ("no_wavechain", _lib.VARIANT_NO_WAVECHAIN)):
+        c = copy.deepcopy(cfg)
+        c["agents"]["gtn"]["kernel_variant"] = variant
+        torch.manual_seed(0)
+        m = GTN_Master(c, bohb_id=0, seed=7, graph=False)
+        m.cfg.test_mode = 1
+        m.inner = m.task.make_inner(m.cpw * m.n_local)
+        m.step(0)
+        torch.cuda.synchronize()
+        masters[label] = m
+    chains = masters["wavechain"].cpw * masters["wavechain"].n_local
+    query = _lib.lib().lenv_td3_rn_team_size if isinstance(masters["wavechain"].cfg, _lib.Td3Cfg) else _lib.lib().lenv_dueling_team_size
+    teams = {label: int(query(C.byref(m.cfg), chains)) for label, m in masters.items()}
+    times = {label: [] for label in masters}
+    same = True
+    for it in range(1, 1 + gens):
+        for label, m in masters.items():
+            t0 = time.perf_counter()
+            m.step(it)
+            torch.cuda.synchronize()
+            times[label].append(time.perf_counter() - t0)
+        a, b = masters["wavechain"], masters["no_wavechain"]
+        same = same and torch.equal(a.inner.score, b.inner.score) and torch.equal(a.inner.stats, b.inner.stats) and torch.equal(a.theta, b.theta)
+    med = {label: sorted(t)[len(t) // 2] for label, t in times.items()}
+    spread = {label: max(t) - min(t) for label, t in times.items()}
+    st = masters["wavechain"].inner.stats.cpu().numpy()
+    out = dict(config=name, test_mode=1, chains=int(chains), team_size=teams, generations_each=gens,
+               ms_median={k: 1e3 * v for k, v in med.items()}, ms_spread={k: 1e3 * v for k, v in spread.items()},
+               ms_samples={k: [round(1e3 * x, 3) for x in v] for k, v in times.items()}, ratio=med["no_wavechain"] / med["wavechain"],
+               wavechain_faster_by_more_than_the_spread=bool(med["no_wavechain"] - med["wavechain"] > max(spread.values())),
+               bit_identical=bool(same), train_steps=int(st[:, 1].sum()), learn_steps=int(st[:, 2].sum()), test_steps=int(st[:, 3].sum()))
+    print(json.dumps(out))
+    return out
+
+
 import bench  # noqa: E402  (the byte / FLOP models live next to the contract line)
 HBM_PEAK_GBPS, MFMA_F32_PEAK_TFLOPS = bench.HBM_PEAK_GBPS, bench.MFMA_F32_PEAK_TFLOPS
 
@@ -257,6 +302,11 @@ if __name__ == "__main__":
         # nets + argmax + update) from the cost of a test step (a table walk)
         run("Cliff SE + QL pop 128 = 384 chains (100 episodes x 50 steps, freshly initialised SE)", configs.fixed_work(configs.cliff_syn_env_ql(128), 100),
             gens=7, median=True, extra=lambda cfg, st, dt: dict(train_steps_per_chain=float(st[:, 1].mean()), test_steps_per_chain=float(st[:, 3].mean())))
+    if "test_mode1" in which:
+        # the evaluation harness's training call on the wave-chain kernels' shapes: Acrobot SE + DuelingDDQN at 96 chains (ten init episodes + two
+        # learning ones of up to 500 steps) and the Pendulum RewardEnv + TD3 at 48 chains (twenty init episodes + two learning ones of 200 steps)
+        run_test_mode1_ab("Acrobot SE + DuelingDDQN pop 32, test_mode 1 (12 episodes)", configs.fixed_work(configs.acrobot_syn_env_duelingddqn(32), 12))
+        run_test_mode1_ab("Pendulum RN + TD3 pop 16, test_mode 1 (22 episodes x 200 steps)", configs.fixed_work(configs.pendulum_reward_env_td3(16), 22))
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
