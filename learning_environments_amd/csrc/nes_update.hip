@@ -60,12 +60,59 @@ __global__ void worker_best_multi_kernel(const double *chain_scores, int64_t pop
 
 constexpr int RT_NT = 1024;
 
+// np.add.reduce of `n` doubles a(0..n-1) in numpy's pairwise order (np.mean(scores_orig) of score_transform types 5-7; the oracle's
+// numpy_pairwise_sum is the same algorithm written recursively):
+//   n < 8      added left to right;
+//   n <= 128   eight interleaved accumulators r[j] += a(8k + j), combined as ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)), then the n % 8
+//              leftover elements added to that one by one;
+//   n > 128    split at n/2 rounded down to a multiple of 8, sum(left) + sum(right).
+// The recursion runs on an explicit stack: a frame is (offset, length) of a right half still to be summed and the left half's sum
+// it is to be added to.  A half is at least 64 elements long, so 64 frames cover every int64 length.  One thread calls this.
+constexpr int PW_DEPTH = 64;
+struct pw_stack { int64_t off[PW_DEPTH], len[PW_DEPTH]; double left[PW_DEPTH]; int has_left[PW_DEPTH]; };
+
+template <class A>
+__device__ double numpy_pairwise_sum(A a, int64_t n, pw_stack &st)
+{
+    int sp = 0;
+    int64_t off = 0, len = n;
+    for (;;) {
+        while (len > 128) {                                       // descend into the left halves, remembering the right ones
+            int64_t n2 = len / 2;
+            n2 -= n2 % 8;
+            st.off[sp] = off + n2; st.len[sp] = len - n2; st.has_left[sp] = 0; ++sp;
+            len = n2;
+        }
+        double res;
+        if (len < 8) {
+            res = 0.0;
+            for (int64_t i = 0; i < len; ++i) res += a(off + i);
+        } else {
+            double r[8];
+            for (int j = 0; j < 8; ++j) r[j] = a(off + j);
+            int64_t i = 8;
+            for (; i < len - (len % 8); i += 8)
+                for (int j = 0; j < 8; ++j) r[j] += a(off + i + j);
+            res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+            for (; i < len; ++i) res += a(off + i);
+        }
+        // `res` is a finished subtree: it is either the left operand of the innermost open frame, or that frame's right operand
+        for (;;) {
+            if (sp == 0) return res;
+            if (!st.has_left[sp - 1]) { st.left[sp - 1] = res; st.has_left[sp - 1] = 1; off = st.off[sp - 1]; len = st.len[sp - 1]; break; }
+            res = st.left[sp - 1] + res;
+            --sp;
+        }
+    }
+}
+
 // single workgroup: weights_out[i] = score_transform(scores)[i]
 __global__ __launch_bounds__(RT_NT) void score_transform_kernel(int type, const double *gathered, const double *rank_table,
                                                                 int64_t pop, double *weights_out)
 {
     __shared__ double red[RT_NT];
     __shared__ double sh[4];
+    __shared__ pw_stack pw;
     const int tid = threadIdx.x;
     auto score = [&](int64_t i) { return gathered[i * 4]; };
     auto orig = [&](int64_t i) { return gathered[i * 4 + 1]; };
@@ -99,17 +146,16 @@ __global__ __launch_bounds__(RT_NT) void score_transform_kernel(int type, const 
         for (int64_t i = tid; i < pop; i += RT_NT) weights_out[i] = weights_out[i] / mx;
         return;
     }
-    // sequential reductions by thread 0 keep python's sum()/min()/max() order
+    // sequential reductions by thread 0 keep python's sum()/min()/max() order; np.mean(scores_orig) keeps numpy's (pairwise) one
     if (tid == 0) {
-        double mn = score(0), mx = score(0), so = 0.0;
+        double mn = score(0), mx = score(0);
         int64_t am = 0, cnt = 0;
         for (int64_t i = 0; i < pop; ++i) {
             const double s = score(i);
             if (s < mn) mn = s;
             if (s > mx) { mx = s; am = i; }
-            so += orig(i);
         }
-        const double avg = so / (double)pop;
+        const double avg = numpy_pairwise_sum(orig, pop, pw) / (double)pop;
         for (int64_t i = 0; i < pop; ++i) cnt += score(i) > avg + 1e-6;
         sh[0] = mn; sh[1] = mx; sh[2] = avg; sh[3] = (double)am;
         red[0] = (double)cnt;

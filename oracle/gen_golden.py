@@ -350,6 +350,84 @@ def gen_g7():
 
 
 # ------------------------------------------------------------------------------------------------
+# G7P: GTN_Master.score_transform at the population sizes where np.mean changes its summation order (sequential below 8,
+# eight accumulators up to 128, recursive halving above), on the score sets a run produces, + update_env at pop 17
+# ------------------------------------------------------------------------------------------------
+G7P_POPS = (2, 7, 8, 9, 16, 64, 128, 130, 257)
+G7P_SETS = ("cont", "int", "timeout", "below", "equal")
+
+
+def g7p_score_sets(pop):
+    """{name: (scores, scores_orig)}; every draw from a RandomState of this pop's own, so the file does not depend on what ran before."""
+    rng = np.random.RandomState(7700 + pop)
+    sets = {}
+    orig = rng.normal(-300.0, 50.0, pop)
+    sets["cont"] = (orig + rng.normal(0.0, 20.0, pop), orig)                  # continuous negative returns (Pendulum-like)
+    orig = rng.randint(9, 201, pop).astype(np.float64)
+    sets["int"] = (rng.choice(np.arange(1, 2001), pop, replace=False).astype(np.float64), orig)     # integer returns, no two scores equal
+    orig = rng.normal(-300.0, 50.0, pop)
+    sc = orig + rng.normal(0.0, 20.0, pop)
+    k = max(1, pop // 4)
+    sc[rng.choice(pop, k, replace=False)] = -1e9                               # timed-out workers
+    orig = orig.copy()
+    orig[rng.choice(pop, max(1, pop // 8), replace=False)] = -1e9
+    sets["timeout"] = (sc, orig)
+    orig = rng.normal(-300.0, 50.0, pop)
+    sets["below"] = (orig.min() - rng.uniform(0.0, 40.0, pop), orig)          # no score above avg + 1e-6: types 5-7 give zeros
+    sets["equal"] = (np.full(pop, -123.456), np.full(pop, -123.456))
+    if pop <= 16:
+        orig = rng.normal(-300.0, 50.0, pop)
+        vals = orig[: max(1, pop // 3)] + 10.0
+        sets["tied"] = (vals[rng.randint(0, vals.size, pop)], orig)             # ties: np.argsort's order among them is its own (SIMD sorts are not stable)
+    return sets
+
+
+def gen_g7p():
+    from agents.GTN import GTN_Master
+    cfg = load_cfg("default_config_cartpole_syn_env.yaml")
+    n = 17
+    cfg["agents"]["gtn"]["num_workers"] = n
+    cfg["envs"]["CartPole-v0"]["hidden_size"] = 31        # theta of 843 elements: off the update kernel's 256-wide blocks, and a small file
+    out = {}
+    with quiet():
+        seed_all(770)
+        m = GTN_Master(cfg, bohb_id=0)
+        for pop in G7P_POPS:
+            for name, (sc, so) in g7p_score_sets(pop).items():
+                pre = "p%d_%s_" % (pop, name)
+                out[pre + "scores"], out[pre + "scores_orig"] = sc, so
+                for t in range(8):
+                    if name == "tied" and t not in (1, 2, 3):
+                        continue
+                    if name == "equal" and t in (1, 2, 3) and pop > 16:
+                        continue                                                # all-equal IS a tie; above pop 16 np.argsort's order is unspecified
+                    m.score_transform_type = t
+                    m.score_list = list(sc); m.score_orig_list = list(so)
+                    m.score_transform()
+                    out[pre + "tf%d" % t] = np.array(m.score_transform_list, np.float64)
+        rng = np.random.RandomState(7717)
+        sc, so = g7p_score_sets(n)["cont"]
+        theta0 = se_theta(m.synthetic_env_orig)
+        eps = []
+        for e in m.eps_list:
+            flat = (rng.randn(theta0.size) * 0.0124).astype(np.float32)
+            e.load_state_dict(_sd_from_flat(e, flat))
+            eps.append(flat)
+        m.score_transform_type = 7
+        m.score_list = list(sc); m.score_orig_list = list(so)
+        m.score_transform()
+        w = np.array(m.score_transform_list)
+        m.update_env()
+        theta1 = se_theta(m.synthetic_env_orig)
+        m.nes_step_size = True
+        m.weight_decay = 0.01
+        m.update_env()
+        theta2 = se_theta(m.synthetic_env_orig)
+    save("g7p_master_pops", pops=np.array(G7P_POPS), u_scores=sc, u_scores_orig=so, u_theta0=theta0, u_eps=np.stack(eps), u_weights=w,
+         u_step_size=np.array(cfg["agents"]["gtn"]["step_size"]), u_theta1=theta1, u_theta2=theta2, **out)
+
+
+# ------------------------------------------------------------------------------------------------
 # G8: full GTN_Worker.calc_score with recorded RNG tapes + per-step trace (cfg 1 shapes)
 # ------------------------------------------------------------------------------------------------
 class Recorder(object):
@@ -1853,7 +1931,7 @@ def gen_g12t(name, seed, vary_seed, agents_num=2, ckpt="ckpt_cartpole_se_referen
 
 def main():
     # no arguments (or "all"): every fixture under tests/golden is regenerated (the full-shape runs g8df / g8tf take minutes each)
-    ALL = ["g1", "g1ln", "g2", "g3", "g4", "g4d", "g4t", "g6", "g7", "g8", "g8d", "g8t", "g9", "g10", "g2f", "ckpt", "g8w", "g6m", "g9x",
+    ALL = ["g1", "g1ln", "g2", "g3", "g4", "g4d", "g4t", "g6", "g7", "g7p", "g8", "g8d", "g8t", "g9", "g10", "g2f", "ckpt", "g8w", "g6m", "g9x",
            "g8tv", "g8ts", "g8p", "g8c", "g8cf", "g8co", "g8pf", "g8ti", "g8tf", "g8tln", "g8df", "g8l2", "g8ln", "g8seln", "g8tseln", "g8tdseln", "g9ln", "g8m", "g8r", "g8rl", "g8i", "g8v", "g11", "g4td", "g8td", "g8k", "g9k", "g8long"]
     which = sys.argv[1:] or ALL
     if "all" in which:
@@ -1897,6 +1975,8 @@ def main():
         gen_g11()
     if "g7" in which:
         gen_g7()
+    if "g7p" in which:
+        gen_g7p()
     if "g4t" in which:
         gen_g4t()
     if "g8t" in which:

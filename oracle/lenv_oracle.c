@@ -1631,6 +1631,34 @@ static void argsort_stable(const double *v, int64_t n, int descending, int64_t *
     }
 }
 
+/* np.add.reduce of a contiguous double array = numpy's pairwise summation: fewer than 8 elements are added left to right;
+ * up to 128 go through eight interleaved accumulators r[j] += a[8k + j], combined as ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)),
+ * the n % 8 leftover elements added to that one by one; above 128 the array is split at n/2 rounded down to a multiple of 8 and
+ * the two halves' sums are added.  (The reduction starts from the identity 0.0, which changes no finite sum.) */
+static double numpy_pairwise_sum(const double *a, int64_t n)
+{
+    if (n < 8) {
+        double res = 0.0;
+        for (int64_t i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    if (n <= 128) {
+        double r[8];
+        int64_t i;
+        for (int j = 0; j < 8; ++j) r[j] = a[j];
+        for (i = 8; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += a[i];
+        return res;
+    }
+    int64_t n2 = n / 2;
+    n2 -= n2 % 8;
+    return numpy_pairwise_sum(a, n2) + numpy_pairwise_sum(a + n2, n - n2);
+}
+
+double orc_numpy_sum(const double *a, int64_t n) { return numpy_pairwise_sum(a, n); }
+
 int orc_score_transform(int type, const double *scores_in, const double *scores_orig, int64_t n, double *out)
 {
     double *scores = malloc(sizeof(double) * n);
@@ -1660,11 +1688,7 @@ int orc_score_transform(int type, const double *scores_in, const double *scores_
         for (int64_t i = 1; i < n; ++i) if (scores_in[i] > scores_in[am]) am = i;
         for (int64_t i = 0; i < n; ++i) scores[i] = i == am ? 1.0 : 0.0;
     } else if (type == 5 || type == 6 || type == 7) {
-        /* np.mean: pairwise summation for n >= 8 blocks; for the population sizes here (<= 1024)
-         * the fixture test pins equality on non-pathological inputs */
-        double sm = 0.0;
-        for (int64_t i = 0; i < n; ++i) sm += scores_orig[i];
-        double avg = sm / (double)n;
+        const double avg = numpy_pairwise_sum(scores_orig, n) / (double)n;       /* np.mean(scores_orig) */
         int64_t cnt = 0, am = 0;
         double mx = scores_in[0];
         for (int64_t i = 0; i < n; ++i) { if (scores_in[i] > avg + 1e-6) ++cnt; if (scores_in[i] > mx) { mx = scores_in[i]; am = i; } }

@@ -369,6 +369,7 @@ void orc_worker_best(const double *score_add, const double *score_sub, int64_t p
 int orc_worker_best_multi(const double *score_add, const double *score_sub, int64_t pop, int G, int mirrored, int grad_eval_type,
                           double *score_best, float *sign);
 /* GTN_master.py:197-265; ties broken by lower index first (documented stable order) */
+double orc_numpy_sum(const double *a, int64_t n);   /* np.add.reduce order (pairwise), the sum behind np.mean in score_transform types 5-7 */
 int orc_score_transform(int type, const double *scores, const double *scores_orig, int64_t n, double *out);
 /* GTN_master.py:267-298: theta <- theta*(1-wd); theta += ss*w_i*sign_i*eps_i sequentially over i */
 void orc_update_env(float *theta, const float *eps, const float *sign, const double *weights, int64_t pop, int64_t p_theta,

@@ -383,6 +383,14 @@ def worker_best(score_add, score_sub, mirrored=True):
     return best, sign
 
 
+def numpy_sum(a):
+    """np.add.reduce of a contiguous float64 vector, in numpy's pairwise order (orc_score_transform's mean)."""
+    a = np.ascontiguousarray(a, np.float64)
+    L = lib()
+    L.orc_numpy_sum.restype = C.c_double
+    return float(L.orc_numpy_sum(_p(a, C.c_double), C.c_int64(a.size)))
+
+
 def score_transform(type_, scores, scores_orig):
     s = np.ascontiguousarray(scores, np.float64)
     so = np.ascontiguousarray(scores_orig, np.float64)

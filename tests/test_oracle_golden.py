@@ -155,6 +155,75 @@ def test_g7_master(golden):
     assert np.array_equal(th2, g["theta2"])
 
 
+def g7p_cases(g):
+    """(pop, set name, type, scores, scores_orig, reference weights) of every score_transform call recorded in fixture G7P."""
+    for pop in [int(v) for v in g["pops"]]:
+        for name in ("cont", "int", "timeout", "below", "equal", "tied"):
+            pre = "p%d_%s_" % (pop, name)
+            if pre + "scores" not in g:
+                continue
+            for t in range(8):
+                if pre + "tf%d" % t in g:
+                    yield pop, name, t, g[pre + "scores"], g[pre + "scores_orig"], g[pre + "tf%d" % t]
+
+
+def g7p_check_rank_type(got, ref, scores, msg):
+    """Types 1-3 against the reference: element by element at G7's 1e-15 where no two scores are equal.  Where some are (the tied,
+    all-equal and several-time-outs sets) the order np.argsort gave them in the fixture is that numpy build's own -- its SIMD sorts
+    are not stable even at pop <= 16 -- so, as for G7's tied set, the multiset of weights and each tie group's weight must agree."""
+    if np.unique(scores).size == scores.size:
+        np.testing.assert_allclose(got, ref, rtol=1e-15, atol=1e-15, err_msg=msg)
+        return
+    np.testing.assert_allclose(np.sort(got), np.sort(ref), rtol=1e-15, atol=1e-15, err_msg=msg)
+    for val in np.unique(scores):
+        sel = scores == val
+        np.testing.assert_allclose(got[sel].sum(), ref[sel].sum(), rtol=1e-14, atol=1e-15, err_msg=msg)
+        if sel.sum() == 1:
+            np.testing.assert_allclose(got[sel], ref[sel], rtol=1e-15, atol=1e-15, err_msg=msg)
+
+
+def test_g7p_score_transform_at_numpy_summation_boundaries(golden):
+    """GTN_Master.score_transform of the reference at pops 2..257 (np.mean sums sequentially below 8 elements, through eight
+    accumulators up to 128, by recursive halving above) on continuous, integer, timed-out, nothing-above-average, all-equal and
+    (pop <= 16) tied score sets.  Types 0 and 4-7 are plain fp64 arithmetic in the reference's order: equal bit for bit.
+    Types 1-3 go through log(): the 1e-15 of G7."""
+    g = golden("g7p_master_pops")
+    seen, bad = set(), []
+    for pop, name, t, sc, so, ref in g7p_cases(g):
+        got = orc.score_transform(t, sc, so)
+        seen.add((pop, name, t))
+        if t in (1, 2, 3):
+            g7p_check_rank_type(got, ref, sc, "pop %d %s type %d" % (pop, name, t))
+        elif not np.array_equal(got, ref):
+            bad.append((pop, name, t))
+    assert not bad, "%d of %d cases differ from the reference: %s" % (len(bad), len(seen), bad)
+    pops = (2, 7, 8, 9, 16, 64, 128, 130, 257)
+    for pop in pops:
+        for name in ("cont", "int", "timeout", "below", "equal"):
+            for t in range(8):
+                assert (pop, name, t) in seen or (name == "equal" and t in (1, 2, 3) and pop > 16), (pop, name, t)
+        for t in (1, 2, 3):
+            assert ((pop, "tied", t) in seen) == (pop <= 16)
+    for pop in pops:                               # the set that must give zeros does
+        for t in (5, 6, 7):
+            assert not g["p%d_below_tf%d" % (pop, t)].any()
+    # np.mean itself: the oracle's summation against numpy's on the fixture's vectors and across the 8 / 128 boundaries
+    rng = np.random.RandomState(5)
+    for n in list(range(1, 300)) + [511, 512, 513, 1000, 1024, 1025, 2500, 4099]:
+        a = rng.normal(-300.0, 50.0, n)
+        assert orc.numpy_sum(a) == np.add.reduce(a), n
+    # update_env at pop 17, P 843 (not a multiple of 256)
+    pop, P = g["u_eps"].shape
+    assert (pop, P % 256 != 0) == (17, True)
+    w = orc.score_transform(7, g["u_scores"], g["u_scores_orig"])
+    assert np.array_equal(w, g["u_weights"])
+    sign = np.ones(pop, np.float32)
+    th1 = orc.update_env(g["u_theta0"], g["u_eps"], sign, w, float(g["u_step_size"]))
+    assert np.array_equal(th1, g["u_theta1"])
+    th2 = orc.update_env(th1, g["u_eps"], sign, w, float(g["u_step_size"]), nes_step_size=True, weight_decay=0.01)
+    assert np.array_equal(th2, g["u_theta2"])
+
+
 @pytest.mark.parametrize("name,chunk", [("g8_calc_score_cartpole_a", 13), ("g8_calc_score_cartpole_b", 13),
                                         ("g8w_calc_score_cartpole_ringwrap", 13),
                                         ("g8l2_calc_score_acrobot_ddqn_2layer", 0),    # Critic_DQN 6-128-128-3: batch gradient
