@@ -185,6 +185,28 @@ int lenv_se_step_population(const lenv_mlp_desc *state_net /*HOST*/, const lenv_
                             float *done, void *stream);
 
 /*
+ * The same step for ACTION VECTORS (the continuous-action SEs: Pendulum, MountainCarContinuous, HalfCheetah), with the `same_action_num`
+ * repeat of EnvWrapper.step's virtual branch (envs/env_wrapper.py:28-30) inside the launch.  Descriptor checks, eps == NULL, the LayerNorm
+ * layout and the raw done-net output as in lenv_se_step_population.  action [chains,n_per_chain,A] is the row the nets see (input row =
+ * [action | state], envs/virtual_env.py:43-54; a one-hot row gives lenv_se_step_population's bits).  repeat >= 1 (else LENV_ERR_INVALID):
+ * that many SE steps with the same action, each fed the previous next state; reward = the fp32 sum left to right, next_state / done of the
+ * last step, no break on done.  Every element of W_c is fmaf(sign[c], eps[worker[c]][i], theta[i]); every dot product the canonical order.
+ * Two kernels: W_c resident in LDS when it fits 160 KiB in the padded layout of the kernel (rows of round8(n_in) + 4 floats) next to the
+ * buffers of one block of 8 rows -- ask lenv_se_step_vec_path rather than estimating it --, else streamed through LDS in K-panels against
+ * blocks of rows (a weight leaves HBM once per chain, repeat and block of 8 / 16 / 32 rows).  chains == 0 returns LENV_OK after the
+ * pointer checks, like lenv_se_step_population; chains >= 2^31 is LENV_ERR_UNSUPPORTED.  Takes every shape lenv_mlp_forward takes with
+ * hidden <= 256, layers 1..3 and S + A <= 256; beyond that LENV_ERR_UNSUPPORTED.
+ */
+int lenv_se_step_population_vec(const lenv_mlp_desc *state_net /*HOST*/, const lenv_mlp_desc *reward_net /*HOST*/,
+                                const lenv_mlp_desc *done_net /*HOST*/, const float *theta, const float *eps,
+                                const int32_t *worker, const float *sign, int64_t chains, int32_t n_per_chain, int32_t repeat,
+                                const float *state, const float *action, float *next_state, float *reward,
+                                float *done, void *stream);
+/* HOST: which kernel that launch runs: 0 = resident, 1 = streaming, or a negative LENV_ERR_* (the launch's own checks). */
+int32_t lenv_se_step_vec_path(const lenv_mlp_desc *state_net /*HOST*/, const lenv_mlp_desc *reward_net /*HOST*/,
+                              const lenv_mlp_desc *done_net /*HOST*/, int32_t n_per_chain);
+
+/*
  * DDQN TD forward over replay minibatches (agents/DDQN.py:63-85): for every chain, gathers rows
  * idx[c,b] of its replay buffer (row = [s(S), a, s'(S), r, done], stride row_stride floats) and writes
  * q_sa[c,b] = Q(s)[a], y[c,b] = r + gamma * Q_target(s')[argmax Q(s')] * (1 - done).

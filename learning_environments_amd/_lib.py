@@ -194,6 +194,8 @@ SIGNATURES = {
     "lenv_mlp_num_params": (_i64, [_P(MlpDesc)]),
     "lenv_mlp_forward": (C.c_int, [_P(MlpDesc), _vp, _vp, _i64, _vp, _vp]),
     "lenv_se_step_population": (C.c_int, [_P(MlpDesc)] * 3 + [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lenv_se_step_population_vec": (C.c_int, [_P(MlpDesc)] * 3 + [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lenv_se_step_vec_path": (_i32, [_P(MlpDesc)] * 3 + [_i32]),
     "lenv_qnet_td_forward": (C.c_int, [_P(MlpDesc), _vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),
     "lenv_chain_key": (C.c_uint64, [C.c_uint64] * 4),
     "lenv_rng_unit": (_f64, [C.c_uint64, C.c_uint32, C.c_uint64]),

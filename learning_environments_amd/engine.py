@@ -102,6 +102,41 @@ def se_step_population(descs, theta, eps, worker, sign, state, action):
     return ns, r, d
 
 
+def se_step_vec_path(descs, n_per_chain=1):
+    """Which kernel lenv_se_step_population_vec runs for these nets (host only): 0 = weights resident in LDS, 1 = streamed through it."""
+    sn, rn, dn = descs
+    path = int(_lib.lib().lenv_se_step_vec_path(C.byref(sn), C.byref(rn), C.byref(dn), int(n_per_chain)))
+    _lib.check(path if path < 0 else 0, "lenv_se_step_vec_path")
+    return path
+
+
+def se_step_population_vec(descs, theta, eps, worker, sign, state, action, repeat=1):
+    """se_step_population for action VECTORS: state [chains,S] or [chains,n,S]; action fp32 [chains,A] or [chains,n,A], the row the nets
+    see (a continuous action, or a one-hot).  `repeat` = same_action_num of EnvWrapper.step's virtual branch: that many SE steps on the
+    same action, each fed the previous next state, rewards summed in fp32; next_state / done of the last.  Returns (next_state, reward,
+    done) shaped like se_step_population's."""
+    dev = require_device()
+    sn, rn, dn = descs
+    squeeze = state.dim() == 2
+    if squeeze:
+        state, action = state.unsqueeze(1), action.unsqueeze(1)
+    chains, n, S = state.shape
+    if tuple(action.shape) != (chains, n, sn.in_dim - S):
+        raise ValueError("action must be [chains,n,%d] next to state [chains,n,%d]" % (sn.in_dim - S, S))
+    _chk(theta, torch.float32, "theta"); _chk(state, torch.float32, "state"); _chk(action, torch.float32, "action")
+    _chk(eps, torch.float32, "eps"); _chk(worker, torch.int32, "worker"); _chk(sign, torch.float32, "sign")
+    ns = torch.empty((chains, n, S), dtype=torch.float32, device=dev)
+    r = torch.empty((chains, n), dtype=torch.float32, device=dev)
+    d = torch.empty((chains, n), dtype=torch.float32, device=dev)
+    rc = _lib.lib().lenv_se_step_population_vec(C.byref(sn), C.byref(rn), C.byref(dn), _ptr(theta), _ptr(eps), _ptr(worker),
+                                                _ptr(sign), chains, n, int(repeat), _ptr(state), _ptr(action), _ptr(ns), _ptr(r),
+                                                _ptr(d), _stream())
+    _lib.check(rc, "lenv_se_step_population_vec")
+    if squeeze:
+        return ns[:, 0], r[:, 0], d[:, 0]
+    return ns, r, d
+
+
 def qnet_td_forward(qd, online, target, replay, idx, gamma):
     """online/target [chains,P]; replay [chains,cap,row_stride]; idx int32 [chains,B] -> (q_sa, y) [chains,B]."""
     dev = require_device()

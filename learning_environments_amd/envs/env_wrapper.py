@@ -53,14 +53,20 @@ class EnvWrapper(nn.Module):
         obs_t = as_f32(obs)
         return (obs_t.unsqueeze(0) if obs_t.dim() == 0 else obs_t), as_f32(total), as_f32(done)
 
-    def step_population(self, actions, states, eps=None, worker=None, sign=None):
-        """Batched fast path: chain c steps the SE with weights theta + sign[c]*eps[worker[c]].
-        actions int32 [chains], states fp32 [chains,S] (device).  Returns device tensors."""
+    def step_population(self, actions, states, eps=None, worker=None, sign=None, repeat=1):
+        """Batched fast path: chain c steps the SE with weights theta + sign[c]*eps[worker[c]], `repeat` times on the same action
+        (what `same_action_num` does in `step`: rewards summed, next state / done of the last step).
+        Discrete action space: actions int32 [chains] (or [chains,n]); continuous: fp32 [chains,A] (or [chains,n,A]).
+        states fp32 [chains,S] (or [chains,n,S]), all on the device.  Returns device tensors."""
         if not self.is_virtual_env():
             raise NotImplementedError("step_population is defined for virtual envs")
+        args = (self.env.descs(), self.env.step_params(), self.env.step_eps(eps), worker, sign, states)
         if not self.has_discrete_action_space():
-            raise NotImplementedError("step_population takes action indices: virtual envs over a discrete action space")
-        return engine.se_step_population(self.env.descs(), self.env.step_params(), self.env.step_eps(eps), worker, sign, states, actions)
+            return engine.se_step_population_vec(*args, actions, repeat=repeat)
+        if repeat == 1:
+            return engine.se_step_population(*args, actions)
+        one_hot = torch.nn.functional.one_hot(actions.long(), self.get_action_dim()).to(torch.float32)
+        return engine.se_step_population_vec(*args, one_hot, repeat=repeat)
 
     def reset(self):
         """CPU fp32 state of a fresh episode; a virtual env over a discrete observation space hands back the index."""
