@@ -288,6 +288,16 @@ int lenv_ql_rn_inner_loop(const lenv_ql_cfg *cfg /*HOST*/, const float *theta, c
                           const float *sign, const float *shaped_override, const int32_t *next_state, const double *reward,
                           const uint8_t *done, const uint64_t *rng_keys, const lenv_tapes *tapes /*HOST, may be NULL*/,
                           int64_t chains, const lenv_ql_out *out /*HOST struct of device ptrs*/, void *stream);
+/* The same loop for a population of agents with their own hyper-parameters (experiments/GTNC_evaluate_gridworld_transfer_vary_hp.py:92-123:
+ * every agent draws alpha and gamma): chain c learns with alpha[c] and bootstraps with gamma[c] (fp64, the python floats of the reference),
+ * and, because BaseAgent.train hands gamma to the env (base_agent.py:86), its shaped-reward table of reward types 1 / 2 -- and its row of
+ * out->shaped -- uses (float)gamma[c].  A NULL array = cfg's value for every chain; lenv_ql_rn_inner_loop is the NULL / NULL call.
+ * (Added under ABI 7: a new entry point only, no struct changed.) */
+int lenv_ql_rn_inner_loop_hp(const lenv_ql_cfg *cfg /*HOST*/, const double *alpha /*DEVICE [chains], may be NULL*/,
+                             const double *gamma /*DEVICE [chains], may be NULL*/, const float *theta, const float *eps, const int32_t *worker,
+                             const float *sign, const float *shaped_override, const int32_t *next_state, const double *reward,
+                             const uint8_t *done, const uint64_t *rng_keys, const lenv_tapes *tapes /*HOST, may be NULL*/,
+                             int64_t chains, const lenv_ql_out *out /*HOST struct of device ptrs*/, void *stream);
 
 /*
  * The tabular agents on a gridworld VirtualEnv (synthetic_env_type 0): GTN_Worker.calc_score (agents/GTN_worker.py:187-221) with

@@ -220,6 +220,7 @@ SIGNATURES = {
     "lenv_cont_env_reset": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "lenv_cont_env_step": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lenv_ql_rn_inner_loop": (C.c_int, [_P(QlCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(Tapes), _i64, _P(QlOut), _vp]),
+    "lenv_ql_rn_inner_loop_hp": (C.c_int, [_P(QlCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(Tapes), _i64, _P(QlOut), _vp]),
     "lenv_ql_se_num_params": (_i64, [_P(QlCfg)]),
     "lenv_ql_se_lds_bytes": (_i64, [_P(QlCfg)]),
     "lenv_ql_se_workspace_bytes": (_i64, [_P(QlCfg), _i64]),

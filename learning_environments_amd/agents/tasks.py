@@ -7,6 +7,8 @@ combination owns one fused kernel:
     DDQN_vary / DuelingDDQN_vary on a VirtualEnv  -> lenv_dueling_se_inner_loop_hp (per-chain lr / batch / width / depth)
     TD3_vary on a RewardEnv over the stand-in     -> lenv_td3_rn_inner_loop_hp
     QL / QL_cb / SARSA / SARSA_cb on a RewardEnv over a gridworld (type 1) -> lenv_ql_rn_inner_loop (BASELINE config 4)
+    the same agents with their own alpha / gamma per chain (the gridworld transfer scripts; experiments/transfer_gridworld.py builds QlRnTask itself: the
+        variation lives in the script, no agent name selects it) -> lenv_ql_rn_inner_loop_hp
     QL / QL_cb / SARSA / SARSA_cb on a VirtualEnv over a gridworld (type 0) -> lenv_ql_se_inner_loop
     TD3  on a RewardEnv over the HalfCheetah stand-in -> lenv_td3_rn_inner_loop (BASELINE config 5)
     TD3_discrete_vary on a VirtualEnv (CartPole / Acrobot / MountainCar) -> lenv_td3d_inner_loop

@@ -16,7 +16,10 @@ rule is restated here from the published algorithm:
 The reference's ConfigurationSpace is created WITHOUT a seed (its RandomState comes from OS entropy), so no bit stream can
 be matched: parity is the distribution, plus a deterministic replay of recorded draws (fixture G8V).  Here u comes from the
 chain's counter RNG (stream STREAM_VARY_HP, one index per hyper-parameter in ConfigSpace's alphabetical order), so a
-generation is reproducible from (seed, generation, worker, kind) like everything else in the inner loop."""
+generation is reproducible from (seed, generation, worker, kind) like everything else in the inner loop.
+
+The gridworld transfer script (experiments/GTNC_evaluate_gridworld_transfer_vary_hp.py:92-123) varies the tabular agents the same way, in
+the script instead of an agent class: alpha and gamma, each a UniformFloatHyperparameter(log=False) on [0.1, 1] (vary_tabular)."""
 import math
 
 STREAM_VARY_HP = 11                                   # csrc/lenv_device.cuh
@@ -55,8 +58,24 @@ def vary_hyperparameters(agent_section, units):
             "hidden_layer": uniform_int(u["hidden_layer"], *bd["hidden_layer"], log=False)}
 
 
-def chain_units(key):
-    """The four draws of the chain with counter-RNG key `key` (host function of the library, no device work)."""
+TABULAR_HP_ORDER = ("alpha", "gamma")                 # ConfigSpace's alphabetical order
+TABULAR_HP_BOUNDS = {"alpha": (0.1, 1.0), "gamma": (0.1, 1.0)}
+
+
+def uniform_float(u, lower, upper):
+    """UniformFloatHyperparameter(log=False): value = u * (upper - lower) + lower, clipped to the bounds."""
+    return min(upper, max(lower, u * (upper - lower) + lower))
+
+
+def vary_tabular(agent_section, units):
+    """units: two uniforms in [0, 1) in TABULAR_HP_ORDER.  Returns {alpha, gamma} as the script's vary_hp draws them; the section's own alpha /
+    gamma are only the (unused) default values of the space, so agent_section does not enter the draw."""
+    u = dict(zip(TABULAR_HP_ORDER, units))
+    return {k: uniform_float(u[k], *TABULAR_HP_BOUNDS[k]) for k in TABULAR_HP_ORDER}
+
+
+def chain_units(key, n=len(HP_ORDER)):
+    """The first n (default: the four of HP_ORDER) draws of the chain with counter-RNG key `key` (host function of the library, no device work)."""
     from .. import _lib
     L = _lib.lib()
-    return [L.lenv_rng_unit(int(key), STREAM_VARY_HP, i) for i in range(len(HP_ORDER))]
+    return [L.lenv_rng_unit(int(key), STREAM_VARY_HP, i) for i in range(n)]

@@ -22,6 +22,7 @@ struct QlArgs {
     const float *shaped_override;
     const int32_t *next_state; const double *reward; const uint8_t *done;
     const uint64_t *rng_keys;
+    const double *hp_alpha, *hp_gamma;   // [chains] the chains' own alpha / gamma (lenv_ql_rn_inner_loop_hp); NULL: cfg's value for every chain
     lenv_tapes tapes;
     lenv_ql_out out;
     int64_t P;
@@ -38,11 +39,12 @@ __device__ __forceinline__ int ql_argmax_f32(const double *row, int n)
 
 // phi(s) = reward_net(one_hot(s)) for all states with W = theta + sign*eps[worker] (reward_env.py:74-76,
 // GTN_worker.py:165-175), then RewardEnv._calc_reward for every (s,a) (reward_env.py:81-110) in fp32, left to right.
-// One wave; phi/shaped are LDS (or global) arrays of the calling wave.  Ends with a barrier.
+// One wave; phi/shaped are LDS (or global) arrays of the calling wave.  `gamma` is the agent's (BaseAgent.train hands it to the env,
+// base_agent.py:86): the chain's own under lenv_ql_rn_inner_loop_hp.  Ends with a barrier.
 __device__ __forceinline__ void rn_phi_and_shaped(const lenv_ql_cfg &cfg, const float *theta, const float *eps_all,
                                                   const int32_t *worker, const float *sign, const float *shaped_override,
                                                   const int32_t *next_state, const double *reward, int64_t P, int64_t chain,
-                                                  int lane, float *phi, float *shaped, float *shaped_out, float *phi_out, float *hbuf)
+                                                  double gamma, int lane, float *phi, float *shaped, float *shaped_out, float *phi_out, float *hbuf)
 {
     const int N = cfg.n_states, A = cfg.n_actions, H = cfg.rn_hidden;
     const int t = cfg.reward_env_type;
@@ -103,7 +105,7 @@ __device__ __forceinline__ void rn_phi_and_shaped(const lenv_ql_cfg &cfg, const 
         for (int s = lane; s < N; s += 64) phi[s] = 0.0f;
     }
     __syncthreads();
-    const float g32 = (float)cfg.gamma;
+    const float g32 = (float)gamma;
     for (int i = lane; i < N * A; i += 64) {
         float v;
         if (shaped_override) v = shaped_override[i];
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(64) void rn_shape_kernel(const QlArgs a, float *phi
     const int N = a.cfg.n_states, A = a.cfg.n_actions;
     float *phi = reinterpret_cast<float *>(lds_raw), *shaped = phi + N;
     const int64_t chain = blockIdx.x;
-    rn_phi_and_shaped(a.cfg, a.theta, a.eps, a.worker, a.sign, nullptr, a.next_state, a.reward, a.P, chain, threadIdx.x, phi,
+    rn_phi_and_shaped(a.cfg, a.theta, a.eps, a.worker, a.sign, nullptr, a.next_state, a.reward, a.P, chain, a.cfg.gamma, threadIdx.x, phi,
                       shaped, shaped_out + chain * N * A, phi_out ? phi_out + chain * N : nullptr, shaped + N * A);
 }
 
@@ -160,7 +162,10 @@ __global__ __launch_bounds__(64) void ql_rn_inner_kernel(const QlArgs a)
     int *a_buf = reinterpret_cast<int *>(u_buf + draw_cap);          // [draw_cap]
     volatile int *xctl = a_buf + draw_cap;                           // [8] walker -> wave: stop flags, draw counters
 
-    rn_phi_and_shaped(cfg, a.theta, a.eps, a.worker, a.sign, a.shaped_override, a.next_state, a.reward, a.P, chain, lane,
+    // the chain's own alpha / gamma, read once into wave-uniform values (every lane reads the same address)
+    const double alpha_c = a.hp_alpha ? a.hp_alpha[chain] : cfg.alpha;
+    const double gamma_c = a.hp_gamma ? a.hp_gamma[chain] : cfg.gamma;
+    rn_phi_and_shaped(cfg, a.theta, a.eps, a.worker, a.sign, a.shaped_override, a.next_state, a.reward, a.P, chain, gamma_c, lane,
                       phi, shaped, a.out.shaped ? a.out.shaped + chain * N * A : nullptr, nullptr, hbuf);
     for (int i = lane; i < N * A; i += 64) { q[i] = 0.0; if (CB) visits[i] = 0; }   // QL.py:25,31
     __syncthreads();
@@ -316,8 +321,8 @@ __global__ __launch_bounds__(64) void ql_rn_inner_kernel(const QlArgs a)
                         visits[s * A + ac] += 1;
                         rr += cfg.beta / (__builtin_sqrt((double)visits[s * A + ac]) + 1e-9);
                     }
-                    const double delta = rr + cfg.gamma * boot * (dn ? 0.0 : 1.0) - q[s * A + ac];
-                    q[s * A + ac] += cfg.alpha * delta;
+                    const double delta = rr + gamma_c * boot * (dn ? 0.0 : 1.0) - q[s * A + ac];
+                    q[s * A + ac] += alpha_c * delta;
                 }
                 ++learn_steps;
             }
@@ -385,10 +390,12 @@ static int64_t ql_rn_params(const lenv_ql_cfg *cfg)
     return (int64_t)cfg->n_states * H + H + (int64_t)(cfg->rn_layers - 1) * (H * H + H) + H + 1;
 }
 
-extern "C" int lenv_ql_rn_inner_loop(const lenv_ql_cfg *cfg, const float *theta, const float *eps, const int32_t *worker,
-                                     const float *sign, const float *shaped_override, const int32_t *next_state,
-                                     const double *reward, const uint8_t *done, const uint64_t *rng_keys,
-                                     const lenv_tapes *tapes, int64_t chains, const lenv_ql_out *out, void *stream)
+// alpha / gamma [chains] (device, each may be NULL = cfg's value for every chain): a population of agents with their own hyper-parameters
+// (experiments/GTNC_evaluate_gridworld_transfer_vary_hp.py:92-123) as the chains of one launch
+extern "C" int lenv_ql_rn_inner_loop_hp(const lenv_ql_cfg *cfg, const double *alpha, const double *gamma, const float *theta, const float *eps,
+                                        const int32_t *worker, const float *sign, const float *shaped_override, const int32_t *next_state,
+                                        const double *reward, const uint8_t *done, const uint64_t *rng_keys,
+                                        const lenv_tapes *tapes, int64_t chains, const lenv_ql_out *out, void *stream)
 {
     if (!cfg || !next_state || !reward || !done || !out || !out->score || chains < 0) return LENV_ERR_INVALID;
     if (!theta && !shaped_override) return LENV_ERR_INVALID;
@@ -406,6 +413,7 @@ extern "C" int lenv_ql_rn_inner_loop(const lenv_ql_cfg *cfg, const float *theta,
     a.cfg = *cfg;
     a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.shaped_override = shaped_override;
     a.next_state = next_state; a.reward = reward; a.done = done; a.rng_keys = rng_keys;
+    a.hp_alpha = alpha; a.hp_gamma = gamma;
     if (tapes) a.tapes = *tapes; else a.tapes = lenv_tapes{};
     a.out = *out;
     a.P = ql_rn_params(cfg);
@@ -429,6 +437,15 @@ extern "C" int lenv_ql_rn_inner_loop(const lenv_ql_cfg *cfg, const float *theta,
     return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
 }
 
+extern "C" int lenv_ql_rn_inner_loop(const lenv_ql_cfg *cfg, const float *theta, const float *eps, const int32_t *worker,
+                                     const float *sign, const float *shaped_override, const int32_t *next_state,
+                                     const double *reward, const uint8_t *done, const uint64_t *rng_keys,
+                                     const lenv_tapes *tapes, int64_t chains, const lenv_ql_out *out, void *stream)
+{
+    return lenv_ql_rn_inner_loop_hp(cfg, nullptr, nullptr, theta, eps, worker, sign, shaped_override, next_state, reward, done, rng_keys, tapes,
+                                    chains, out, stream);
+}
+
 
 // RewardEnv shaping for a population (the `rn_shape_population` entry of SURVEY.md §8(b)): phi_out [chains,N] (optional),
 // shaped_out [chains,N*A].
@@ -446,6 +463,7 @@ extern "C" int lenv_rn_shape_population(const lenv_ql_cfg *cfg, const float *the
     a.cfg = *cfg;
     a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.shaped_override = nullptr;
     a.next_state = next_state; a.reward = reward; a.done = nullptr; a.rng_keys = nullptr;
+    a.hp_alpha = a.hp_gamma = nullptr;
     a.tapes = lenv_tapes{}; a.out = lenv_ql_out{};
     a.P = ql_rn_params(cfg);
     const size_t lds_bytes = sizeof(float) * ((size_t)cfg->n_states * (1 + cfg->n_actions)) + 16 + (cfg->rn_layers > 1 ? sizeof(float) * 2 * 64 * (size_t)cfg->rn_hidden : 0);

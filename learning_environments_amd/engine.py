@@ -377,16 +377,30 @@ class QlInnerLoop(_InnerLoopBase):
         if want_episode_stats:
             self.q_table = torch.zeros((self.chains, N * A), dtype=torch.float64, device=self.dev)
             self.shaped = torch.zeros((self.chains, N * A), dtype=torch.float32, device=self.dev)
+        self.hp_alpha = self.hp_gamma = None
         self._alloc_outputs(None, want_episode_stats, False, trace_cap)
+
+    def set_hp(self, alpha=None, gamma=None):
+        """The chains' own alpha / gamma (host sequences of length `chains`; None: cfg's value for every chain): run() then goes through
+        lenv_ql_rn_inner_loop_hp.  gamma also enters the chain's shaped-reward table (BaseAgent.train hands it to the env)."""
+        for name, vals in (("hp_alpha", alpha), ("hp_gamma", gamma)):
+            if vals is not None:
+                if len(vals) != self.chains:
+                    raise ValueError("set_hp: need %d values per hyper-parameter" % self.chains)
+                vals = torch.tensor([float(v) for v in vals], dtype=torch.float64).to(self.dev)
+            setattr(self, name, vals)
 
     def run(self, theta, eps, worker, sign, rng_keys=None, tapes=None, shaped_override=None):
         self._check_run(theta, eps, worker, sign, rng_keys)
         _chk(shaped_override, torch.float32, "shaped_override")
         if theta is not None and theta.numel() != self.p_theta and self.cfg.reward_env_type != 0:
             raise ValueError("theta must hold %d reward-net parameters" % self.p_theta)
-        rc = _lib.lib().lenv_ql_rn_inner_loop(C.byref(self.cfg), _ptr(theta), _ptr(eps), _ptr(worker), _ptr(sign),
-                                              _ptr(shaped_override), _ptr(self.next_state), _ptr(self.reward), _ptr(self.done),
-                                              _ptr(rng_keys), self._tapes_arg(tapes), self.chains, C.byref(self.out), _stream())
+        args = (_ptr(theta), _ptr(eps), _ptr(worker), _ptr(sign), _ptr(shaped_override), _ptr(self.next_state), _ptr(self.reward),
+                _ptr(self.done), _ptr(rng_keys), self._tapes_arg(tapes), self.chains, C.byref(self.out), _stream())
+        if self.hp_alpha is None and self.hp_gamma is None:
+            rc = _lib.lib().lenv_ql_rn_inner_loop(C.byref(self.cfg), *args)
+        else:
+            rc = _lib.lib().lenv_ql_rn_inner_loop_hp(C.byref(self.cfg), _ptr(self.hp_alpha), _ptr(self.hp_gamma), *args)
         _lib.check(rc, "lenv_ql_rn_inner_loop")
         return self.score
 

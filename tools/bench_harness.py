@@ -4,7 +4,12 @@ Models: CartPole SEs of default_config_cartpole.yaml's shape whose reward net sa
 the virtual early-out after 20-30 episodes).  usage: python tools/bench_harness.py [model_num] [agents_num] [agent] [mode]
 agent = ppo_transfer: the reward-net transfer experiment (experiments/GTNC_evaluate_cmc_transfer_algo.py: 10 models x 10 PPO agents per mode) at the
 script's PPO settings on a reduced episode budget ([mode] = training episodes per agent, default 40), all models in one launch; models =
-freshly initialised MountainCarContinuous reward nets of default_config_cmc_reward_env.yaml's shape (a stand-in for trained ones)."""
+freshly initialised MountainCarContinuous reward nets of default_config_cmc_reward_env.yaml's shape (a stand-in for trained ones).
+agent = gridworld_transfer: the gridworld reward-net transfer experiment (experiments/GTNC_evaluate_gridworld_transfer_vary_hp.py: 10 models x 10 QL
+agents per mode, every agent with its own alpha / gamma) at the script's size (500 episodes), all models in ONE launch of
+lenv_ql_rn_inner_loop_hp ([mode] = the script's mode, default 2), and in the same run the same agents as model_num x agents_num single-chain
+launches of lenv_ql_rn_inner_loop, each with its own cfg -- the only way a heterogeneous population runs without the per-chain entry.  Medians
+of 7.  Models = freshly initialised Cliff reward nets with the weight matrices scaled by 1.5 (a stand-in for trained ones)."""
 import json
 import os
 import sys
@@ -55,7 +60,79 @@ def ppo_transfer(model_num, agents_num, episodes):
                       "mfma_f32_frac_of_busy_cus": 6.0 * rows * W * epochs / dt / 1e12 / (bench.MFMA_F32_PEAK_TFLOPS * busy / 256.0)}))
 
 
+def gridworld_transfer(model_num, agents_num, mode):
+    import copy
+    import numpy as np
+    from learning_environments_amd import _lib, configs, engine
+    from learning_environments_amd.envs.env_factory import EnvFactory
+    from learning_environments_amd.experiments import transfer_gridworld as tg
+    base = configs.cliff_reward_env_ql()
+    base["envs"]["Cliff"].update(solved_reward=tg.SOLVED_REWARD, reward_env_type=int(mode) if int(mode) > 0 else 2)
+    real_env = EnvFactory(copy.deepcopy(base)).generate_real_env()
+    envs = []
+    for m in range(model_num):
+        torch.manual_seed(100 + m)
+        env = EnvFactory(copy.deepcopy(base)).generate_reward_env()
+        with torch.no_grad():
+            for p in env.env.reward_net.parameters():
+                if p.dim() == 2:
+                    p.mul_(1.5)
+        envs.append(env if int(mode) > 0 else real_env)
+    tg.train_test_agents_models(mode, envs[:1], real_env, copy.deepcopy(base), agents_num=1, settings=dict(train_episodes=5))       # warm-up
+    torch.cuda.synchronize()
+    reps = 7
+
+    def median(fn):
+        times = []
+        for rep in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.time()
+            fn(rep)
+            torch.cuda.synchronize()
+            times.append(time.time() - t0)
+        return sorted(times)[reps // 2], times
+
+    # (1) the whole call: settings, draws, set_hp, one launch, the lists
+    res = {}
+
+    def call(rep):
+        res["out"], res["launch"] = tg.train_test_agents_models(mode, envs, real_env, copy.deepcopy(base), agents_num=agents_num, seed=0, details=True)
+    t_call, all_call = median(call)
+    launch = res["launch"]
+    inner, chains = launch["inner"], launch["inner"].chains
+    keys_t = torch.from_numpy(launch["keys"].view(np.int64)).to(inner.dev)
+    # (2) its launch alone
+    t_launch, all_launch = median(lambda rep: inner.run(launch["theta"], launch["eps"], launch["worker"], launch["sign"], rng_keys=keys_t))
+    st = inner.stats.cpu().numpy()
+    fused = (inner.episode_test_mean.cpu().numpy().copy(), inner.episode_len.cpu().numpy().copy(), inner.q_table.cpu().numpy().copy())
+    # (3) the same agents as single-chain launches of the plain entry, each with its own cfg (buffers allocated before the clock starts)
+    singles = []
+    for c in range(chains):
+        cfg = _lib.QlCfg.from_buffer_copy(inner.cfg)
+        cfg.alpha, cfg.gamma = launch["hp"][c]["alpha"], launch["hp"][c]["gamma"]
+        il = engine.QlInnerLoop(cfg, 1, real_env.env.tables)
+        w = int(launch["worker"][c])
+        theta = (launch["eps"][w] if float(launch["sign"][c]) != 0.0 else launch["theta"]).contiguous()
+        singles.append((il, theta, keys_t[c:c + 1].contiguous()))
+
+    def run_singles(rep):
+        for il, theta, k in singles:
+            il.run(theta, None, None, None, rng_keys=k)
+    t_single, all_single = median(run_singles)
+    for c, (il, _, _) in enumerate(singles):                  # the same agents: the same runs
+        assert np.array_equal(il.episode_test_mean[0].cpu().numpy(), fused[0][c], equal_nan=True) and np.array_equal(il.episode_len[0].cpu().numpy(), fused[1][c])
+        assert np.array_equal(il.q_table[0].cpu().numpy(), fused[2][c])
+    print(json.dumps({"experiment": "gridworld transfer (vary_hp script), mode %s" % mode, "models": model_num, "agents": chains,
+                      "train_episodes": int(inner.cfg.train_episodes), "train_steps": int(st[:, 1].sum()), "test_steps": int(st[:, 3].sum()),
+                      "seconds_call_median_of_7": t_call, "seconds_launch_median_of_7": t_launch,
+                      "seconds_single_chain_launches_median_of_7": t_single, "agents_per_s_call": chains / t_call,
+                      "agents_per_s_launch": chains / t_launch, "agents_per_s_single_chain_launches": chains / t_single,
+                      "single_over_fused_launch": t_single / t_launch, "all_call": all_call, "all_launch": all_launch, "all_single": all_single}))
+
+
 def main():
+    if len(sys.argv) > 3 and sys.argv[3] == "gridworld_transfer":
+        return gridworld_transfer(int(sys.argv[1]), int(sys.argv[2]), sys.argv[4] if len(sys.argv) > 4 else "2")
     if len(sys.argv) > 3 and sys.argv[3] == "ppo_transfer":
         return ppo_transfer(int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[4]) if len(sys.argv) > 4 else 40)
     model_num = int(sys.argv[1]) if len(sys.argv) > 1 else 40
