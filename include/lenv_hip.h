@@ -494,6 +494,42 @@ int lenv_td3_rn_inner_loop_icm(const lenv_td3_cfg *cfg /*HOST*/, const lenv_chai
                                const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
                                const lenv_td3_tapes *tapes /*HOST*/, int64_t chains, void *workspace, size_t workspace_bytes,
                                const lenv_td3_out *out /*HOST*/, void *stream);
+/* The same inner loop in EPISODE SEGMENTS (ABI 7, a function only): a launch runs episodes [episode_begin, episode_end) of every chain and
+ * leaves a resume record per chain; the next launch (episode_begin = the last episode_end) goes on from it.  Always the generic GEMM-queue
+ * kernel, one workgroup per chain (never the wave-chain / shape-specialised / product-queue-free instantiations).  For every split
+ * 0 = e0 < e1 < .. < ek = train_episodes the k launches leave every lenv_td3_out array, icm_final and the traces bit-identical to one
+ * lenv_td3_rn_inner_loop_icm / _hp launch on that kernel.
+ *   episode_begin == 0: the arena is initialised from agent_init / icm_init; the record is written, never read.
+ *   episode_begin  > 0: nothing is initialised; the caller passes the same workspace (untouched in between), out arrays, tapes, hp, icm and
+ *     theta / eps / worker / sign as to the earlier segments.  A chain whose record does not say "next episode == episode_begin" writes
+ *     status -10 and does nothing else.
+ * The closing part (final agent.test, score, final_returns, the NaN / time-out padding of unrun episodes, icm_final) runs once per chain,
+ * in the segment in which the chain ends (train_episodes reached, early out, step_budget time-out); the chain is then `finished` and later
+ * segments leave it and its outputs untouched.  A segment that ends with the chain unfinished writes the cumulative stats and final_params
+ * (a checkpoint) and nothing else of the closing part.
+ * Refused with LENV_ERR_INVALID: !(0 <= episode_begin < episode_end <= cfg->train_episodes), resume == NULL, and whatever
+ * lenv_td3_rn_inner_loop_icm refuses.  workspace_bytes: lenv_td3_rn_workspace_bytes.
+ * The record (opaque to callers), int64 words per chain:
+ *    0 next episode to run            1 finished (0 / 1)               2 status so far (0 ok, else the minimum of the chain's codes)
+ *    3 timed_out_at (-1: no time-out) 4 n_rand (random actions drawn)  5 n_actn (train-action noise rows drawn)
+ *    6 n_testn (test noise rows)      7 n_test_ep (test episodes run)  8 learn_it (TD3.learn calls)
+ *    9 train_steps (agent steps; ring position = train_steps % capacity)   10 test_steps   11 episodes_run
+ *   12 trace cursor: rows of the step trace written, before the trace_cap clamp (one row per agent step: always equal to word 9)
+ *   13..16 bit patterns of the doubles beta1^t, beta2^t of the critic optimizer, then of the actor optimizer
+ *   17..18 bit patterns of the ICM optimizer's beta1^t, beta2^t (1.0 without an ICM)      19..31 reserved (0)
+ * The early-out meter (the per-episode test means) lives in the arena.
+ * Status of a FAILING chain: a thread keeps the code of its latest failure and the launch reports the minimum over the threads; a series of
+ * segments folds that minimum at every boundary and starts every thread of the next segment from it, so after different kinds of failure in
+ * different segments a series can report a smaller code than the single launch would (-7 then -3: -7 instead of -3).  Both are non-zero.
+ * Status -10 here means "the record names another episode"; on the team launches of the other entry points the same value means that a
+ * team member gave up waiting (lenv_ddqn_cfg::team_size): a caller that retries -10 with team_size 1 must not do so after a segment launch. */
+#define LENV_TD3_RESUME_WORDS 32
+int lenv_td3_rn_inner_loop_segment(const lenv_td3_cfg *cfg /*HOST*/, const lenv_chain_hp *hp /*HOST, may be NULL*/,
+                                   const lenv_icm_io *icm /*HOST, NULL iff !cfg->icm_enabled*/, const float *theta, const float *eps,
+                                   const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                                   const lenv_td3_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace, size_t workspace_bytes,
+                                   const lenv_td3_out *out /*HOST*/, int32_t episode_begin, int32_t episode_end,
+                                   int64_t *resume /*DEVICE [chains, LENV_TD3_RESUME_WORDS]*/, void *stream);
 /* Workgroups per chain a production launch (counter RNG, no trace, no hp, no ICM) of this cfg will use: the wave-chain kernel of the
  * published HalfCheetah RewardEnv + TD3 shape runs a chain on a TEAM of 6, 3 or 2 workgroups when 8 * ceil(chains / 8) * G of them
  * are resident at once (one per CU), with test_mode 0 and 1 alike, and so do its other shapes; every other launch: 1.  cfg->team_size

@@ -65,6 +65,9 @@ struct Td3Args {
     int64_t a_icm[IB_COUNT];
     int64_t a_params, a_targets, a_m, a_v, a_grad, a_replay, a_xc, a_xn, a_xa, a_hc1[T3_MAXL], a_hc2[T3_MAXL], a_ha[T3_MAXL],
         a_ht[T3_MAXL], a_d[2], a_dx, a_act, a_th, a_dz, a_meter, a_xh[3][T3_MAXL], a_rstd;      // a_xh / a_rstd: LayerNorm rows of critic_1 / critic_2 / actor passes
+    // lenv_td3_rn_inner_loop_segment (the SEG instantiations): episodes [ep_begin, ep_end) of every chain, resume records [chains, LENV_TD3_RESUME_WORDS];
+    // every other entry point: 0, train_episodes, nullptr.  (Behind everything else: the other instantiations read their arguments where they were.)
+    int ep_begin, ep_end; int64_t *resume;
 };
 
 // Diagnostic build only (-DLENV_PHASE_TIMING): per-phase shader-clock totals of chain 0, never in the shipped library.
@@ -564,10 +567,29 @@ __device__ __forceinline__ float se_chain128(const gfloat *wt, int stride_rt, co
 // with the epilogues' bias / activation / derivative arithmetic, so the bits are those of the GEMM-queue path and of the oracle.  Its own
 // instantiations: as a run-time branch next to the queued learn step the extra live state pushed the Pendulum instantiation into SGPR spills, where
 // the ROCm 7.2 backend emits an illegal VALU compare on the LDS aperture register.
-template <bool ICM, int ENV, int SHAPE = 0, bool DIRECT = false>
+// The resume record of a chain after a segment (include/lenv_hip.h documents the words): thread 0, behind the barrier that follows the threads'
+// atomicMin into the folded status
+__device__ __forceinline__ void td3_write_record(int64_t *rec, int next_episode, int finished, int status, int timed_out_at, int64_t n_rand,
+                                                 int64_t n_actn, int64_t n_testn, int64_t n_test_ep, int64_t learn_it, int train_steps,
+                                                 int test_steps, int episodes_run, const double *pows, const double *icm_pows)
+{
+    rec[0] = next_episode; rec[1] = finished; rec[2] = status; rec[3] = timed_out_at;
+    rec[4] = n_rand; rec[5] = n_actn; rec[6] = n_testn; rec[7] = n_test_ep; rec[8] = learn_it;
+    rec[9] = train_steps; rec[10] = test_steps; rec[11] = episodes_run; rec[12] = train_steps;
+    for (int i = 0; i < 4; ++i) rec[13 + i] = __double_as_longlong(pows[i]);
+    for (int i = 0; i < 2; ++i) rec[17 + i] = __double_as_longlong(icm_pows[i]);
+    for (int w = 19; w < LENV_TD3_RESUME_WORDS; ++w) rec[w] = 0;
+}
+
+// SEG (lenv_td3_rn_inner_loop_segment, include/lenv_hip.h) = the queued kernel over the episodes [a.ep_begin, a.ep_end): everything the loop carries
+// from episode to episode outside the arena -- the counters, the Adam bias-correction powers, the status -- is read from / written to the chain's
+// resume record; the reward net (LDS) is staged by every segment, the agent / ICM only by the first; the closing part runs in the segment in
+// which the chain ends.  Its own instantiations: the code of the others is what it was.
+template <bool ICM, int ENV, int SHAPE = 0, bool DIRECT = false, bool SEG = false>
 __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
 {
     static_assert(!DIRECT || (SHAPE == 0 && !ICM && DNT == 512), "the DIRECT instantiations: generic shapes, no ICM, two 256-thread halves");
+    static_assert(!SEG || (SHAPE == 0 && !DIRECT), "the SEG instantiations: the generic GEMM-queue kernel");
     using EnvT = ContEnv<ENV>;
     constexpr bool FIXED = SHAPE != 0;
     constexpr Td3Shape kTd3Shape = kTd3Shapes[SHAPE];
@@ -578,7 +600,16 @@ __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
     const int64_t chain = blockIdx.x;
     // the chain's status word starts at 0 (ok); written here rather than by a memset node in front of the launch (a captured
     // generation replayed under rocprofv3 did not run the memset)
-    if (threadIdx.x == 0 && a.out.status) a.out.status[chain] = 0;
+    int64_t *rec = nullptr;
+    const bool fresh = !SEG || a.ep_begin == 0;          // the arena is initialised by this launch
+    if constexpr (SEG) {
+        rec = a.resume + chain * LENV_TD3_RESUME_WORDS;
+        if (!fresh) {                                    // uniform per chain
+            if (rec[1] == 1) return;                     // finished in an earlier segment: the chain and its outputs stay as they are
+            if (rec[0] != (int64_t)a.ep_begin) { if (tid == 0 && a.out.status) a.out.status[chain] = -10; return; }
+        }
+    }
+    if (threadIdx.x == 0 && a.out.status) { if (fresh) a.out.status[chain] = 0; }
     constexpr int S = EnvT::S, A = EnvT::A, SA = S + A, SD = EnvT::SD;   // observation / action dims, fp64 words of the env's own state
     const bool vary = FIXED ? false : a.hp_batch != nullptr;
     const int H = FIXED ? kTd3Shape.H : (vary ? a.hp_hidden[chain] : cfg.hidden), L = FIXED ? kTd3Shape.L : (vary ? a.hp_layers[chain] : cfg.layers);
@@ -590,7 +621,11 @@ __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
     const bool virtual_env = FIXED ? kTd3Shape.virtual_env != 0 : cfg.virtual_env != 0;
     const int info_dim = cfg.info_dim, policy_delay = FIXED ? kTd3Shape.policy_delay : cfg.policy_delay;
     if (vary && (H < 1 || H > cfg.hidden || L < 1 || L > cfg.layers || B < 1 || B > Bm)) {   // uniform per chain
-        if (tid == 0) { if (a.out.status) a.out.status[chain] = -8; a.out.score[chain] = 0.0; }
+        if (tid == 0) {
+            if (a.out.status) a.out.status[chain] = -8;
+            a.out.score[chain] = 0.0;
+            if constexpr (SEG) { for (int w = 0; w < LENV_TD3_RESUME_WORDS; ++w) rec[w] = 0; rec[1] = 1; rec[2] = -8; rec[3] = -1; }
+        }
         return;
     }
     MlpOff mo_actor, mo_critic;
@@ -629,6 +664,9 @@ __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
     float *newrow = action + 8;                           // [56] replay row [s | a | s' | r | done] + scratch + info[4] at 2S+A+4
     volatile float *ctrl = misc;
     volatile int *ictrl = reinterpret_cast<volatile int *>(misc + 32);
+    // the control words in use: ctrl[10..15] (Adam, reward net, LayerNorm rows), ctrl[20..21] (ICM's Adam), ictrl[3..4] = misc[35..36];
+    // misc[MISC_STATUS_FOLD] (an int): the SEG instantiations' fold of the threads' status codes.  A new control word takes a free index below it.
+    constexpr int MISC_STATUS_FOLD = 48;
 
     float *arena = a.arena + chain * a.arena_stride;
     float *params = arena + a.a_params, *targets = arena + a.a_targets, *adam_m = arena + a.a_m, *adam_v = arena + a.a_v;
@@ -667,7 +705,7 @@ __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
             }
         }
     }
-    for (int p = tid; p < P; p += DNT) {
+    if (fresh) for (int p = tid; p < P; p += DNT) {
         const float w = a.agent_init[chain * a.P + p];
         params[p] = w; targets[p] = w; adam_m[p] = 0.0f; adam_v[p] = 0.0f;
     }
@@ -677,7 +715,7 @@ __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
     if constexpr (ICM) {
         icm_build(icm, S, A, cfg.icm_feature_dim, cfg.icm_hidden, /*discrete=*/false);
         float *ip = arena + a.a_icm[IB_P], *im = arena + a.a_icm[IB_M], *iv = arena + a.a_icm[IB_V];
-        for (int p = tid; p < icm.P; p += DNT) { ip[p] = a.icm_init[chain * a.P_icm + p]; im[p] = 0.0f; iv[p] = 0.0f; }
+        if (fresh) for (int p = tid; p < icm.P; p += DNT) { ip[p] = a.icm_init[chain * a.P_icm + p]; im[p] = 0.0f; iv[p] = 0.0f; }
     }
     if (tid < 64) misc[tid] = 0.0f;
     __syncthreads();
@@ -691,6 +729,15 @@ __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
     int train_steps = 0, test_steps = 0, episodes_run = 0;
     double pows[4] = { 1.0, 1.0, 1.0, 1.0 };
     const int rb_cap = (int)a.rb_cap;
+    if constexpr (SEG) {
+        if (!fresh) {                                    // every thread its copy, like the counters of a single launch
+            status = (int)rec[2];
+            n_rand = rec[4]; n_actn = rec[5]; n_testn = rec[6]; n_test_ep = rec[7]; learn_it = rec[8];
+            train_steps = (int)rec[9]; test_steps = (int)rec[10]; episodes_run = (int)rec[11];
+            for (int i = 0; i < 4; ++i) pows[i] = __longlong_as_double(rec[13 + i]);
+            for (int i = 0; i < 2; ++i) icm_pows[i] = __longlong_as_double(rec[17 + i]);
+        }
+    }
 
     // ---- generic MLP forward over I <= 256 rows (row stride ldx); hidden activations to hid[l][I][H].  The layer products
     // are QUEUED (gq); the caller runs the queue.  final_tanh: out = tanh(net)*max_action (Actor_TD3.forward) with tanh
@@ -1049,7 +1096,9 @@ __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
     const bool budgeted = cfg.step_budget > 0;
     int timed_out_at = -1;
     const bool no_test_env = FIXED ? false : cfg.test_mode == 1;      // BaseAgent.train(env, test_env=None): lenv_ddqn_cfg::test_mode
-    for (int episode = 0; episode < cfg.train_episodes; ++episode) {
+    bool early_out = false;                               // SEG: the loop ended at the early out
+    const int ep_first = SEG ? a.ep_begin : 0, ep_last = SEG ? a.ep_end : cfg.train_episodes;
+    for (int episode = ep_first; episode < ep_last; ++episode) {
         if (budgeted && (int64_t)train_steps + test_steps > cfg.step_budget) { timed_out_at = episode; break; }   // uniform
         const bool learning = episode >= cfg.init_episodes;
         // env.reset(): RewardEnv.reset -> real_env.reset() (reward_env.py:141-143)
@@ -1337,7 +1386,25 @@ __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
         __syncthreads();
         const int brk = ictrl[3];
         __syncthreads();
-        if (brk) break;
+        if (brk) { if constexpr (SEG) early_out = true; break; }
+    }
+    if constexpr (SEG) {
+        if (!early_out && timed_out_at < 0 && a.ep_end < cfg.train_episodes) {
+            // the chain goes on in the next segment: a checkpoint (cumulative stats, the parameters so far) and the record
+            int *st_fold = reinterpret_cast<int *>(misc + MISC_STATUS_FOLD);     // the minimum of the threads' status codes (0 after the clear of misc)
+            if (status != 0) { atomicMin(st_fold, status); if (a.out.status) atomicMin(&a.out.status[chain], status); }
+            if (a.out.final_params) for (int p = tid; p < P; p += DNT) a.out.final_params[chain * a.P + p] = params[p];
+            __syncthreads();
+            if (tid == 0) {
+                if (a.out.stats) {
+                    a.out.stats[chain * 4 + 0] = episodes_run; a.out.stats[chain * 4 + 1] = train_steps;
+                    a.out.stats[chain * 4 + 2] = learn_it; a.out.stats[chain * 4 + 3] = test_steps;
+                }
+                td3_write_record(rec, a.ep_end, 0, *st_fold, timed_out_at, n_rand, n_actn, n_testn, n_test_ep, learn_it, train_steps, test_steps,
+                                 episodes_run, pows, icm_pows);
+            }
+            return;
+        }
     }
     PT_MARK(10);
     const int64_t remaining = cfg.step_budget - ((int64_t)train_steps + test_steps);     // time_remaining - elapsed
@@ -1394,6 +1461,13 @@ __global__ __launch_bounds__(DNT) void td3_rn_inner_kernel(const Td3Args a)
         if (a.icm_final) for (int p = tid; p < icm.P; p += DNT) a.icm_final[chain * a.P_icm + p] = arena[a.a_icm[IB_P] + p];
     }
     if (a.out.status && status != 0) atomicMin(&a.out.status[chain], status);
+    if constexpr (SEG) {
+        int *st_fold = reinterpret_cast<int *>(misc + MISC_STATUS_FOLD);
+        if (status != 0) atomicMin(st_fold, status);
+        __syncthreads();
+        if (tid == 0) td3_write_record(rec, a.ep_end, 1, *st_fold, timed_out_at, n_rand, n_actn, n_testn, n_test_ep, learn_it, train_steps, test_steps,
+                                       episodes_run, pows, icm_pows);
+    }
 }
 
 // Fresh TD3 agents (actor | critic_1 | critic_2, TD3.py:31-39) for chains with their own network shapes: nn.Linear's default
@@ -1576,10 +1650,12 @@ extern "C" int lenv_td3_rn_inner_loop_hp(const lenv_td3_cfg *cfg, const lenv_cha
                                       workspace_bytes, out, stream);
 }
 
-extern "C" int lenv_td3_rn_inner_loop_icm(const lenv_td3_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta,
-                                          const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
-                                          const uint64_t *rng_keys, const lenv_td3_tapes *tapes, int64_t chains, void *workspace,
-                                          size_t workspace_bytes, const lenv_td3_out *out, void *stream)
+// the launch behind lenv_td3_rn_inner_loop_icm (segment false: one launch from the first episode to the final test, resume unused) and
+// lenv_td3_rn_inner_loop_segment (segment true: episodes [ep_begin, ep_end) on the SEG instantiations of the queued kernel)
+static int td3_launch(const lenv_td3_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta, const float *eps,
+                      const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys, const lenv_td3_tapes *tapes,
+                      int64_t chains, void *workspace, size_t workspace_bytes, const lenv_td3_out *out, bool segment, int32_t ep_begin,
+                      int32_t ep_end, int64_t *resume, void *stream)
 {
     if (hp && (!hp->lr || !hp->batch_size || !hp->q_hidden || !hp->q_layers)) return LENV_ERR_INVALID;
     if (cfg && cfg->icm_enabled && (!icm || !icm->icm_init)) return LENV_ERR_INVALID;
@@ -1588,6 +1664,7 @@ extern "C" int lenv_td3_rn_inner_loop_icm(const lenv_td3_cfg *cfg, const lenv_ch
     if (eps && (!worker || !sign)) return LENV_ERR_INVALID;
     if (cfg->rng_mode == LENV_RNG_TAPE && !tapes) return LENV_ERR_INVALID;
     if (cfg->rng_mode == LENV_RNG_COUNTER && !rng_keys) return LENV_ERR_INVALID;
+    if (segment && (!resume || ep_begin < 0 || ep_begin >= ep_end || ep_end > cfg->train_episodes)) return LENV_ERR_INVALID;
     if (chains == 0) return LENV_OK;
     Td3Args a;
     size_t lds_bytes;
@@ -1595,6 +1672,7 @@ extern "C" int lenv_td3_rn_inner_loop_icm(const lenv_td3_cfg *cfg, const lenv_ch
     if (rc != LENV_OK) return rc;
     if (workspace_bytes < (size_t)chains * a.arena_stride * sizeof(float)) return LENV_ERR_WORKSPACE;
     a.cfg = *cfg;
+    a.ep_begin = segment ? ep_begin : 0; a.ep_end = segment ? ep_end : cfg->train_episodes; a.resume = segment ? resume : nullptr;
     a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.agent_init = agent_init; a.rng_keys = rng_keys;
     if (tapes) a.tapes = *tapes; else a.tapes = lenv_td3_tapes{};
     a.arena = static_cast<float *>(workspace);
@@ -1609,13 +1687,17 @@ extern "C" int lenv_td3_rn_inner_loop_icm(const lenv_td3_cfg *cfg, const lenv_ch
     {
         const int S = cfg->state_dim, A = cfg->action_dim, H = cfg->hidden, B = cfg->batch_size;
         const int64_t need = H <= T3_DIRECT_H && B <= T3_DIRECT_B ? t3d_layout(S, A, H, B).total : INT64_MAX;      // activation matrix + rows + two staged nets + the context record
-        direct = !cfg->icm_enabled && !cfg->use_layer_norm && cfg->layers == 1 && H <= T3_DIRECT_H && B <= T3_DIRECT_B && !(cfg->kernel_variant & LENV_VARIANT_NO_DIRECT) &&
+        direct = !segment && !cfg->icm_enabled && !cfg->use_layer_norm && cfg->layers == 1 && H <= T3_DIRECT_H && B <= T3_DIRECT_B && !(cfg->kernel_variant & LENV_VARIANT_NO_DIRECT) &&
                  need <= (int64_t)(GemmShape<T3_MAXI>::PS_FLOATS + GemmShape<T3_MAXI>::QS_FLOATS);
     }
     if (cfg->env_id == LENV_ENV_PENDULUM) kern = cfg->icm_enabled ? td3_rn_inner_kernel<true, LENV_ENV_PENDULUM> : (direct ? td3_rn_inner_kernel<false, LENV_ENV_PENDULUM, 0, true> : td3_rn_inner_kernel<false, LENV_ENV_PENDULUM>);
     else if (cfg->env_id == LENV_ENV_CMC) kern = cfg->icm_enabled ? td3_rn_inner_kernel<true, LENV_ENV_CMC> : (direct ? td3_rn_inner_kernel<false, LENV_ENV_CMC, 0, true> : td3_rn_inner_kernel<false, LENV_ENV_CMC>);
     else kern = cfg->icm_enabled ? td3_rn_inner_kernel<true, LENV_ENV_CHEETAH_STANDIN> : (direct ? td3_rn_inner_kernel<false, LENV_ENV_CHEETAH_STANDIN, 0, true> : td3_rn_inner_kernel<false, LENV_ENV_CHEETAH_STANDIN>);
-    {
+    if (segment) {
+        if (cfg->env_id == LENV_ENV_PENDULUM) kern = cfg->icm_enabled ? td3_rn_inner_kernel<true, LENV_ENV_PENDULUM, 0, false, true> : td3_rn_inner_kernel<false, LENV_ENV_PENDULUM, 0, false, true>;
+        else if (cfg->env_id == LENV_ENV_CMC) kern = cfg->icm_enabled ? td3_rn_inner_kernel<true, LENV_ENV_CMC, 0, false, true> : td3_rn_inner_kernel<false, LENV_ENV_CMC, 0, false, true>;
+        else kern = cfg->icm_enabled ? td3_rn_inner_kernel<true, LENV_ENV_CHEETAH_STANDIN, 0, false, true> : td3_rn_inner_kernel<false, LENV_ENV_CHEETAH_STANDIN, 0, false, true>;
+    } else {
         // the published HalfCheetah RewardEnv + TD3 shape in production form takes the shape-specialised instantiation
         const bool off = (cfg->kernel_variant & LENV_VARIANT_GENERIC) != 0;
         auto matches = [&](const Td3Shape &sp) {
@@ -1640,6 +1722,25 @@ extern "C" int lenv_td3_rn_inner_loop_icm(const lenv_td3_cfg *cfg, const lenv_ch
     if (e != hipSuccess) return LENV_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+}
+
+extern "C" int lenv_td3_rn_inner_loop_icm(const lenv_td3_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta,
+                                          const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
+                                          const uint64_t *rng_keys, const lenv_td3_tapes *tapes, int64_t chains, void *workspace,
+                                          size_t workspace_bytes, const lenv_td3_out *out, void *stream)
+{
+    return td3_launch(cfg, hp, icm, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, false, 0, 0,
+                      nullptr, stream);
+}
+
+extern "C" int lenv_td3_rn_inner_loop_segment(const lenv_td3_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta,
+                                              const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
+                                              const uint64_t *rng_keys, const lenv_td3_tapes *tapes, int64_t chains, void *workspace,
+                                              size_t workspace_bytes, const lenv_td3_out *out, int32_t episode_begin, int32_t episode_end,
+                                              int64_t *resume, void *stream)
+{
+    return td3_launch(cfg, hp, icm, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, true,
+                      episode_begin, episode_end, resume, stream);
 }
 
 #ifdef LENV_PHASE_TIMING

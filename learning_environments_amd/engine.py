@@ -452,16 +452,60 @@ class Td3InnerLoop(_InnerLoopBase):
         self._init_vary(vary)
         self._init_icm("lenv_td3_icm_num_params")       # TD3(icm=True): select_agent "td3_icm" / "td3_icm_vary"
         self.p_theta = cfg.state_dim * cfg.rn_hidden + 2 * cfg.rn_hidden + 1
+        self.resume = None                              # the segment launches' records [chains, TD3_RESUME_WORDS], allocated by the first
         self._alloc_outputs(_lib.lib().lenv_td3_rn_workspace_bytes(C.byref(cfg), self.chains), want_episode_stats, want_final_params,
                             trace_cap)
 
-    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None):
+    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None, episodes_per_launch=None, on_segment=None):
+        """episodes_per_launch None: one launch from the first episode to the final test (asynchronous).  An integer: the same inner loop
+        as a series of segment launches of that many episodes each (lenv_td3_rn_inner_loop_segment, always the generic kernel; same bits
+        for every split).  After each segment the chains' `finished` words and statuses come to the host (one small copy, the only
+        synchronisation), on_segment(episodes_done, finished_count) is called if given, then -- after the callback, so that it sees the segment
+        in which a chain failed -- a bad status raises as check_status does, and the series stops as soon as every chain is finished.  A cfg
+        without training episodes has no segment to run: ValueError (the single launch runs its closing test)."""
         if agent_init is None and self.vary:
             agent_init = self.agent_init
-        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
-        rc = _lib.lib().lenv_td3_rn_inner_loop_icm(C.byref(self.cfg), self._hp_arg(), self._icm_arg(), *args)
-        _lib.check(rc, "lenv_td3_rn_inner_loop")
+        if episodes_per_launch is None:
+            args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+            rc = _lib.lib().lenv_td3_rn_inner_loop_icm(C.byref(self.cfg), self._hp_arg(), self._icm_arg(), *args)
+            _lib.check(rc, "lenv_td3_rn_inner_loop")
+            return self.score
+        step = int(episodes_per_launch)
+        if step < 1:
+            raise ValueError("episodes_per_launch must be at least 1")
+        E = self.cfg.train_episodes
+        if E < 1:
+            raise ValueError("episodes_per_launch needs a cfg with at least one training episode")
+        for begin in range(0, E, step):
+            end = min(E, begin + step)
+            self.run_segment(theta, eps, worker, sign, agent_init, begin, end, rng_keys=rng_keys, tapes=tapes)
+            finished, st = self.segment_state()
+            if on_segment is not None:
+                on_segment(end, int(finished.sum()))
+            if int(st.min()) != 0:
+                raise _lib.LenvError("inner loop reported status %s" % st.tolist())
+            if int(finished.min()) == 1:
+                break
         return self.score
+
+    def run_segment(self, theta, eps, worker, sign, agent_init, episode_begin, episode_end, rng_keys=None, tapes=None):
+        """Enqueue episodes [episode_begin, episode_end) of every chain (asynchronous).  episode_begin 0 starts afresh; a later segment goes
+        on from self.resume and needs the same arguments and an untouched workspace."""
+        if agent_init is None and self.vary:
+            agent_init = self.agent_init
+        if self.resume is None:
+            self.resume = torch.zeros((self.chains, _lib.TD3_RESUME_WORDS), dtype=torch.int64, device=self.dev)
+        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+        rc = _lib.lib().lenv_td3_rn_inner_loop_segment(C.byref(self.cfg), self._hp_arg(), self._icm_arg(), *args[:-1], int(episode_begin),
+                                                       int(episode_end), _ptr(self.resume), args[-1])
+        _lib.check(rc, "lenv_td3_rn_inner_loop_segment")
+        return self.score
+
+    def segment_state(self):
+        """(finished [chains], status [chains]) on the host after the segments enqueued so far (synchronises): the record's finished word and
+        the smaller of the record's status and the status output (a refused continuation, -10, is reported there alone)."""
+        both = torch.stack((self.resume[:, 1], torch.minimum(self.resume[:, 2], self.status.to(torch.int64)))).cpu()
+        return both[0], both[1]
 
 
 class Td3DiscreteInnerLoop(_InnerLoopBase):

@@ -100,6 +100,79 @@ def run_test_mode1_ab(name, cfg, gens=7):
     return out
 
 
+def _td3_loop(cfgd, chains, seed=0, **over):
+    """A Td3InnerLoop at cfgd's TD3 shape on the generic GEMM-queue kernel with seeded inputs: (inner loop, run arguments, keyword arguments)."""
+    import numpy as np
+    from learning_environments_amd import _lib, engine
+    from learning_environments_amd.agents.nes_common import linear_init_bounds
+    from learning_environments_amd.config import td3_cfg_from_config, td3_layer_dims
+    cfg = td3_cfg_from_config(cfgd, kernel_variant=_lib.VARIANT_GENERIC, **over)
+    il = engine.Td3InnerLoop(cfg, chains, want_episode_stats=True, want_final_params=True)
+    rng = np.random.RandomState(seed)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    S, Hrn, Lrn = cfg.state_dim, cfg.rn_hidden, cfg.rn_layers
+    if cfg.virtual_env:
+        SA = S + cfg.action_dim
+        p_theta = sum(SA * Hrn + Hrn + (Lrn - 1) * (Hrn * Hrn + Hrn) + o * Hrn + o for o in (S, 1, 1))
+    else:
+        p_theta = max(1, engine.rn_num_params(cfg.reward_env_type, S, cfg.info_dim, Hrn, Lrn))
+    theta = dev((rng.randn(p_theta) * 0.1).astype(np.float32))
+    bounds = linear_init_bounds(td3_layer_dims(cfg))
+    init = dev((rng.uniform(-1.0, 1.0, (chains, il.p_agent)) * bounds[None]).astype(np.float32))
+    keys = dev(np.array([engine.chain_key(11, 0, c, 0) for c in range(chains)], np.uint64).view(np.int64))
+    return il, (theta, None, None, None, init), dict(rng_keys=keys)
+
+
+def run_td3_segments(name, cfgd, chains, episodes, splits, runs=7):
+    """The cost of splitting: one workload as one launch of lenv_td3_rn_inner_loop_icm (the generic kernel: kernel_variant GENERIC), as ONE
+    segment launch and as `splits` segment launches of lenv_td3_rn_inner_loop_segment (with the host's read of the finished words behind each),
+    `runs` timed runs each in alternation after a warm-up of each; medians, spreads and ratios to the old entry; the three must agree bit for bit."""
+    il, pos, kw = _td3_loop(cfgd, chains, train_episodes=episodes)
+    per = -(-episodes // splits)
+    forms = (("old_entry", None), ("one_segment", episodes), ("%d_segments" % splits, per))
+    times, snaps = {k: [] for k, _ in forms}, {}
+    for it in range(runs + 1):
+        for label, epl in forms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            il.run(*pos, episodes_per_launch=epl, **kw)
+            torch.cuda.synchronize()
+            if it:
+                times[label].append(time.perf_counter() - t0)
+            snaps[label] = [t.clone() for t in (il.score, il.stats, il.status, il.episode_test_mean, il.episode_len, il.final_returns, il.final_params)]
+    same = all(all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(snaps["old_entry"], snaps[k])) for k in snaps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    st = il.stats.cpu().numpy()
+    out = dict(config=name, chains=chains, episodes=episodes, runs_each=runs, s_median=med, s_spread={k: max(v) - min(v) for k, v in times.items()},
+               ratio_to_old_entry={k: med[k] / med["old_entry"] for k in med}, bit_identical=bool(same), status_ok=bool(int(il.status.min()) == 0),
+               train_steps_per_chain=float(st[:, 1].mean()), learn_steps_per_chain=float(st[:, 2].mean()), test_steps_per_chain=float(st[:, 3].mean()),
+               workspace_MiB=il.ws_bytes / 2.0 ** 20)
+    print(json.dumps(out))
+    return out
+
+
+def run_td3_episode_time(name, cfgd, shape, chains=8, timed=2):
+    """Seconds per learning episode of a chain at `shape` = (hidden, layers, batch): segment launches of one episode each, one init episode and
+    one learning episode as warm-up, then `timed` learning episodes timed one by one (the median).  A chain has its workgroup to itself, so the
+    time does not depend on the number of chains while they fit the CUs."""
+    H, L, B = shape
+    il, pos, kw = _td3_loop(cfgd, chains, train_episodes=2 + timed, init_episodes=1, hidden=H, layers=L, batch_size=B)
+    times = []
+    for e in range(2 + timed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        il.run_segment(*pos, e, e + 1, **kw)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    st = il.stats.cpu().numpy()
+    fin, status = il.segment_state()
+    out = dict(config=name, hidden=H, layers=L, batch=B, chains=chains, s_per_learning_episode=sorted(times[2:])[len(times[2:]) // 2],
+               s_samples=[round(t, 4) for t in times], status_ok=bool(int(status.min()) == 0), train_steps_per_chain=float(st[:, 1].mean()),
+               learn_steps_per_chain=float(st[:, 2].mean()), test_steps_per_chain=float(st[:, 3].mean()))
+    print(json.dumps(out))
+    return out
+
+
 import bench  # noqa: E402  (the byte / FLOP models live next to the contract line)
 HBM_PEAK_GBPS, MFMA_F32_PEAK_TFLOPS = bench.HBM_PEAK_GBPS, bench.MFMA_F32_PEAK_TFLOPS
 
@@ -307,6 +380,22 @@ if __name__ == "__main__":
         # learning ones of up to 500 steps) and the Pendulum RewardEnv + TD3 at 48 chains (twenty init episodes + two learning ones of 200 steps)
         run_test_mode1_ab("Acrobot SE + DuelingDDQN pop 32, test_mode 1 (12 episodes)", configs.fixed_work(configs.acrobot_syn_env_duelingddqn(32), 12))
         run_test_mode1_ab("Pendulum RN + TD3 pop 16, test_mode 1 (22 episodes x 200 steps)", configs.fixed_work(configs.pendulum_reward_env_td3(16), 22))
+    if "td3_segments" in which:
+        # default_config_cmc.yaml's TD3 shape (2-128-128-1 / 3-128-128-1 relu, B 256, policy_delay 2, same_action_num 2, a VirtualEnv of three
+        # 3-96-96-x nets) on 48 chains, 60 episodes of 100 agent steps (6 init episodes): the old entry, one segment, six segments
+        c = configs.fixed_work(configs.cmc_syn_env_td3(16), 60)
+        c["agents"]["td3"]["init_episodes"] = 6
+        c["envs"]["MountainCarContinuous-v0"]["max_steps"] = 200
+        run_td3_segments("MountainCarContinuous SE + TD3 (B 256) 48 chains, 60 episodes x 100 agent steps: 1 launch / 1 segment / 6 segments", c, 48, 60, 6)
+    if "td3_episode_time" in which:
+        # the TD3 *_transfer_vary_hp scripts' chains (a RewardEnv on the real env, full-length episodes): the nominal shape and the largest one
+        # their hyper-parameter draw can give (hidden 384, 3 layers, batch 768)
+        for make, label in ((configs.cmc_reward_env_td3, "MountainCarContinuous RN (999 steps, same_action_num 2)"),
+                            (configs.halfcheetah_reward_env_td3, "HalfCheetah-standin RN (1000 steps)")):
+            for shape in ((128, 2, 256), (384, 3, 768)):
+                c = configs.fixed_work(make(16), 4)
+                c["agents"]["td3"]["test_episodes"] = 1
+                run_td3_episode_time(label + " + TD3 %dx%d B %d" % shape, c, shape)
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
