@@ -402,6 +402,43 @@ int lenv_dueling_se_inner_loop_hp(const lenv_ddqn_cfg *cfg /*HOST*/, const lenv_
                                   const float *agent_init, const uint64_t *rng_keys, const lenv_tapes *tapes /*HOST*/,
                                   int64_t chains, void *workspace, size_t workspace_bytes, const lenv_inner_out *out /*HOST*/,
                                   void *stream);
+/* The same inner loop in EPISODE SEGMENTS (ABI 7, a function only; the DDQN / DuelingDDQN sibling of lenv_td3_rn_inner_loop_segment): a
+ * launch runs episodes [episode_begin, episode_end) of every chain and leaves a resume record per chain; the next launch (episode_begin =
+ * the last episode_end) goes on from it.  Always the generic GEMM-queue kernel, one workgroup per chain (never the shape-specialised,
+ * wave-chain or team kernels, nor the register-resident lenv_ddqn_se_inner_loop).  For every split 0 = e0 < e1 < .. < ek = train_episodes the
+ * k launches leave every lenv_inner_out array, icm_final and the step trace bit-identical to one lenv_dueling_se_inner_loop_icm / _hp launch
+ * on that kernel.
+ *   episode_begin == 0: the arena is initialised from agent_init / icm_init; the record is written, never read.
+ *   episode_begin  > 0: nothing in the arena is initialised (online and target nets, Adam state, replay ring, early-out meter, ICM parameters
+ *     and their Adam state); the perturbed SE / reward net is staged again from theta / eps (deterministic: the same bits).  The caller passes
+ *     the same workspace (untouched in between), out arrays, tapes, hp, icm and theta / eps / worker / sign as to the earlier segments.  A
+ *     chain whose record does not say "next episode == episode_begin" writes status -10 and does nothing else.
+ * The closing part (final agent.test, score, final_returns, the NaN / time-out padding of unrun episodes, final_online, icm_final) runs once
+ * per chain, in the segment in which the chain ends (train_episodes reached, early out, step_budget time-out); the chain is then `finished`
+ * and later segments leave it and its outputs untouched.  A segment that ends with the chain unfinished writes the cumulative stats and
+ * final_online (a checkpoint) and nothing else of the closing part.
+ * Refused with LENV_ERR_INVALID: !(0 <= episode_begin < episode_end <= cfg->train_episodes), resume == NULL, and whatever
+ * lenv_dueling_se_inner_loop_icm refuses.  workspace_bytes: lenv_dueling_se_workspace_bytes.
+ * The record (opaque to callers), int64 words per chain:
+ *    0 next episode to run            1 finished (0 / 1)               2 status so far (0 ok, else the minimum of the chain's codes)
+ *    3 timed_out_at (-1: no time-out) 4 n_act (random actions drawn)   5 learn_it (learn calls; replay-index draws = learn_it * batch)
+ *    6 n_test_ep (test episodes run = test resets drawn)               7 train_steps (agent steps = epsilon uniforms drawn; ring position
+ *      = train_steps % capacity)      8 test_steps                     9 episodes_run
+ *   10 trace cursor: rows of the step trace written, before the trace_cap clamp (one row per agent step: always equal to word 7)
+ *   11 bit pattern of the double eps_g (the epsilon of the last episode run)
+ *   12..13 bit patterns of the doubles beta1^t, beta2^t of the agent's Adam      14..15 the same of the ICM's Adam (1.0 without an ICM)
+ *   16..31 reserved (0)
+ * Everything else the loop carries lives in the arena (the early-out meter included); the kernel's LDS control words are all rewritten
+ * inside an episode before they are read (the flag guarding the carried phi(s) of reward types 1 / 2 is cleared by the episode's reset;
+ * test_mode 1 sums an episode's training reward in a register that starts at 0 with the episode), so none crosses a boundary.
+ * Status of a FAILING chain and the double meaning of -10: as documented at lenv_td3_rn_inner_loop_segment. */
+#define LENV_DUELING_RESUME_WORDS 32
+int lenv_dueling_se_inner_loop_segment(const lenv_ddqn_cfg *cfg /*HOST*/, const lenv_chain_hp *hp /*HOST, may be NULL*/,
+                                       const lenv_icm_io *icm /*HOST, NULL iff !cfg->icm_enabled*/, const float *theta, const float *eps,
+                                       const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                                       const lenv_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace, size_t workspace_bytes,
+                                       const lenv_inner_out *out /*HOST*/, int32_t episode_begin, int32_t episode_end,
+                                       int64_t *resume /*DEVICE [chains, LENV_DUELING_RESUME_WORDS]*/, void *stream);
 
 /*
  * Config 5: fused inner loop for a TD3 agent on a RewardEnv over a continuous-state real env (agents/TD3.py:63-135,

@@ -12,6 +12,7 @@ ENV = {"CartPole-v0": 0, "Acrobot-v1": 1, "HalfCheetah-v3": 2, "MountainCar-v0":
 RNG_COUNTER, RNG_TAPE = 0, 1
 VARIANT_NO_WAVECHAIN, VARIANT_GENERIC, VARIANT_TEAM_NARROW, VARIANT_NO_DIRECT = 1, 2, 4, 8     # lenv_ddqn_cfg / lenv_td3_cfg kernel_variant bits (A/B timing, kernel-vs-kernel parity tests)
 TD3_RESUME_WORDS = 32                            # LENV_TD3_RESUME_WORDS: int64 words of a chain's record between two segment launches
+DUELING_RESUME_WORDS = 32                        # LENV_DUELING_RESUME_WORDS: the same for lenv_dueling_se_inner_loop_segment
 STATUS_TEAM_GAVE_UP = -10                        # a team member waited too long for the others: repeat the launch with team_size 1
 STATUS_WRONG_SEGMENT = -10                       # the same value from lenv_td3_rn_inner_loop_segment: the chain's record names another episode_begin
                                                  # (segment launches never run on a team; engine.run_checked's retry is for single launches only)
@@ -214,6 +215,7 @@ SIGNATURES = {
     "lenv_dueling_se_inner_loop": (C.c_int, [_P(DdqnCfg)] + _DDQN_RUN),
     "lenv_dueling_se_inner_loop_hp": (C.c_int, [_P(DdqnCfg), _P(ChainHp)] + _DDQN_RUN),
     "lenv_dueling_se_inner_loop_icm": (C.c_int, [_P(DdqnCfg), _P(ChainHp), _P(IcmIo)] + _DDQN_RUN),
+    "lenv_dueling_se_inner_loop_segment": (C.c_int, [_P(DdqnCfg), _P(ChainHp), _P(IcmIo)] + _DDQN_RUN[:-1] + [_i32, _i32, _vp, _vp]),
     "lenv_dueling_agent_init_hp": (C.c_int, [_P(DdqnCfg), _P(ChainHp), _vp, _i64, _vp, _vp]),
     "lenv_icm_num_params": (_i64, [_P(DdqnCfg)]),
     "lenv_real_env_reset": (C.c_int, [_i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),

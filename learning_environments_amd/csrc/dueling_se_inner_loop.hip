@@ -70,6 +70,10 @@ struct DuelArgs {
     // ICM agents (cfg.icm_enabled): fresh parameters per chain, optional final parameters, arena offsets of the ICM buffers
     const float *icm_init; float *icm_final; int P_icm;
     int64_t a_icm[IB_COUNT];
+    // lenv_dueling_se_inner_loop_segment (the SEG instantiations): episodes [ep_begin, ep_end) of every chain, resume records
+    // [chains, LENV_DUELING_RESUME_WORDS]; every other entry point: 0, train_episodes, nullptr.  (Behind everything else: the other
+    // instantiations read their arguments where they were.)
+    int ep_begin, ep_end; int64_t *resume;
 };
 
 // parameter offsets inside one parameter vector (state-dict order)
@@ -120,16 +124,44 @@ constexpr DuelShape kDuelShapes[] = {
     { LENV_ENV_MOUNTAINCAR, 0, 2, 3, 3, 256, 2, 128, 128, 10, LENV_ACT_RELU, LENV_ACT_LEAKYRELU },      // 2: default_config_mountaincar.yaml (DDQN 2-256-256-3)
 };
 
-template <bool ICM, int SHAPE = 0>
+// The resume record of a chain after a segment (include/lenv_hip.h documents the words): thread 0 -- whose copies of the Adam powers are
+// the live ones --, behind the barrier that follows the threads' atomicMin into the folded status
+__device__ __forceinline__ void duel_write_record(int64_t *rec, int next_episode, int finished, int status, int timed_out_at, int n_act,
+                                                  int learn_it, int n_test_ep, int train_steps, int test_steps, int episodes_run, double eps_g,
+                                                  double b1pow, double b2pow, const double *icm_pows)
+{
+    rec[0] = next_episode; rec[1] = finished; rec[2] = status; rec[3] = timed_out_at;
+    rec[4] = n_act; rec[5] = learn_it; rec[6] = n_test_ep; rec[7] = train_steps; rec[8] = test_steps; rec[9] = episodes_run;
+    rec[10] = train_steps;
+    rec[11] = __double_as_longlong(eps_g); rec[12] = __double_as_longlong(b1pow); rec[13] = __double_as_longlong(b2pow);
+    rec[14] = __double_as_longlong(icm_pows[0]); rec[15] = __double_as_longlong(icm_pows[1]);
+    for (int w = 16; w < LENV_DUELING_RESUME_WORDS; ++w) rec[w] = 0;
+}
+
+// SEG (lenv_dueling_se_inner_loop_segment, include/lenv_hip.h) = the generic kernel over the episodes [a.ep_begin, a.ep_end): everything the
+// loop carries from episode to episode outside the arena -- the counters, epsilon, the Adam bias-correction powers, the status -- is read
+// from / written to the chain's resume record; the SE / reward net is staged by every segment, the agent / ICM only by the first; the closing
+// part runs in the segment in which the chain ends.  Its own instantiations: the code of the others is what it was.
+template <bool ICM, int SHAPE = 0, bool SEG = false>
 __global__ __launch_bounds__(DNT) void dueling_se_inner_kernel(const DuelArgs a)
 {
+    static_assert(!SEG || SHAPE == 0, "the SEG instantiations: the generic GEMM-queue kernel");
     extern __shared__ __align__(16) float lds[];
     const lenv_ddqn_cfg &cfg = a.cfg;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t chain = blockIdx.x;
     // the chain's status word starts at 0 (ok); written here rather than by a memset node in front of the launch (a captured
     // generation replayed under rocprofv3 did not run the memset)
-    if (threadIdx.x == 0 && a.out.status) a.out.status[chain] = 0;
+    int64_t *rec = nullptr;
+    const bool fresh = !SEG || a.ep_begin == 0;          // the arena is initialised by this launch
+    if constexpr (SEG) {
+        rec = a.resume + chain * LENV_DUELING_RESUME_WORDS;
+        if (!fresh) {                                    // uniform per chain
+            if (rec[1] == 1) return;                     // finished in an earlier segment: the chain and its outputs stay as they are
+            if (rec[0] != (int64_t)a.ep_begin) { if (tid == 0 && a.out.status) a.out.status[chain] = -10; return; }
+        }
+    }
+    if (threadIdx.x == 0 && a.out.status) { if (fresh) a.out.status[chain] = 0; }
     constexpr bool FIXED = SHAPE != 0;
     constexpr DuelShape kDuelShape = kDuelShapes[SHAPE];
     static_assert(!(FIXED && ICM), "the specialised instantiations have no ICM");
@@ -146,7 +178,11 @@ __global__ __launch_bounds__(DNT) void dueling_se_inner_kernel(const DuelArgs a)
     const int B = FIXED ? kDuelShape.B : (vary ? a.hp_batch[chain] : cfg.batch_size);
     const double lr = vary ? a.hp_lr[chain] : cfg.lr;
     if (vary && (H < 1 || H > cfg.q_hidden || L < 1 || L > cfg.q_layers || B < 1 || B > CFG_B)) {   // uniform per chain
-        if (tid == 0) { if (a.out.status) a.out.status[chain] = -8; a.out.score[chain] = 0.0; }
+        if (tid == 0) {
+            if (a.out.status) a.out.status[chain] = -8;
+            a.out.score[chain] = 0.0;
+            if constexpr (SEG) { for (int w = 0; w < LENV_DUELING_RESUME_WORDS; ++w) rec[w] = 0; rec[1] = 1; rec[2] = -8; rec[3] = -1; }
+        }
         return;
     }
     // `use_layer_norm` of the agent's section (model_utils.py:22-37): the shared LayerNorm behind hidden Linear 2..L of the Q-net / the feature stream
@@ -184,6 +220,12 @@ __global__ __launch_bounds__(DNT) void dueling_se_inner_kernel(const DuelArgs a)
     volatile float *ctrl = misc;
     volatile int *ictrl = reinterpret_cast<volatile int *>(misc + 32);
     float *se_ln_stat = misc + 20;                        // [3][2] mean | rstd of the SE nets' LayerNorm rows (cfg.se_layer_norm)
+    // the control words in use: ctrl[8..16] (advantage mean, Adam, the ICM's Adam at 12..13, phi(s) / phi(s') / the real reward at 14..16),
+    // se_ln_stat = misc[20..25], ictrl[0..5] = misc[32..37].  Every one is written before it is read inside ONE episode (ictrl[5], the
+    // "phi(s) carried over" flag that guards ctrl[14], is cleared by the episode's reset; test_mode 1 sums the training reward in a register
+    // that starts at 0 with every episode), so none of them crosses a segment boundary.
+    // misc[MISC_STATUS_FOLD] (an int): the SEG instantiations' fold of the threads' status codes.  A new control word takes a free index below it.
+    constexpr int MISC_STATUS_FOLD = 48;
     const bool se_ln = FIXED ? false : (cfg.se_layer_norm != 0);
 
     float *arena = a.arena + chain * a.arena_stride;
@@ -229,7 +271,7 @@ __global__ __launch_bounds__(DNT) void dueling_se_inner_kernel(const DuelArgs a)
         }
     }
     // ---- fresh agent: online = target = agent_init, Adam state 0 (DuelingDDQN.py:31-36) ----
-    for (int p = tid; p < P; p += DNT) {
+    if (fresh) for (int p = tid; p < P; p += DNT) {
         const float w = a.agent_init[chain * a.P + p];
         online[p] = w; target[p] = w; adam_m[p] = 0.0f; adam_v[p] = 0.0f;
     }
@@ -239,7 +281,7 @@ __global__ __launch_bounds__(DNT) void dueling_se_inner_kernel(const DuelArgs a)
     if constexpr (ICM) {
         icm_build(icm, S, A, cfg.icm_feature_dim, cfg.icm_hidden, /*discrete=*/true);
         float *ip = arena + a.a_icm[IB_P], *im = arena + a.a_icm[IB_M], *iv = arena + a.a_icm[IB_V];
-        for (int p = tid; p < icm.P; p += DNT) { ip[p] = a.icm_init[chain * a.P_icm + p]; im[p] = 0.0f; iv[p] = 0.0f; }
+        if (fresh) for (int p = tid; p < icm.P; p += DNT) { ip[p] = a.icm_init[chain * a.P_icm + p]; im[p] = 0.0f; iv[p] = 0.0f; }
     }
     if (tid < 64) misc[tid] = 0.0f;
     __syncthreads();
@@ -252,6 +294,15 @@ __global__ __launch_bounds__(DNT) void dueling_se_inner_kernel(const DuelArgs a)
     int train_steps = 0, n_act = 0, learn_it = 0, n_test_ep = 0, test_steps = 0, episodes_run = 0;
     double eps_g = cfg.eps_init, b1pow = 1.0, b2pow = 1.0;
     const int rb_cap = (int)a.rb_cap;
+    if constexpr (SEG) {
+        if (!fresh) {                                    // every thread its copy, like the counters of a single launch
+            status = (int)rec[2];
+            n_act = (int)rec[4]; learn_it = (int)rec[5]; n_test_ep = (int)rec[6]; train_steps = (int)rec[7]; test_steps = (int)rec[8];
+            episodes_run = (int)rec[9];
+            eps_g = __longlong_as_double(rec[11]); b1pow = __longlong_as_double(rec[12]); b2pow = __longlong_as_double(rec[13]);
+            icm_pows[0] = __longlong_as_double(rec[14]); icm_pows[1] = __longlong_as_double(rec[15]);
+        }
+    }
 
     auto obs_of = [&](const double *st, float *obs) { real_env_obs(env_id, st, obs); };
 
@@ -397,7 +448,9 @@ __global__ __launch_bounds__(DNT) void dueling_se_inner_kernel(const DuelArgs a)
     const bool budgeted = cfg.step_budget > 0;
     const bool no_test_env = FIXED ? false : cfg.test_mode == 1;      // BaseAgent.train(env, test_env=None): lenv_ddqn_cfg::test_mode
     int timed_out_at = -1;
-    for (int episode = 0; episode < cfg.train_episodes; ++episode) {
+    bool early_out = false;                               // SEG: the loop ended at the early out
+    const int ep_first = SEG ? a.ep_begin : 0, ep_last = SEG ? a.ep_end : cfg.train_episodes;
+    for (int episode = ep_first; episode < ep_last; ++episode) {
         if (budgeted && (int64_t)train_steps + test_steps > cfg.step_budget) { timed_out_at = episode; break; }   // uniform
         if (episode == 0) eps_g = cfg.eps_init;            // DuelingDDQN.update_parameters_per_episode (:112-117)
         else { eps_g *= cfg.eps_decay; if (eps_g < cfg.eps_min) eps_g = cfg.eps_min; }
@@ -796,7 +849,25 @@ __global__ __launch_bounds__(DNT) void dueling_se_inner_kernel(const DuelArgs a)
         __syncthreads();
         const int brk = ictrl[3];
         __syncthreads();
-        if (brk) break;
+        if (brk) { if constexpr (SEG) early_out = true; break; }
+    }
+    if constexpr (SEG) {
+        if (!early_out && timed_out_at < 0 && a.ep_end < cfg.train_episodes) {
+            // the chain goes on in the next segment: a checkpoint (cumulative stats, the parameters so far) and the record
+            int *st_fold = reinterpret_cast<int *>(misc + MISC_STATUS_FOLD);     // the minimum of the threads' status codes (0 after the clear of misc)
+            if (status != 0) { atomicMin(st_fold, status); if (a.out.status) atomicMin(&a.out.status[chain], status); }
+            if (a.out.final_online) for (int p = tid; p < P; p += DNT) a.out.final_online[chain * a.P + p] = online[p];
+            __syncthreads();
+            if (tid == 0) {
+                if (a.out.stats) {
+                    a.out.stats[chain * 4 + 0] = episodes_run; a.out.stats[chain * 4 + 1] = train_steps;
+                    a.out.stats[chain * 4 + 2] = learn_it; a.out.stats[chain * 4 + 3] = test_steps;
+                }
+                duel_write_record(rec, a.ep_end, 0, *st_fold, timed_out_at, n_act, learn_it, n_test_ep, train_steps, test_steps, episodes_run,
+                                  eps_g, b1pow, b2pow, icm_pows);
+            }
+            return;
+        }
     }
     PT_MARK(9);
     const int64_t remaining = cfg.step_budget - ((int64_t)train_steps + test_steps);     // time_remaining - elapsed
@@ -855,6 +926,13 @@ __global__ __launch_bounds__(DNT) void dueling_se_inner_kernel(const DuelArgs a)
         if (a.icm_final) for (int p = tid; p < icm.P; p += DNT) a.icm_final[chain * a.P_icm + p] = arena[a.a_icm[IB_P] + p];
     }
     if (a.out.status && status != 0) atomicMin(&a.out.status[chain], status);
+    if constexpr (SEG) {
+        int *st_fold = reinterpret_cast<int *>(misc + MISC_STATUS_FOLD);
+        if (status != 0) atomicMin(st_fold, status);
+        __syncthreads();
+        if (tid == 0) duel_write_record(rec, a.ep_end, 1, *st_fold, timed_out_at, n_act, learn_it, n_test_ep, train_steps, test_steps, episodes_run,
+                                        eps_g, b1pow, b2pow, icm_pows);
+    }
     (void)lane; (void)wave;
 }
 
@@ -1018,10 +1096,12 @@ extern "C" int lenv_dueling_se_inner_loop_hp(const lenv_ddqn_cfg *cfg, const len
                                           workspace_bytes, out, stream);
 }
 
-extern "C" int lenv_dueling_se_inner_loop_icm(const lenv_ddqn_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta,
-                                              const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
-                                              const uint64_t *rng_keys, const lenv_tapes *tapes, int64_t chains, void *workspace,
-                                              size_t workspace_bytes, const lenv_inner_out *out, void *stream)
+// the launch behind lenv_dueling_se_inner_loop_icm (segment false: one launch from the first episode to the final test, resume unused) and
+// lenv_dueling_se_inner_loop_segment (segment true: episodes [ep_begin, ep_end) on the SEG instantiations of the generic kernel)
+static int dueling_launch(const lenv_ddqn_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta, const float *eps,
+                          const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys, const lenv_tapes *tapes,
+                          int64_t chains, void *workspace, size_t workspace_bytes, const lenv_inner_out *out, bool segment, int32_t ep_begin,
+                          int32_t ep_end, int64_t *resume, void *stream)
 {
     if (!cfg || !theta || !agent_init || !out || !out->score || !workspace || chains < 0) return LENV_ERR_INVALID;
     if (cfg->icm_enabled && (!icm || !icm->icm_init)) return LENV_ERR_INVALID;
@@ -1029,6 +1109,7 @@ extern "C" int lenv_dueling_se_inner_loop_icm(const lenv_ddqn_cfg *cfg, const le
     if (eps && (!worker || !sign)) return LENV_ERR_INVALID;
     if (cfg->rng_mode == LENV_RNG_TAPE && !tapes) return LENV_ERR_INVALID;
     if (cfg->rng_mode == LENV_RNG_COUNTER && !rng_keys) return LENV_ERR_INVALID;
+    if (segment && (!resume || ep_begin < 0 || ep_begin >= ep_end || ep_end > cfg->train_episodes)) return LENV_ERR_INVALID;
     if (chains == 0) return LENV_OK;
     DuelArgs a;
     size_t lds_bytes;
@@ -1036,6 +1117,7 @@ extern "C" int lenv_dueling_se_inner_loop_icm(const lenv_ddqn_cfg *cfg, const le
     if (rc != LENV_OK) return rc;
     if (workspace_bytes < (size_t)chains * a.arena_stride * sizeof(float)) return LENV_ERR_WORKSPACE;
     a.cfg = *cfg;
+    a.ep_begin = segment ? ep_begin : 0; a.ep_end = segment ? ep_end : cfg->train_episodes; a.resume = segment ? resume : nullptr;
     a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.agent_init = agent_init; a.rng_keys = rng_keys;
     if (tapes) a.tapes = *tapes; else a.tapes = lenv_tapes{};
     a.arena = static_cast<float *>(workspace);
@@ -1044,7 +1126,8 @@ extern "C" int lenv_dueling_se_inner_loop_icm(const lenv_ddqn_cfg *cfg, const le
     a.hp_hidden = hp ? hp->q_hidden : nullptr; a.hp_layers = hp ? hp->q_layers : nullptr;
     a.icm_init = cfg->icm_enabled ? icm->icm_init : nullptr; a.icm_final = cfg->icm_enabled ? icm->icm_final : nullptr;
     void (*kern)(const DuelArgs) = cfg->icm_enabled ? dueling_se_inner_kernel<true> : dueling_se_inner_kernel<false>;
-    {
+    if (segment) kern = cfg->icm_enabled ? dueling_se_inner_kernel<true, 0, true> : dueling_se_inner_kernel<false, 0, true>;
+    else {
         // the published Acrobot DuelingDDQN shape in production form takes the shape-specialised instantiation
         const bool off = (cfg->kernel_variant & LENV_VARIANT_GENERIC) != 0;
         auto matches = [&](const DuelShape &sp) {
@@ -1075,6 +1158,25 @@ extern "C" int lenv_dueling_se_inner_loop_icm(const lenv_ddqn_cfg *cfg, const le
     if (e != hipSuccess) return LENV_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+}
+
+extern "C" int lenv_dueling_se_inner_loop_icm(const lenv_ddqn_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta,
+                                              const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
+                                              const uint64_t *rng_keys, const lenv_tapes *tapes, int64_t chains, void *workspace,
+                                              size_t workspace_bytes, const lenv_inner_out *out, void *stream)
+{
+    return dueling_launch(cfg, hp, icm, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, false, 0,
+                          0, nullptr, stream);
+}
+
+extern "C" int lenv_dueling_se_inner_loop_segment(const lenv_ddqn_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta,
+                                                  const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
+                                                  const uint64_t *rng_keys, const lenv_tapes *tapes, int64_t chains, void *workspace,
+                                                  size_t workspace_bytes, const lenv_inner_out *out, int32_t episode_begin,
+                                                  int32_t episode_end, int64_t *resume, void *stream)
+{
+    return dueling_launch(cfg, hp, icm, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, true,
+                          episode_begin, episode_end, resume, stream);
 }
 
 extern "C" int lenv_dueling_agent_init_hp(const lenv_ddqn_cfg *cfg, const lenv_chain_hp *hp, const uint64_t *rng_keys, int64_t chains,

@@ -325,9 +325,12 @@ class InnerLoop(_InnerLoopBase):
     cfg_type, hp_fields = DdqnCfg, ("batch_size", "q_hidden", "q_layers")
     num_params_fn, agent_init_fn = "lenv_dueling_num_params", "lenv_dueling_agent_init_hp"
 
-    def __init__(self, cfg, chains, want_episode_stats=True, want_final_online=False, trace_cap=0, vary=False):
+    def __init__(self, cfg, chains, want_episode_stats=True, want_final_online=False, trace_cap=0, vary=False, segments=False):
         """vary=True: the *_vary agents -- cfg carries the MAXIMAL batch_size / q_hidden / q_layers, every chain runs with its
-        own lr / batch_size / hidden_size / hidden_layer (set_hp) in the GEMM-tiled kernel (lenv_dueling_se_inner_loop_icm)."""
+        own lr / batch_size / hidden_size / hidden_layer (set_hp) in the GEMM-tiled kernel (lenv_dueling_se_inner_loop_icm).
+        segments=True: the inner loop will run as segment launches (run(episodes_per_launch=) / run_segment), which exist on the
+        GEMM-tiled kernel alone: a cfg the register-resident kernel would take is routed there too (its single launch included; a plain-DQN
+        cfg needs grad_chunk 0, the one sequential batch gradient that kernel computes)."""
         super().__init__(cfg, chains)
         L = _lib.lib()
         # DuelingDDQN, and DDQN whose Critic_DQN the register-resident kernel refuses (hidden_layer >= 2 / wide layers),
@@ -335,7 +338,9 @@ class InnerLoop(_InnerLoopBase):
         # (a RewardEnv / real-env cfg with an explicit micro-chunk takes the register-resident kernel's RENV instantiations; with grad_chunk 0 --
         # one sequential batch gradient -- the probe refuses it and the GEMM-tiled kernel runs it)
         icm = bool(cfg.icm_enabled)                    # ICM agents (ddqn_icm / duelingddqn_icm): GEMM-tiled kernel only
-        self.dueling = bool(vary) or icm or cfg.agent_kind == 1 or (cfg.agent_kind == 0 and L.lenv_ddqn_se_lds_bytes(C.byref(cfg)) <= 0
+        self.segments = bool(segments)
+        self.resume = None                              # the segment launches' records [chains, DUELING_RESUME_WORDS], allocated by the first
+        self.dueling = bool(vary) or icm or self.segments or cfg.agent_kind == 1 or (cfg.agent_kind == 0 and L.lenv_ddqn_se_lds_bytes(C.byref(cfg)) <= 0
                                                                     and L.lenv_dueling_num_params(C.byref(cfg)) > 0)
         if self.dueling:
             self.p_agent = self._num_params(cfg)
@@ -347,17 +352,62 @@ class InnerLoop(_InnerLoopBase):
         self._init_icm("lenv_icm_num_params")
         self._alloc_outputs(ws_bytes, want_episode_stats, want_final_online, trace_cap)
 
-    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None):
-        """Enqueue one fused inner loop for all chains on the current stream (asynchronous)."""
+    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None, episodes_per_launch=None, on_segment=None):
+        """episodes_per_launch None: one fused inner loop for all chains on the current stream (asynchronous).  An integer: the same inner
+        loop as a series of segment launches of that many episodes each (lenv_dueling_se_inner_loop_segment, always the generic GEMM-tiled
+        kernel: the inner loop must have been built with segments=True; same bits for every split).  After each segment the chains'
+        `finished` words and statuses come to the host (one small copy, the only synchronisation), on_segment(episodes_done,
+        finished_count) is called if given, then -- after the callback, so that it sees the segment in which a chain failed -- a bad status
+        raises as check_status does, and the series stops as soon as every chain is finished.  A cfg without training episodes has no
+        segment to run: ValueError (the single launch runs its closing test)."""
         if agent_init is None and self.vary:
             agent_init = self.agent_init
-        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
-        if self.dueling:       # the GEMM-tiled kernel: per-chain hyper-parameters and the ICM may be NULL
-            args = (self._hp_arg(), self._icm_arg()) + args
-        fn = "lenv_dueling_se_inner_loop_icm" if self.dueling else "lenv_ddqn_se_inner_loop"
-        rc = getattr(_lib.lib(), fn)(C.byref(self.cfg), *args)
-        _lib.check(rc, "lenv_dueling_se_inner_loop" if self.dueling else "lenv_ddqn_se_inner_loop")
+        if episodes_per_launch is None:
+            args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+            if self.dueling:       # the GEMM-tiled kernel: per-chain hyper-parameters and the ICM may be NULL
+                args = (self._hp_arg(), self._icm_arg()) + args
+            fn = "lenv_dueling_se_inner_loop_icm" if self.dueling else "lenv_ddqn_se_inner_loop"
+            rc = getattr(_lib.lib(), fn)(C.byref(self.cfg), *args)
+            _lib.check(rc, "lenv_dueling_se_inner_loop" if self.dueling else "lenv_ddqn_se_inner_loop")
+            return self.score
+        step = int(episodes_per_launch)
+        if step < 1:
+            raise ValueError("episodes_per_launch must be at least 1")
+        E = self.cfg.train_episodes
+        if E < 1:
+            raise ValueError("episodes_per_launch needs a cfg with at least one training episode")
+        for begin in range(0, E, step):
+            end = min(E, begin + step)
+            self.run_segment(theta, eps, worker, sign, agent_init, begin, end, rng_keys=rng_keys, tapes=tapes)
+            finished, st = self.segment_state()
+            if on_segment is not None:
+                on_segment(end, int(finished.sum()))
+            if int(st.min()) != 0:
+                raise _lib.LenvError("inner loop reported status %s" % st.tolist())
+            if int(finished.min()) == 1:
+                break
         return self.score
+
+    def run_segment(self, theta, eps, worker, sign, agent_init, episode_begin, episode_end, rng_keys=None, tapes=None):
+        """Enqueue episodes [episode_begin, episode_end) of every chain (asynchronous).  episode_begin 0 starts afresh; a later segment goes
+        on from self.resume and needs the same arguments and an untouched workspace."""
+        if not self.segments:
+            raise ValueError("segment launches need an inner loop built with segments=True (the GEMM-tiled kernel and its workspace)")
+        if agent_init is None and self.vary:
+            agent_init = self.agent_init
+        if self.resume is None:
+            self.resume = torch.zeros((self.chains, _lib.DUELING_RESUME_WORDS), dtype=torch.int64, device=self.dev)
+        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+        rc = _lib.lib().lenv_dueling_se_inner_loop_segment(C.byref(self.cfg), self._hp_arg(), self._icm_arg(), *args[:-1], int(episode_begin),
+                                                           int(episode_end), _ptr(self.resume), args[-1])
+        _lib.check(rc, "lenv_dueling_se_inner_loop_segment")
+        return self.score
+
+    def segment_state(self):
+        """(finished [chains], status [chains]) on the host after the segments enqueued so far (synchronises): the record's finished word and
+        the smaller of the record's status and the status output (a refused continuation, -10, is reported there alone)."""
+        both = torch.stack((self.resume[:, 1], torch.minimum(self.resume[:, 2], self.status.to(torch.int64)))).cpu()
+        return both[0], both[1]
 
 
 class QlInnerLoop(_InnerLoopBase):

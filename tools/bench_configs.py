@@ -173,6 +173,116 @@ def run_td3_episode_time(name, cfgd, shape, chains=8, timed=2):
     return out
 
 
+def _dueling_loop(cfgd, chains, shape, seed=0, lr=None):
+    """An InnerLoop built for segments (the generic GEMM-tiled kernel, per-chain hyper-parameter arrays with `shape` = (hidden, layers, batch) for
+    every chain, as experiments/transfer_cartpole.py launches its agents) with seeded inputs: (inner loop, run arguments, keyword arguments)."""
+    import numpy as np
+    from learning_environments_amd import engine
+    from learning_environments_amd.config import ddqn_cfg_from_config
+    H, L, B = shape
+    family = "duelingddqn" if "duelingddqn" in cfgd["agents"] else "ddqn"
+    cfgd["agents"][family].update(hidden_size=H, hidden_layer=L, batch_size=B)
+    cfgd["agents"]["gtn"]["agent_name"] = family + "_vary"
+    cfg = ddqn_cfg_from_config(cfgd)
+    cfg.grad_chunk = 0
+    il = engine.InnerLoop(cfg, chains, want_episode_stats=True, want_final_online=True, vary=True, segments=True)
+    a = cfgd["agents"][family]
+    il.set_hp([a["lr"] if lr is None else lr] * chains, [B] * chains, [H] * chains, [L] * chains)
+    rng = np.random.RandomState(seed)
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    p_theta = engine.mlp_num_params(engine.mlp_desc(1 if cfg.reward_env_type == 0 else cfg.state_dim, cfg.se_hidden, cfg.se_layers, 1, cfg.se_act))
+    theta = dev((rng.randn(p_theta) * 0.1).astype(np.float32))
+    keys = dev(np.array([engine.chain_key(13, 0, c, 0) for c in range(chains)], np.uint64).view(np.int64))
+    il.draw_agent_init(keys)
+    return il, (theta, None, None, None, None), dict(rng_keys=keys)
+
+
+def _cartpole_transfer_config(script, episodes):
+    """The CartPole RewardEnv (published values: type 2, PReLU reward net 4-64-1, 200 steps) with the transfer script's settings block."""
+    from learning_environments_amd.experiments import transfer_cartpole as tc
+    c = tc.apply_settings(tc.base_config(), script, dict(train_episodes=episodes))
+    c["envs"]["CartPole-v0"]["solved_reward"] = tc.SOLVED_REWARD
+    if script == "algo":
+        c["agents"].pop("ddqn")
+    return c
+
+
+def run_dueling_segments(name, cfgd, chains, shape, episodes, splits, runs=7):
+    """The cost of splitting the DDQN / DuelingDDQN inner loop: one workload as one launch of lenv_dueling_se_inner_loop_hp / _icm (per-chain
+    hyper-parameters: the generic kernel), as ONE segment launch and as `splits` segment launches of lenv_dueling_se_inner_loop_segment (with the
+    host's read of the finished words behind each), `runs` timed runs each in alternation after a warm-up of each; medians, the runs' ranges
+    and ratios to the old entry; the three must agree bit for bit."""
+    il, pos, kw = _dueling_loop(cfgd, chains, shape)
+    per = -(-episodes // splits)
+    forms = (("old_entry", None), ("one_segment", episodes), ("%d_segments" % splits, per))
+    times, snaps = {k: [] for k, _ in forms}, {}
+    for it in range(runs + 1):
+        for label, epl in forms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            il.run(*pos, episodes_per_launch=epl, **kw)
+            torch.cuda.synchronize()
+            if it:
+                times[label].append(time.perf_counter() - t0)
+            snaps[label] = [t.clone() for t in (il.score, il.stats, il.status, il.episode_test_mean, il.episode_len, il.final_returns, il.final_online)]
+    same = all(all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(snaps["old_entry"], snaps[k])) for k in snaps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    lo, hi = min(times["old_entry"]), max(times["old_entry"])
+    last = "%d_segments" % splits
+    st = il.stats.cpu().numpy()
+    out = dict(config=name, chains=chains, episodes=episodes, runs_each=runs, s_median=med, s_min={k: min(v) for k, v in times.items()},
+               s_max={k: max(v) for k, v in times.items()}, s_spread={k: max(v) - min(v) for k, v in times.items()},
+               ratio_to_old_entry={k: med[k] / med["old_entry"] for k in med}, split_median_inside_old_entry_range=bool(lo <= med[last] <= hi),
+               bit_identical=bool(same), status_ok=bool(int(il.status.min()) == 0), train_steps_per_chain=float(st[:, 1].mean()),
+               train_steps_max=int(st[:, 1].max()), learn_steps_per_chain=float(st[:, 2].mean()), test_steps_per_chain=float(st[:, 3].mean()),
+               workspace_MiB=il.ws_bytes / 2.0 ** 20)
+    assert same, "the three forms of the launch differ"
+    # where a split series can lose time: a workgroup per chain and every chain resident, so a launch lasts as long as its slowest chain -- one launch
+    # max_c sum_e steps(c, e), a series sum_seg max_c sum_(e in seg) steps(c, e): the chains wait for each other at every boundary.  steps = the
+    # episode's agent steps plus `w` times its test steps (CartPole with one test episode: the test return IS its length), for w = 0 and 0.2
+    ln = il.episode_len.cpu().numpy().astype(float)
+    tl = il.episode_test_mean.cpu().numpy() if il.cfg.test_episodes == 1 and il.cfg.env_id == 0 else 0.0 * ln
+    model = {}
+    for w in (0.0, 0.2):
+        S = ln + w * tl
+        model["test_step_weight_%.1f" % w] = sum(S[:, b:b + per].sum(1).max() for b in range(0, episodes, per)) / S.sum(1).max()
+    out["boundary_wait_model_ratio"] = model
+    out["slowest_chain_per_segment"] = [int(ln[:, b:b + per].sum(1).argmax()) for b in range(0, episodes, per)]
+    print(json.dumps(out))
+    return out
+
+
+def run_dueling_episode_time(name, cfgd, shape, chains=8, episodes=300, lr=1e-3):
+    """Seconds per FULL-LENGTH learning episode (max_steps agent steps, each with a learn step) of a chain at `shape` = (hidden, layers, batch):
+    segment launches of one episode each, every one timed.  CartPole episodes end when the pole falls, so a launch is full-length only once an
+    agent balances: the chains train (lr 1e-3 instead of the block's: the time of a step does not depend on it) and the figure is the median
+    over the segments in which some chain ran max_steps steps -- a workgroup per chain, so such a segment takes what its longest chain takes,
+    including that chain's test episode.  Beside it: every learning segment's time scaled to max_steps by its longest chain's length."""
+    il, pos, kw = _dueling_loop(cfgd, chains, shape, lr=lr)
+    E, full_len = il.cfg.train_episodes, il.cfg.max_steps
+    assert E == episodes
+    times = []
+    for e in range(E):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        il.run_segment(*pos, e, e + 1, **kw)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    fin, status = il.segment_state()
+    longest = il.episode_len.cpu().numpy().max(axis=0)
+    full = sorted(t for t, n in zip(times[2:], longest[2:]) if n == full_len)
+    scaled = sorted(t * full_len / n for t, n in zip(times[2:], longest[2:]))
+    st = il.stats.cpu().numpy()
+    out = dict(config=name, hidden=shape[0], layers=shape[1], batch=shape[2], chains=chains, episodes=E, full_length_segments=len(full),
+               s_per_full_length_episode=full[len(full) // 2] if full else None, s_full_min=full[0] if full else None, s_full_max=full[-1] if full else None,
+               s_scaled_to_full_length_median=scaled[len(scaled) // 2], s_scaled_to_full_length_max=scaled[-1],
+               us_per_agent_step_of_full_segments=1e6 * full[len(full) // 2] / full_len if full else None, status_ok=bool(int(status.min()) == 0),
+               finished=int(fin.sum()), train_steps_per_chain=float(st[:, 1].mean()), learn_steps_per_chain=float(st[:, 2].mean()),
+               test_steps_per_chain=float(st[:, 3].mean()))
+    print(json.dumps(out))
+    return out
+
+
 import bench  # noqa: E402  (the byte / FLOP models live next to the contract line)
 HBM_PEAK_GBPS, MFMA_F32_PEAK_TFLOPS = bench.HBM_PEAK_GBPS, bench.MFMA_F32_PEAK_TFLOPS
 
@@ -396,6 +506,22 @@ if __name__ == "__main__":
                 c = configs.fixed_work(make(16), 4)
                 c["agents"]["td3"]["test_episodes"] = 1
                 run_td3_episode_time(label + " + TD3 %dx%d B %d" % shape, c, shape)
+    if "dueling_segments" in which:
+        # the CartPole vary_hp transfer script's nominal DDQN chain (4-64-2 relu, batch 32, lr 2.5e-4, eps 1.0 -> 0.1 at 0.9 per episode, one init
+        # episode, one test episode per training episode) on the published CartPole RewardEnv (type 2, reward net 4-64-1), 48 chains, 240 episodes of
+        # up to 200 steps: the old entry, one segment, six segments
+        run_dueling_segments("CartPole RN + DDQN 64x1 B 32, 48 chains, 240 episodes of up to 200 steps: 1 launch / 1 segment / 6 segments",
+                             _cartpole_transfer_config("vary_hp", 240), 48, (64, 1, 32), 240, 6)
+        # the same with ONE chain (chain 0 of the 48): no chain waits for another at a boundary, what is left is the cost of splitting itself
+        run_dueling_segments("CartPole RN + DDQN 64x1 B 32, 1 chain, 240 episodes of up to 200 steps: 1 launch / 1 segment / 6 segments",
+                             _cartpole_transfer_config("vary_hp", 240), 1, (64, 1, 32), 240, 6)
+    if "dueling_episode_time" in which:
+        # the CartPole transfer scripts' chains (a RewardEnv on the real env, episodes of up to 200 steps): the nominal shape and the largest one
+        # the vary_hp script's draw can give (hidden 192, 2 layers, batch 96), for the plain-DQN agent (vary_hp script) and the dueling one (algo
+        # script, feature_dim 128)
+        for script, label in (("vary_hp", "DDQN"), ("algo", "DuelingDDQN f128")):
+            for shape in ((64, 1, 32), (192, 2, 96)):
+                run_dueling_episode_time("CartPole RN (200 steps) + %s %dx%d B %d" % ((label,) + shape), _cartpole_transfer_config(script, 300), shape)
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
