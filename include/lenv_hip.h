@@ -734,6 +734,39 @@ int lenv_ppo_rn_inner_loop(const lenv_ppo_cfg *cfg /*HOST*/, const float *theta,
                            const float *sign, const float *agent_init, const uint64_t *rng_keys,
                            const lenv_ppo_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace,
                            size_t workspace_bytes, const lenv_ppo_out *out /*HOST*/, void *stream);
+/* The same inner loop in EPISODE SEGMENTS (ABI 7, a function only): a launch runs episodes [episode_begin, episode_end) of every chain and
+ * leaves a resume record per chain; the next launch (episode_begin = the last episode_end) goes on from it.  For every split
+ * 0 = e0 < e1 < .. < ek = train_episodes the k launches leave every lenv_ppo_out array (score, stats, status, episode_test_mean, episode_len,
+ * final_returns, final_params, the five trace arrays, learn_step, learn_params) bit-identical to one lenv_ppo_rn_inner_loop launch.
+ *   episode_begin == 0: the arena is initialised from agent_init; the record is written, never read.
+ *   episode_begin  > 0: nothing in the arena is initialised; the caller passes the same workspace (untouched in between), out arrays, tapes
+ *     and theta / eps / worker / sign / rng_keys as to the earlier segments.  A chain whose record does not say
+ *     "next episode == episode_begin" writes status -10 and does nothing else.
+ * The closing part (final agent.test, score, final_returns, the NaN / 0 padding of unrun episodes, the final stats) runs once per chain, in the
+ * segment in which the chain ends (train_episodes reached or early out); the chain is then `finished` and later segments return at once and
+ * leave it and its outputs untouched.  A segment that ends with the chain unfinished writes the cumulative stats and final_params (a
+ * checkpoint) and nothing else of the closing part.
+ * Refused with LENV_ERR_INVALID, before the `chains == 0` return: !(0 <= episode_begin < episode_end <= cfg->train_episodes), resume == NULL,
+ * and whatever lenv_ppo_rn_inner_loop refuses (an unsupported cfg: its own code).  workspace_bytes: lenv_ppo_rn_workspace_bytes.
+ * The record (opaque to callers), int64 words per chain:
+ *    0 next episode to run            1 finished (0 / 1)               2 status so far (0 ok, else the minimum of the chain's codes)
+ *    3 n_actn (train-action noise rows drawn)   4 n_testn (test noise rows)   5 n_test_ep (test episodes run)
+ *    6 time_step (env steps since the last learn call: PPO.py:100's counter)   7 n_rows (rows waiting in the on-policy buffer)
+ *    8 train_steps (agent steps; also the trace cursor before the trace_cap clamp)   9 test_steps   10 episodes_run
+ *   11 learn_calls (PPO.learn calls; also the learn_step / learn_params cursor before the learn_cap clamp)
+ *   12..13 bit patterns of the doubles beta1^t, beta2^t of the optimizer
+ *   14..21 bit patterns (low 32 bits) of actor_old's action_std[0..8) as the next action has to see it: clamped to >= 0.001 by the
+ *          actions taken so far, equal to actor's after a learn call; entries >= action_dim are 0      22..31 reserved (0)
+ * The parameters, the Adam moments, the partly filled on-policy row buffer and the early-out meter live in the arena.
+ * Status of a FAILING chain: a thread keeps the code of its latest failure and the launch reports the minimum over the threads; a series of
+ * segments folds that minimum at every boundary and starts every thread of the next segment from it, so after different kinds of failure in
+ * different segments a series can report a smaller code than the single launch would.  Both are non-zero. */
+#define LENV_PPO_RESUME_WORDS 32
+int lenv_ppo_rn_inner_loop_segment(const lenv_ppo_cfg *cfg /*HOST*/, const float *theta, const float *eps, const int32_t *worker,
+                                   const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                                   const lenv_ppo_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace,
+                                   size_t workspace_bytes, const lenv_ppo_out *out /*HOST*/, int32_t episode_begin, int32_t episode_end,
+                                   int64_t *resume /*DEVICE [chains, LENV_PPO_RESUME_WORDS]*/, void *stream);
 
 /*
  * Batched forward of one MLP in the flat layout above: y [rows,out] = net(x [rows,in]) (models/model_utils.py:31-39;

@@ -13,6 +13,7 @@ RNG_COUNTER, RNG_TAPE = 0, 1
 VARIANT_NO_WAVECHAIN, VARIANT_GENERIC, VARIANT_TEAM_NARROW, VARIANT_NO_DIRECT = 1, 2, 4, 8     # lenv_ddqn_cfg / lenv_td3_cfg kernel_variant bits (A/B timing, kernel-vs-kernel parity tests)
 TD3_RESUME_WORDS = 32                            # LENV_TD3_RESUME_WORDS: int64 words of a chain's record between two segment launches
 DUELING_RESUME_WORDS = 32                        # LENV_DUELING_RESUME_WORDS: the same for lenv_dueling_se_inner_loop_segment
+PPO_RESUME_WORDS = 32                            # LENV_PPO_RESUME_WORDS: the same for lenv_ppo_rn_inner_loop_segment
 STATUS_TEAM_GAVE_UP = -10                        # a team member waited too long for the others: repeat the launch with team_size 1
 STATUS_WRONG_SEGMENT = -10                       # the same value from lenv_td3_rn_inner_loop_segment: the chain's record names another episode_begin
                                                  # (segment launches never run on a team; engine.run_checked's retry is for single launches only)
@@ -258,6 +259,7 @@ SIGNATURES = {
     "lenv_ppo_rn_lds_bytes": (_i64, [_P(PpoCfg)]),
     "lenv_ppo_rn_workspace_bytes": (_i64, [_P(PpoCfg), _i64]),
     "lenv_ppo_rn_inner_loop": (C.c_int, [_P(PpoCfg)] + [_vp] * 6 + [_P(PpoTapes), _i64, _vp, C.c_size_t, _P(PpoOut), _vp]),
+    "lenv_ppo_rn_inner_loop_segment": (C.c_int, [_P(PpoCfg)] + [_vp] * 6 + [_P(PpoTapes), _i64, _vp, C.c_size_t, _P(PpoOut), _i32, _i32, _vp, _vp]),
     "lenv_nes_worker_best": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "lenv_nes_worker_best_multi": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "lenv_nes_draw": (C.c_int, [C.c_uint64, C.c_uint64] + _NES_DRAW_TAIL),

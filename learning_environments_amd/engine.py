@@ -617,18 +617,63 @@ class PpoInnerLoop(_InnerLoopBase):
         self.p_theta = _count("lenv_ppo_rn_num_params", C.byref(cfg))
         self.learn_cap = int(learn_cap)
         self.learn_step = self.learn_params = None
+        self.resume = None                              # the segment launches' records [chains, PPO_RESUME_WORDS], allocated by the first
         if self.learn_cap:
             self.learn_step = torch.zeros((self.chains, self.learn_cap), dtype=torch.int32, device=self.dev)
             self.learn_params = torch.zeros((self.chains, self.learn_cap, self.p_agent), dtype=torch.float32, device=self.dev)
         self._alloc_outputs(_count("lenv_ppo_rn_workspace_bytes", C.byref(cfg), self.chains), want_episode_stats, want_final_params, trace_cap)
 
-    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None):
+    def _ppo_args(self, theta, eps, worker, sign, agent_init, rng_keys, tapes):
         args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
         if theta is not None and self.cfg.reward_env_type != 0 and theta.numel() != self.p_theta:
             raise ValueError("theta must hold %d reward-net parameters" % self.p_theta)
-        rc = _lib.lib().lenv_ppo_rn_inner_loop(C.byref(self.cfg), *args)
-        _lib.check(rc, "lenv_ppo_rn_inner_loop")
+        return args
+
+    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None, episodes_per_launch=None, on_segment=None):
+        """episodes_per_launch None: one launch from the first episode to the final test (asynchronous).  An integer: the same inner loop
+        as a series of segment launches of that many episodes each (lenv_ppo_rn_inner_loop_segment; same bits for every split).  After each
+        segment the chains' `finished` words and statuses come to the host (one small copy, the only synchronisation),
+        on_segment(episodes_done, finished_count) is called if given, then -- after the callback, so that it sees the segment in which a
+        chain failed -- a bad status raises as check_status does, and the series stops as soon as every chain is finished.  A cfg without
+        training episodes has no segment to run: ValueError (the single launch runs its closing test)."""
+        if episodes_per_launch is None:
+            rc = _lib.lib().lenv_ppo_rn_inner_loop(C.byref(self.cfg), *self._ppo_args(theta, eps, worker, sign, agent_init, rng_keys, tapes))
+            _lib.check(rc, "lenv_ppo_rn_inner_loop")
+            return self.score
+        step = int(episodes_per_launch)
+        if step < 1:
+            raise ValueError("episodes_per_launch must be at least 1")
+        E = self.cfg.train_episodes
+        if E < 1:
+            raise ValueError("episodes_per_launch needs a cfg with at least one training episode")
+        for begin in range(0, E, step):
+            end = min(E, begin + step)
+            self.run_segment(theta, eps, worker, sign, agent_init, begin, end, rng_keys=rng_keys, tapes=tapes)
+            finished, st = self.segment_state()
+            if on_segment is not None:
+                on_segment(end, int(finished.sum()))
+            if int(st.min()) != 0:
+                raise _lib.LenvError("inner loop reported status %s" % st.tolist())
+            if int(finished.min()) == 1:
+                break
         return self.score
+
+    def run_segment(self, theta, eps, worker, sign, agent_init, episode_begin, episode_end, rng_keys=None, tapes=None):
+        """Enqueue episodes [episode_begin, episode_end) of every chain (asynchronous).  episode_begin 0 starts afresh; a later segment goes
+        on from self.resume and needs the same arguments and an untouched workspace."""
+        if self.resume is None:
+            self.resume = torch.zeros((self.chains, _lib.PPO_RESUME_WORDS), dtype=torch.int64, device=self.dev)
+        args = self._ppo_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+        rc = _lib.lib().lenv_ppo_rn_inner_loop_segment(C.byref(self.cfg), *args[:-1], int(episode_begin), int(episode_end), _ptr(self.resume),
+                                                       args[-1])
+        _lib.check(rc, "lenv_ppo_rn_inner_loop_segment")
+        return self.score
+
+    def segment_state(self):
+        """(finished [chains], status [chains]) on the host after the segments enqueued so far (synchronises): the record's finished word and
+        the smaller of the record's status and the status output (a refused continuation, -10, is reported there alone)."""
+        both = torch.stack((self.resume[:, 1], torch.minimum(self.resume[:, 2], self.status.to(torch.int64)))).cpu()
+        return both[0], both[1]
 
 
 def rn_shape_population(cfg, theta, eps, worker, sign, next_state, reward, chains=1):

@@ -10,10 +10,21 @@ same order plus the env name, same return shapes):
         writes the script's "settings for comparability" block (PPO_SETTINGS, restated as data) into config['agents']['ppo'] IN PLACE like the
         reference, then for each of MODEL_AGENTS fresh PPO agents:  reward, episode_length, _ = agent.train(env=env, test_env=real_env)
 
-Here all agents of a call -- and, through train_test_agents_models, all models of a mode -- are the chains of ONE launch of
-lenv_ppo_rn_inner_loop.  Modes: '0' = the real env (a RewardEnv of type 0: the real reward passes through), '1' / '2' / '5' / '6' = reward
-envs of that reward_env_type.  Mode '-1' (ppo_icm) is not built.  Reading hpbandster logs is out of scope: the caller passes model files."""
+and the scripts' drivers (:131-172), which take model files where the scripts read hpbandster logs:
+
+    eval_models(mode, model_files) -> (reward_list, episode_length_list)      every model's MODEL_AGENTS agents, concatenated model by model
+    eval_base(mode, model_file)    -> (reward_list, episode_length_list)      MODEL_NUM x MODEL_AGENTS agents on the real env of one model's config
+    save_list(mode, config, reward_list, episode_length_list, save_dir)       best_transfer_algo<mode>.pt with the scripts' five keys
+
+Here all agents of a call -- and, through train_test_agents_models / eval_models / eval_base, all models of a mode -- are the chains of ONE
+launch of lenv_ppo_rn_inner_loop (episodes_per_launch None) or of one series of segment launches of lenv_ppo_rn_inner_loop_segment
+(episodes_per_launch episodes each, same bits: docs/notebook_ppo_transfer.md).  The scripts disable the early out and train 3 000 x up to 200
+(MountainCarContinuous) or 5 000 x 1 000 (HalfCheetah) agent steps per agent: one launch of that length could neither be bounded nor report
+progress, so the drivers default to segments.  Modes: '0' = the real env (a RewardEnv of type 0: the real reward passes through), '1' / '2' /
+'5' / '6' = reward envs of that reward_env_type.  Mode '-1' (ppo_icm) is not built.  Reading hpbandster logs is out of scope: the caller
+passes model files."""
 import copy
+import os
 
 import numpy as np
 import torch
@@ -25,6 +36,7 @@ from ..engine import HipNesEngine
 from ..envs.env_factory import EnvFactory
 from ..envs.reward_env import RewardEnv
 
+MODEL_NUM = 10             # models per mode (both scripts)
 MODEL_AGENTS = 10          # agents per model (both scripts)
 MODES = ("0", "1", "2", "5", "6")
 
@@ -39,6 +51,13 @@ PPO_SETTINGS = {
 }
 # what the scripts set solved_reward to ("something big enough to prevent early out triggering")
 SOLVED_REWARD = {"MountainCarContinuous-v0": 100000, "HalfCheetah-v3": 100000}
+SCRIPT_DEFAULT = object()  # episodes_per_launch: DEFAULT_EPISODES_PER_LAUNCH of the env (None instead: one launch from the first episode to the final test)
+# Episodes per segment launch of the drivers: the largest of {1, 2, 5, 10, 20, 50, 100, 200} whose segment stays under about 2 s.  Measured on an MI355X
+# (tools/bench_configs.py ppo_episode_time, profiles/ppo_episode_time.log; 10 models x 10 agents at PPO_SETTINGS, full-length episodes, one workgroup per
+# chain, so a segment lasts as long as its slowest chain).  MountainCarContinuous: 0.0124 s per episode without a learn call, 0.10 to 0.13 s with one, a
+# learn call every tenth episode of a chain: 50 episodes = 50 x 0.0124 + 5 x 0.103 = 1.1 s (100 would be 2.3 s).  HalfCheetah stand-in: 0.047 s per episode,
+# a learn call in each: 20 episodes = 0.94 s (50 would be 2.4 s).  Splitting itself costs 0.1 to 0.7 ms per boundary (docs/notebook_ppo_transfer.md).
+DEFAULT_EPISODES_PER_LAUNCH = {"MountainCarContinuous-v0": 50, "HalfCheetah-v3": 20}
 
 
 def base_config(env_name):
@@ -80,31 +99,94 @@ def _task_config(mode, env, config):
     return cfg, env.env.flat_params()
 
 
-def train_test_agents(mode, env, real_env, config, env_name=None, agents_num=MODEL_AGENTS, seed=0, model_index=0, settings=None, details=False):
+def train_test_agents(mode, env, real_env, config, env_name=None, agents_num=MODEL_AGENTS, seed=0, model_index=0, settings=None, details=False,
+                      episodes_per_launch=None, on_segment=None):
     """Returns (rewards, episode_lengths): rewards[i] = the i-th agent's per-episode real-env test means (PPO.train's first return value),
     episode_lengths[i] = its training episode lengths.  `settings` overrides entries of the script's block (a reduced episode budget);
     `seed` / `model_index` key the agents' counter-RNG streams.  details=True: ((rewards, episode_lengths), launch) with launch = the dict of
-    what ran (inner, task, keys, agent_init, theta, eps, worker, sign) for tests and benchmarks."""
-    results, launch = _launch(mode, [env], real_env, config, env_name, agents_num, seed, [model_index], settings)
+    what ran (inner, task, keys, agent_init, theta, eps, worker, sign) for tests and benchmarks.  episodes_per_launch None: one launch; an
+    integer (or SCRIPT_DEFAULT: the env's DEFAULT_EPISODES_PER_LAUNCH): a series of segment launches of that many episodes, after each of
+    which on_segment(episodes_done, finished_count) is called (engine.PpoInnerLoop.run) -- the same results bit for bit."""
+    results, launch = _launch(mode, [env], real_env, config, env_name, agents_num, seed, [model_index], settings, episodes_per_launch, on_segment)
     return (results[0], launch) if details else results[0]
 
 
 def train_test_agents_models(mode, envs, real_env, config, env_name=None, agents_num=MODEL_AGENTS, seed=0, model_indices=None, settings=None,
-                             details=False):
-    """All models of a mode as ONE launch: len(envs) * agents_num chains, chain (m, i) reading model m's reward net.  Returns
+                             details=False, episodes_per_launch=None, on_segment=None):
+    """All models of a mode as ONE launch (or one series of segment launches: episodes_per_launch / on_segment as in train_test_agents):
+    len(envs) * agents_num chains, chain (m, i) reading model m's reward net.  Returns
     [train_test_agents(mode, envs[m], ..., model_index=model_indices[m]) for m], bit for bit (details=True: that list and the launch)."""
     if model_indices is None:
         model_indices = list(range(len(envs)))
-    results, launch = _launch(mode, list(envs), real_env, config, env_name, agents_num, seed, list(model_indices), settings)
+    results, launch = _launch(mode, list(envs), real_env, config, env_name, agents_num, seed, list(model_indices), settings, episodes_per_launch,
+                              on_segment)
     return (results, launch) if details else results
 
 
-def _launch(mode, envs, real_env, config, env_name, agents_num, seed, model_indices, settings):
+def save_list(mode, config, reward_list, episode_length_list, save_dir, model_num=MODEL_NUM, model_agents=MODEL_AGENTS):
+    """The scripts' result file save_dir/best_transfer_algo<mode>.pt: {'config', 'model_num', 'model_agents', 'reward_list',
+    'episode_length_list'}.  Returns its path."""
+    os.makedirs(save_dir, exist_ok=True)
+    file_name = os.path.join(save_dir, 'best_transfer_algo' + str(mode) + '.pt')
+    save_dict = {}
+    save_dict['config'] = config
+    save_dict['model_num'] = model_num
+    save_dict['model_agents'] = model_agents
+    save_dict['reward_list'] = reward_list
+    save_dict['episode_length_list'] = episode_length_list
+    torch.save(save_dict, file_name)
+    return file_name
+
+
+def eval_models(mode, model_files, save_dir=None, agents_num=MODEL_AGENTS, seed=0, settings=None, episodes_per_launch=SCRIPT_DEFAULT,
+                on_segment=None):
+    """The scripts' eval_models over the given model files (the scripts take the MODEL_NUM best of an hpbandster log): agents_num fresh PPO
+    agents per model on that model's reward env, all models' agents as the chains of one series of segment launches.  Returns
+    (reward_list, episode_length_list), concatenated model by model; with save_dir also writes save_list's file, with the config of the last
+    model like the scripts.  The models of one call must have the same reward-net shapes and env settings (they come from one search)."""
+    _check_mode(mode)
+    loaded = [load_envs_and_config(f) for f in model_files]
+    if not loaded:
+        raise ValueError("eval_models: no model files")
+    real_env, config = loaded[-1][1], loaded[-1][2]
+    results = train_test_agents_models(mode, [l[0] for l in loaded], real_env, config, agents_num=agents_num, seed=seed, settings=settings,
+                                       episodes_per_launch=episodes_per_launch, on_segment=on_segment)
+    return _collect(mode, config, results, save_dir, len(loaded), agents_num)
+
+
+def eval_base(mode, model_file, save_dir=None, model_num=MODEL_NUM, agents_num=MODEL_AGENTS, seed=0, settings=None,
+              episodes_per_launch=SCRIPT_DEFAULT, on_segment=None):
+    """The scripts' eval_base: model_num times agents_num fresh PPO agents on the REAL env of model_file's config (the scripts load the best
+    model model_num times and train on its real env), as the chains of one series of segment launches; repetition m keys its agents as model
+    index m.  Returns (reward_list, episode_length_list); with save_dir also writes save_list's file."""
+    _check_mode(mode)
+    _, real_env, config = load_envs_and_config(model_file)
+    results = train_test_agents_models(mode, [real_env] * int(model_num), real_env, config, agents_num=agents_num, seed=seed, settings=settings,
+                                       episodes_per_launch=episodes_per_launch, on_segment=on_segment)
+    return _collect(mode, config, results, save_dir, int(model_num), agents_num)
+
+
+def _collect(mode, config, results, save_dir, model_num, agents_num):
+    reward_list, episode_length_list = [], []
+    for rewards, episode_lengths in results:
+        reward_list += rewards
+        episode_length_list += episode_lengths
+    if save_dir is not None:
+        save_list(mode, config, reward_list, episode_length_list, save_dir, model_num=model_num, model_agents=int(agents_num))
+    return reward_list, episode_length_list
+
+
+def _check_mode(mode):
     mode = str(mode)
     if mode == "-1":
         raise NotImplementedError("mode -1 (ppo_icm: PPO with an Intrinsic Curiosity Module) is not built")
     if mode not in MODES:
         raise NotImplementedError("transfer_algo: mode '%s' (built: %s)" % (mode, ", ".join(MODES)))
+    return mode
+
+
+def _launch(mode, envs, real_env, config, env_name, agents_num, seed, model_indices, settings, episodes_per_launch=None, on_segment=None):
+    mode = _check_mode(mode)
     env_name = env_name or config["env_name"]
     if env_name != config["env_name"]:
         raise ValueError("env_name '%s' does not match the config's '%s'" % (env_name, config["env_name"]))
@@ -113,6 +195,8 @@ def _launch(mode, envs, real_env, config, env_name, agents_num, seed, model_indi
     if real_env.is_virtual_env():
         raise ValueError("real_env must be the real environment")
     config['agents']['ppo'] = dict(PPO_SETTINGS[env_name], **(settings or {}))       # in place, like the scripts
+    if episodes_per_launch is SCRIPT_DEFAULT:
+        episodes_per_launch = DEFAULT_EPISODES_PER_LAUNCH[env_name]
     M, n_ag = len(envs), int(agents_num)
     cfg, theta = _task_config(mode, envs[0], config)
     engine = HipNesEngine()
@@ -144,7 +228,11 @@ def _launch(mode, envs, real_env, config, env_name, agents_num, seed, model_indi
         g.manual_seed(int(seed) + 1000003 * int(mi))
         rows.append(fresh_agent_init(task.agent_bounds, n_ag, g, dev))
     agent_init = torch.cat(rows)
-    task.scores(inner, theta, eps, worker, sign, keys_t, agent_init)
+    if episodes_per_launch is None:
+        task.scores(inner, theta, eps, worker, sign, keys_t, agent_init)
+    else:
+        agent_init[:, :task.cfg.action_dim] = float(task.cfg.action_std)            # what task.scores writes in front of its launch
+        inner.run(theta, eps, worker, sign, agent_init, rng_keys=keys_t, episodes_per_launch=episodes_per_launch, on_segment=on_segment)
     engine.check_status(inner)
     stats = inner.stats.cpu().numpy()
     ep_mean, ep_len = inner.episode_test_mean.cpu().numpy(), inner.episode_len.cpu().numpy()

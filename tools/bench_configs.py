@@ -283,6 +283,95 @@ def run_dueling_episode_time(name, cfgd, shape, chains=8, episodes=300, lr=1e-3)
     return out
 
 
+def _ppo_loop(cfgd, chains, models=1, seed=0, **over):
+    """A PpoInnerLoop at cfgd's PPO shape with seeded inputs: (inner loop, run arguments, keyword arguments).  models > 1: chain c reads reward net
+    c // (chains / models) through its eps row (theta 0, sign 1), as experiments/transfer_algo.py launches the models of a mode."""
+    import numpy as np
+    from learning_environments_amd import engine
+    from learning_environments_amd.agents.nes_common import linear_init_bounds
+    from learning_environments_amd.config import ppo_cfg_from_config, ppo_layer_dims
+    cfg = ppo_cfg_from_config(cfgd, **over)
+    il = engine.PpoInnerLoop(cfg, chains, want_episode_stats=True, want_final_params=True)
+    rng = np.random.RandomState(seed)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    p_theta = max(1, il.p_theta)
+    nets = (rng.randn(models, p_theta) * 0.1).astype(np.float32)
+    bounds = np.concatenate([np.zeros(cfg.action_dim, np.float32), linear_init_bounds(ppo_layer_dims(cfg))])
+    init = (rng.uniform(-1.0, 1.0, (chains, il.p_agent)) * bounds[None]).astype(np.float32)
+    init[:, :cfg.action_dim] = np.float32(cfg.action_std)
+    keys = dev(np.array([engine.chain_key(11, 0, c, 0) for c in range(chains)], np.uint64).view(np.int64))
+    if models == 1:
+        pos = (dev(nets[0]), None, None, None, dev(init))
+    else:
+        pos = (dev(np.zeros(p_theta, np.float32)), dev(nets), dev((np.arange(chains) // (chains // models)).astype(np.int32)),
+               dev(np.ones(chains, np.float32)), dev(init))
+    return il, pos, dict(rng_keys=keys)
+
+
+def run_ppo_segments(name, cfgd, chains, episodes, splits, runs=7):
+    """The cost of splitting: one workload as one launch of lenv_ppo_rn_inner_loop, as ONE segment launch and as `splits` segment launches of
+    lenv_ppo_rn_inner_loop_segment (with the host's read of the finished words behind each), `runs` timed runs each in alternation after a warm-up
+    of each; medians, spreads (max - min) and ratios to the old entry; the three must agree bit for bit."""
+    il, pos, kw = _ppo_loop(cfgd, chains, train_episodes=episodes)
+    per = -(-episodes // splits)
+    forms = (("old_entry", None), ("one_segment", episodes), ("%d_segments" % splits, per))
+    times, snaps = {k: [] for k, _ in forms}, {}
+    for it in range(runs + 1):
+        for label, epl in forms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            il.run(*pos, episodes_per_launch=epl, **kw)
+            torch.cuda.synchronize()
+            if it:
+                times[label].append(time.perf_counter() - t0)
+            snaps[label] = [t.clone() for t in (il.score, il.stats, il.status, il.episode_test_mean, il.episode_len, il.final_returns, il.final_params)]
+    same = all(all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(snaps["old_entry"], snaps[k])) for k in snaps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    st = il.stats.cpu().numpy()
+    out = dict(config=name, chains=chains, episodes=episodes, runs_each=runs, s_median=med, s_spread={k: max(v) - min(v) for k, v in times.items()},
+               s_samples={k: [round(x, 5) for x in v] for k, v in times.items()}, ratio_to_old_entry={k: med[k] / med["old_entry"] for k in med},
+               ms_per_boundary=1e3 * (med["%d_segments" % splits] - med["old_entry"]) / max(1, splits - 1), bit_identical=bool(same),
+               status_ok=bool(int(il.status.min()) == 0), train_steps_per_chain=float(st[:, 1].mean()), learn_calls_per_chain=float(st[:, 2].mean()),
+               test_steps_per_chain=float(st[:, 3].mean()), workspace_MiB=il.ws_bytes / 2.0 ** 20)
+    print(json.dumps(out))
+    return out
+
+
+def run_ppo_episode_time(name, env_name, episodes, models=10, agents=10, seed=0):
+    """Seconds per episode of the PPO transfer scripts' chains: models x agents chains at experiments/transfer_algo.py's PPO_SETTINGS of the env on a
+    RewardEnv of the real env at full episode length, `episodes` segment launches of ONE episode each, every one timed on its own (the first is
+    the warm-up and is left out); segments in which some chain ran PPO.learn and segments in which none did are reported apart (a segment lasts
+    as long as its slowest chain)."""
+    from learning_environments_amd.experiments import transfer_algo as ta
+    cfgd = ta.base_config(env_name)
+    cfgd["agents"]["ppo"] = dict(ta.PPO_SETTINGS[env_name])
+    cfgd["envs"][env_name]["solved_reward"] = ta.SOLVED_REWARD[env_name]
+    chains = models * agents
+    il, pos, kw = _ppo_loop(cfgd, chains, models=models, seed=seed, train_episodes=episodes)
+    times, learned, calls = [], [], 0
+    for e in range(episodes):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        il.run_segment(*pos, e, e + 1, **kw)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+        now = int(il.stats[:, 2].sum())
+        learned.append(now > calls)
+        calls = now
+    fin, status = il.segment_state()
+    st = il.stats.cpu().numpy()
+    med = lambda v: sorted(v)[len(v) // 2] if v else None
+    with_learn = [t for t, l in list(zip(times, learned))[1:] if l]
+    without = [t for t, l in list(zip(times, learned))[1:] if not l]
+    out = dict(config=name, chains=chains, episodes=episodes, rows_per_learn=il.rows, ppo_epochs=il.cfg.ppo_epochs, max_steps=il.cfg.max_steps,
+               same_action_num=il.cfg.same_action_num, s_per_episode_without_learn=med(without), s_per_episode_with_learn=med(with_learn),
+               s_per_episode_mean=sum(times[1:]) / max(1, len(times) - 1), s_samples=[round(t, 4) for t in times], learn_in_segment=learned,
+               status_ok=bool(int(status.min()) == 0), train_steps_per_chain=float(st[:, 1].mean()), learn_calls_per_chain=float(st[:, 2].mean()),
+               test_steps_per_chain=float(st[:, 3].mean()), workspace_MiB=il.ws_bytes / 2.0 ** 20)
+    print(json.dumps(out))
+    return out
+
+
 import bench  # noqa: E402  (the byte / FLOP models live next to the contract line)
 HBM_PEAK_GBPS, MFMA_F32_PEAK_TFLOPS = bench.HBM_PEAK_GBPS, bench.MFMA_F32_PEAK_TFLOPS
 
@@ -522,6 +611,19 @@ if __name__ == "__main__":
         for script, label in (("vary_hp", "DDQN"), ("algo", "DuelingDDQN f128")):
             for shape in ((64, 1, 32), (192, 2, 96)):
                 run_dueling_episode_time("CartPole RN (200 steps) + %s %dx%d B %d" % ((label,) + shape), _cartpole_transfer_config(script, 300), shape)
+    if "ppo_segments" in which:
+        # the README's PPO shape (default_config_pendulum_reward_env.yaml, PPO 64 x 2 relu, a learn call of 10 epochs x 1 001 rows every five episodes)
+        # on 48 chains, 60 episodes of 200 steps: the old entry, one segment, six segments of ten episodes
+        c = configs.fixed_work(configs.pendulum_reward_env_ppo(16, train_episodes=60), 60)
+        run_ppo_segments("Pendulum RN + PPO 64x2, 48 chains, 60 episodes x 200 steps: 1 launch / 1 segment / 6 segments", c, 48, 60, 6)
+        # the same with ONE chain: no chain waits for another at a boundary, what is left is the cost of splitting itself
+        run_ppo_segments("Pendulum RN + PPO 64x2, 1 chain, 60 episodes x 200 steps: 1 launch / 1 segment / 6 segments", c, 1, 60, 6)
+    if "ppo_episode_time" in which:
+        # the PPO *_transfer_algo scripts' chains: 10 models x 10 agents at the scripts' settings, full-length episodes.  MountainCarContinuous: a
+        # learn call (1 999 rows x 80 epochs) about every tenth episode; the HalfCheetah stand-in: one (1 001 rows x 10 epochs) in every episode
+        # from the second
+        run_ppo_episode_time("MountainCarContinuous RN (999 steps, same_action_num 5) + PPO 64x2, 1 999 rows x 80 epochs", "MountainCarContinuous-v0", 23)
+        run_ppo_episode_time("HalfCheetah-standin RN (1000 steps) + PPO 128x2 tanh, 1 001 rows x 10 epochs", "HalfCheetah-v3", 7)
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
