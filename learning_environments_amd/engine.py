@@ -313,62 +313,36 @@ class _InnerLoopBase(object):
         return self.icm_init
 
 
-_TD3_TRACE = (("action", ("action_dim",), torch.float32), ("state", ("state_dim",), torch.float32),
-              ("next_state", ("state_dim",), torch.float32), ("reward", (), torch.float32))
+class _SegmentedInnerLoop(_InnerLoopBase):
+    """run() of the families whose inner loop also runs as a series of episode segments.  A family states `entry` = (the C entry point of
+    the single launch, the name _lib.check reports it under), `segment_entry`, `prefix` = which of the hp / icm arguments stand between the
+    cfg and run()'s arguments, `resume_words` = the width of its resume record (words 0..2 = next episode, finished, status in every
+    family), and overrides _launch_args for argument checks of its own."""
+    entry = segment_entry = resume_words = None
+    prefix = ()
+    vary = False
+    resume = None                         # the segment launches' records [chains, resume_words], allocated by the first
 
+    def _launch_args(self, theta, eps, worker, sign, agent_init, rng_keys, tapes, segment=False):
+        """_run_args behind the family's own checks (the *_vary agents: agent_init None = the drawn self.agent_init)"""
+        if agent_init is None and self.vary:
+            agent_init = self.agent_init
+        return self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
 
-class InnerLoop(_InnerLoopBase):
-    """Owns the workspace/outputs of lenv_ddqn_se_inner_loop for a fixed (cfg, chains)."""
-    Out, Tapes, final = InnerOut, Tapes, "final_online"
-    trace_spec = (("action", (), torch.int32), ("state", ("state_dim",), torch.float32), ("next_state", ("state_dim",), torch.float32),
-                  ("reward_done", (2,), torch.float32))
-    cfg_type, hp_fields = DdqnCfg, ("batch_size", "q_hidden", "q_layers")
-    num_params_fn, agent_init_fn = "lenv_dueling_num_params", "lenv_dueling_agent_init_hp"
-
-    def __init__(self, cfg, chains, want_episode_stats=True, want_final_online=False, trace_cap=0, vary=False, segments=False):
-        """vary=True: the *_vary agents -- cfg carries the MAXIMAL batch_size / q_hidden / q_layers, every chain runs with its
-        own lr / batch_size / hidden_size / hidden_layer (set_hp) in the GEMM-tiled kernel (lenv_dueling_se_inner_loop_icm).
-        segments=True: the inner loop will run as segment launches (run(episodes_per_launch=) / run_segment), which exist on the
-        GEMM-tiled kernel alone: a cfg the register-resident kernel would take is routed there too (its single launch included; a plain-DQN
-        cfg needs grad_chunk 0, the one sequential batch gradient that kernel computes)."""
-        super().__init__(cfg, chains)
-        L = _lib.lib()
-        # DuelingDDQN, and DDQN whose Critic_DQN the register-resident kernel refuses (hidden_layer >= 2 / wide layers),
-        # run in the GEMM-tiled kernel; `dueling` keeps its name from the first of the two
-        # (a RewardEnv / real-env cfg with an explicit micro-chunk takes the register-resident kernel's RENV instantiations; with grad_chunk 0 --
-        # one sequential batch gradient -- the probe refuses it and the GEMM-tiled kernel runs it)
-        icm = bool(cfg.icm_enabled)                    # ICM agents (ddqn_icm / duelingddqn_icm): GEMM-tiled kernel only
-        self.segments = bool(segments)
-        self.resume = None                              # the segment launches' records [chains, DUELING_RESUME_WORDS], allocated by the first
-        self.dueling = bool(vary) or icm or self.segments or cfg.agent_kind == 1 or (cfg.agent_kind == 0 and L.lenv_ddqn_se_lds_bytes(C.byref(cfg)) <= 0
-                                                                    and L.lenv_dueling_num_params(C.byref(cfg)) > 0)
-        if self.dueling:
-            self.p_agent = self._num_params(cfg)
-            ws_bytes = L.lenv_dueling_se_workspace_bytes(C.byref(cfg), self.chains)
-        else:
-            self.p_agent = mlp_num_params(mlp_desc(cfg.state_dim, cfg.q_hidden, cfg.q_layers, cfg.num_actions, cfg.q_act))
-            ws_bytes = L.lenv_ddqn_se_workspace_bytes(C.byref(cfg), self.chains)
-        self._init_vary(vary)
-        self._init_icm("lenv_icm_num_params")
-        self._alloc_outputs(ws_bytes, want_episode_stats, want_final_online, trace_cap)
+    def _prefix_args(self):
+        return tuple(getattr(self, "_%s_arg" % p)() for p in self.prefix)
 
     def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None, episodes_per_launch=None, on_segment=None):
-        """episodes_per_launch None: one fused inner loop for all chains on the current stream (asynchronous).  An integer: the same inner
-        loop as a series of segment launches of that many episodes each (lenv_dueling_se_inner_loop_segment, always the generic GEMM-tiled
-        kernel: the inner loop must have been built with segments=True; same bits for every split).  After each segment the chains'
-        `finished` words and statuses come to the host (one small copy, the only synchronisation), on_segment(episodes_done,
+        """episodes_per_launch None: one launch from the first episode to the final test (asynchronous).  An integer: the same inner loop
+        as a series of segment launches of that many episodes each (run_segment; same bits for every split).  After each segment the
+        chains' `finished` words and statuses come to the host (one small copy, the only synchronisation), on_segment(episodes_done,
         finished_count) is called if given, then -- after the callback, so that it sees the segment in which a chain failed -- a bad status
         raises as check_status does, and the series stops as soon as every chain is finished.  A cfg without training episodes has no
         segment to run: ValueError (the single launch runs its closing test)."""
-        if agent_init is None and self.vary:
-            agent_init = self.agent_init
         if episodes_per_launch is None:
-            args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
-            if self.dueling:       # the GEMM-tiled kernel: per-chain hyper-parameters and the ICM may be NULL
-                args = (self._hp_arg(), self._icm_arg()) + args
-            fn = "lenv_dueling_se_inner_loop_icm" if self.dueling else "lenv_ddqn_se_inner_loop"
-            rc = getattr(_lib.lib(), fn)(C.byref(self.cfg), *args)
-            _lib.check(rc, "lenv_dueling_se_inner_loop" if self.dueling else "lenv_ddqn_se_inner_loop")
+            fn, label = self.entry
+            args = self._launch_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+            _lib.check(getattr(_lib.lib(), fn)(C.byref(self.cfg), *self._prefix_args(), *args), label)
             return self.score
         step = int(episodes_per_launch)
         if step < 1:
@@ -391,16 +365,12 @@ class InnerLoop(_InnerLoopBase):
     def run_segment(self, theta, eps, worker, sign, agent_init, episode_begin, episode_end, rng_keys=None, tapes=None):
         """Enqueue episodes [episode_begin, episode_end) of every chain (asynchronous).  episode_begin 0 starts afresh; a later segment goes
         on from self.resume and needs the same arguments and an untouched workspace."""
-        if not self.segments:
-            raise ValueError("segment launches need an inner loop built with segments=True (the GEMM-tiled kernel and its workspace)")
-        if agent_init is None and self.vary:
-            agent_init = self.agent_init
+        args = self._launch_args(theta, eps, worker, sign, agent_init, rng_keys, tapes, segment=True)
         if self.resume is None:
-            self.resume = torch.zeros((self.chains, _lib.DUELING_RESUME_WORDS), dtype=torch.int64, device=self.dev)
-        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
-        rc = _lib.lib().lenv_dueling_se_inner_loop_segment(C.byref(self.cfg), self._hp_arg(), self._icm_arg(), *args[:-1], int(episode_begin),
-                                                           int(episode_end), _ptr(self.resume), args[-1])
-        _lib.check(rc, "lenv_dueling_se_inner_loop_segment")
+            self.resume = torch.zeros((self.chains, self.resume_words), dtype=torch.int64, device=self.dev)
+        rc = getattr(_lib.lib(), self.segment_entry)(C.byref(self.cfg), *self._prefix_args(), *args[:-1], int(episode_begin), int(episode_end),
+                                                     _ptr(self.resume), args[-1])
+        _lib.check(rc, self.segment_entry)
         return self.score
 
     def segment_state(self):
@@ -408,6 +378,53 @@ class InnerLoop(_InnerLoopBase):
         the smaller of the record's status and the status output (a refused continuation, -10, is reported there alone)."""
         both = torch.stack((self.resume[:, 1], torch.minimum(self.resume[:, 2], self.status.to(torch.int64)))).cpu()
         return both[0], both[1]
+
+
+_TD3_TRACE = (("action", ("action_dim",), torch.float32), ("state", ("state_dim",), torch.float32),
+              ("next_state", ("state_dim",), torch.float32), ("reward", (), torch.float32))
+
+
+class InnerLoop(_SegmentedInnerLoop):
+    """Owns the workspace/outputs of lenv_ddqn_se_inner_loop for a fixed (cfg, chains)."""
+    Out, Tapes, final = InnerOut, Tapes, "final_online"
+    trace_spec = (("action", (), torch.int32), ("state", ("state_dim",), torch.float32), ("next_state", ("state_dim",), torch.float32),
+                  ("reward_done", (2,), torch.float32))
+    cfg_type, hp_fields = DdqnCfg, ("batch_size", "q_hidden", "q_layers")
+    num_params_fn, agent_init_fn = "lenv_dueling_num_params", "lenv_dueling_agent_init_hp"
+    segment_entry, resume_words = "lenv_dueling_se_inner_loop_segment", _lib.DUELING_RESUME_WORDS
+
+    def __init__(self, cfg, chains, want_episode_stats=True, want_final_online=False, trace_cap=0, vary=False, segments=False):
+        """vary=True: the *_vary agents -- cfg carries the MAXIMAL batch_size / q_hidden / q_layers, every chain runs with its
+        own lr / batch_size / hidden_size / hidden_layer (set_hp) in the GEMM-tiled kernel (lenv_dueling_se_inner_loop_icm).
+        segments=True: the inner loop will run as segment launches (run(episodes_per_launch=) / run_segment), which exist on the
+        GEMM-tiled kernel alone: a cfg the register-resident kernel would take is routed there too (its single launch included; a plain-DQN
+        cfg needs grad_chunk 0, the one sequential batch gradient that kernel computes)."""
+        super().__init__(cfg, chains)
+        L = _lib.lib()
+        # DuelingDDQN, and DDQN whose Critic_DQN the register-resident kernel refuses (hidden_layer >= 2 / wide layers),
+        # run in the GEMM-tiled kernel; `dueling` keeps its name from the first of the two
+        # (a RewardEnv / real-env cfg with an explicit micro-chunk takes the register-resident kernel's RENV instantiations; with grad_chunk 0 --
+        # one sequential batch gradient -- the probe refuses it and the GEMM-tiled kernel runs it)
+        icm = bool(cfg.icm_enabled)                    # ICM agents (ddqn_icm / duelingddqn_icm): GEMM-tiled kernel only
+        self.segments = bool(segments)
+        self.dueling = bool(vary) or icm or self.segments or cfg.agent_kind == 1 or (cfg.agent_kind == 0 and L.lenv_ddqn_se_lds_bytes(C.byref(cfg)) <= 0
+                                                                    and L.lenv_dueling_num_params(C.byref(cfg)) > 0)
+        if self.dueling:       # the GEMM-tiled kernel: per-chain hyper-parameters and the ICM may be NULL
+            self.entry, self.prefix = ("lenv_dueling_se_inner_loop_icm", "lenv_dueling_se_inner_loop"), ("hp", "icm")
+            self.p_agent = self._num_params(cfg)
+            ws_bytes = L.lenv_dueling_se_workspace_bytes(C.byref(cfg), self.chains)
+        else:
+            self.entry = ("lenv_ddqn_se_inner_loop",) * 2
+            self.p_agent = mlp_num_params(mlp_desc(cfg.state_dim, cfg.q_hidden, cfg.q_layers, cfg.num_actions, cfg.q_act))
+            ws_bytes = L.lenv_ddqn_se_workspace_bytes(C.byref(cfg), self.chains)
+        self._init_vary(vary)
+        self._init_icm("lenv_icm_num_params")
+        self._alloc_outputs(ws_bytes, want_episode_stats, want_final_online, trace_cap)
+
+    def _launch_args(self, theta, eps, worker, sign, agent_init, rng_keys, tapes, segment=False):
+        if segment and not self.segments:
+            raise ValueError("segment launches need an inner loop built with segments=True (the GEMM-tiled kernel and its workspace)")
+        return super()._launch_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
 
 
 class QlInnerLoop(_InnerLoopBase):
@@ -486,11 +503,13 @@ class QlSeInnerLoop(_InnerLoopBase):
         return self.score
 
 
-class Td3InnerLoop(_InnerLoopBase):
+class Td3InnerLoop(_SegmentedInnerLoop):
     """Owns the workspace/outputs of lenv_td3_rn_inner_loop for a fixed (cfg, chains)."""
     Out, Tapes, final, trace_spec = Td3Out, Td3Tapes, "final_params", _TD3_TRACE
     cfg_type, hp_fields = Td3Cfg, ("batch_size", "hidden", "layers")
     num_params_fn, agent_init_fn = "lenv_td3_num_params", "lenv_td3_agent_init_hp"
+    entry, prefix = ("lenv_td3_rn_inner_loop_icm", "lenv_td3_rn_inner_loop"), ("hp", "icm")
+    segment_entry, resume_words = "lenv_td3_rn_inner_loop_segment", _lib.TD3_RESUME_WORDS
 
     def __init__(self, cfg, chains, want_episode_stats=True, want_final_params=False, trace_cap=0, vary=False):
         """vary=True: TD3_vary -- cfg carries the maximal batch_size / hidden / layers, every chain runs with its own
@@ -502,60 +521,8 @@ class Td3InnerLoop(_InnerLoopBase):
         self._init_vary(vary)
         self._init_icm("lenv_td3_icm_num_params")       # TD3(icm=True): select_agent "td3_icm" / "td3_icm_vary"
         self.p_theta = cfg.state_dim * cfg.rn_hidden + 2 * cfg.rn_hidden + 1
-        self.resume = None                              # the segment launches' records [chains, TD3_RESUME_WORDS], allocated by the first
         self._alloc_outputs(_lib.lib().lenv_td3_rn_workspace_bytes(C.byref(cfg), self.chains), want_episode_stats, want_final_params,
                             trace_cap)
-
-    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None, episodes_per_launch=None, on_segment=None):
-        """episodes_per_launch None: one launch from the first episode to the final test (asynchronous).  An integer: the same inner loop
-        as a series of segment launches of that many episodes each (lenv_td3_rn_inner_loop_segment, always the generic kernel; same bits
-        for every split).  After each segment the chains' `finished` words and statuses come to the host (one small copy, the only
-        synchronisation), on_segment(episodes_done, finished_count) is called if given, then -- after the callback, so that it sees the segment
-        in which a chain failed -- a bad status raises as check_status does, and the series stops as soon as every chain is finished.  A cfg
-        without training episodes has no segment to run: ValueError (the single launch runs its closing test)."""
-        if agent_init is None and self.vary:
-            agent_init = self.agent_init
-        if episodes_per_launch is None:
-            args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
-            rc = _lib.lib().lenv_td3_rn_inner_loop_icm(C.byref(self.cfg), self._hp_arg(), self._icm_arg(), *args)
-            _lib.check(rc, "lenv_td3_rn_inner_loop")
-            return self.score
-        step = int(episodes_per_launch)
-        if step < 1:
-            raise ValueError("episodes_per_launch must be at least 1")
-        E = self.cfg.train_episodes
-        if E < 1:
-            raise ValueError("episodes_per_launch needs a cfg with at least one training episode")
-        for begin in range(0, E, step):
-            end = min(E, begin + step)
-            self.run_segment(theta, eps, worker, sign, agent_init, begin, end, rng_keys=rng_keys, tapes=tapes)
-            finished, st = self.segment_state()
-            if on_segment is not None:
-                on_segment(end, int(finished.sum()))
-            if int(st.min()) != 0:
-                raise _lib.LenvError("inner loop reported status %s" % st.tolist())
-            if int(finished.min()) == 1:
-                break
-        return self.score
-
-    def run_segment(self, theta, eps, worker, sign, agent_init, episode_begin, episode_end, rng_keys=None, tapes=None):
-        """Enqueue episodes [episode_begin, episode_end) of every chain (asynchronous).  episode_begin 0 starts afresh; a later segment goes
-        on from self.resume and needs the same arguments and an untouched workspace."""
-        if agent_init is None and self.vary:
-            agent_init = self.agent_init
-        if self.resume is None:
-            self.resume = torch.zeros((self.chains, _lib.TD3_RESUME_WORDS), dtype=torch.int64, device=self.dev)
-        args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
-        rc = _lib.lib().lenv_td3_rn_inner_loop_segment(C.byref(self.cfg), self._hp_arg(), self._icm_arg(), *args[:-1], int(episode_begin),
-                                                       int(episode_end), _ptr(self.resume), args[-1])
-        _lib.check(rc, "lenv_td3_rn_inner_loop_segment")
-        return self.score
-
-    def segment_state(self):
-        """(finished [chains], status [chains]) on the host after the segments enqueued so far (synchronises): the record's finished word and
-        the smaller of the record's status and the status output (a refused continuation, -10, is reported there alone)."""
-        both = torch.stack((self.resume[:, 1], torch.minimum(self.resume[:, 2], self.status.to(torch.int64)))).cpu()
-        return both[0], both[1]
 
 
 class Td3DiscreteInnerLoop(_InnerLoopBase):
@@ -600,13 +567,15 @@ class Td3DiscreteInnerLoop(_InnerLoopBase):
         return self.score
 
 
-class PpoInnerLoop(_InnerLoopBase):
+class PpoInnerLoop(_SegmentedInnerLoop):
     """Owns the workspace/outputs of lenv_ppo_rn_inner_loop (PPO on a RewardEnv over a continuous real env) for a fixed (cfg, chains).
     learn_cap > 0: the step at which each of the first learn_cap PPO.learn calls fired and the parameters after it are recorded
     (learn_step [chains, learn_cap], learn_params [chains, learn_cap, P])."""
     Out, Tapes, final = PpoOut, PpoTapes, "final_params"
     trace_spec = _TD3_TRACE + (("done", (), torch.float32),)
     cfg_type, num_params_fn = PpoCfg, "lenv_ppo_num_params"
+    entry = ("lenv_ppo_rn_inner_loop",) * 2
+    segment_entry, resume_words = "lenv_ppo_rn_inner_loop_segment", _lib.PPO_RESUME_WORDS
 
     def __init__(self, cfg, chains, want_episode_stats=True, want_final_params=False, trace_cap=0, learn_cap=0):
         super().__init__(cfg, chains)
@@ -617,7 +586,6 @@ class PpoInnerLoop(_InnerLoopBase):
         self.p_theta = _count("lenv_ppo_rn_num_params", C.byref(cfg))
         self.learn_cap = int(learn_cap)
         self.learn_step = self.learn_params = None
-        self.resume = None                              # the segment launches' records [chains, PPO_RESUME_WORDS], allocated by the first
         if self.learn_cap:
             self.learn_step = torch.zeros((self.chains, self.learn_cap), dtype=torch.int32, device=self.dev)
             self.learn_params = torch.zeros((self.chains, self.learn_cap, self.p_agent), dtype=torch.float32, device=self.dev)
@@ -629,51 +597,8 @@ class PpoInnerLoop(_InnerLoopBase):
             raise ValueError("theta must hold %d reward-net parameters" % self.p_theta)
         return args
 
-    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None, episodes_per_launch=None, on_segment=None):
-        """episodes_per_launch None: one launch from the first episode to the final test (asynchronous).  An integer: the same inner loop
-        as a series of segment launches of that many episodes each (lenv_ppo_rn_inner_loop_segment; same bits for every split).  After each
-        segment the chains' `finished` words and statuses come to the host (one small copy, the only synchronisation),
-        on_segment(episodes_done, finished_count) is called if given, then -- after the callback, so that it sees the segment in which a
-        chain failed -- a bad status raises as check_status does, and the series stops as soon as every chain is finished.  A cfg without
-        training episodes has no segment to run: ValueError (the single launch runs its closing test)."""
-        if episodes_per_launch is None:
-            rc = _lib.lib().lenv_ppo_rn_inner_loop(C.byref(self.cfg), *self._ppo_args(theta, eps, worker, sign, agent_init, rng_keys, tapes))
-            _lib.check(rc, "lenv_ppo_rn_inner_loop")
-            return self.score
-        step = int(episodes_per_launch)
-        if step < 1:
-            raise ValueError("episodes_per_launch must be at least 1")
-        E = self.cfg.train_episodes
-        if E < 1:
-            raise ValueError("episodes_per_launch needs a cfg with at least one training episode")
-        for begin in range(0, E, step):
-            end = min(E, begin + step)
-            self.run_segment(theta, eps, worker, sign, agent_init, begin, end, rng_keys=rng_keys, tapes=tapes)
-            finished, st = self.segment_state()
-            if on_segment is not None:
-                on_segment(end, int(finished.sum()))
-            if int(st.min()) != 0:
-                raise _lib.LenvError("inner loop reported status %s" % st.tolist())
-            if int(finished.min()) == 1:
-                break
-        return self.score
-
-    def run_segment(self, theta, eps, worker, sign, agent_init, episode_begin, episode_end, rng_keys=None, tapes=None):
-        """Enqueue episodes [episode_begin, episode_end) of every chain (asynchronous).  episode_begin 0 starts afresh; a later segment goes
-        on from self.resume and needs the same arguments and an untouched workspace."""
-        if self.resume is None:
-            self.resume = torch.zeros((self.chains, _lib.PPO_RESUME_WORDS), dtype=torch.int64, device=self.dev)
-        args = self._ppo_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
-        rc = _lib.lib().lenv_ppo_rn_inner_loop_segment(C.byref(self.cfg), *args[:-1], int(episode_begin), int(episode_end), _ptr(self.resume),
-                                                       args[-1])
-        _lib.check(rc, "lenv_ppo_rn_inner_loop_segment")
-        return self.score
-
-    def segment_state(self):
-        """(finished [chains], status [chains]) on the host after the segments enqueued so far (synchronises): the record's finished word and
-        the smaller of the record's status and the status output (a refused continuation, -10, is reported there alone)."""
-        both = torch.stack((self.resume[:, 1], torch.minimum(self.resume[:, 2], self.status.to(torch.int64)))).cpu()
-        return both[0], both[1]
+    def _launch_args(self, theta, eps, worker, sign, agent_init, rng_keys, tapes, segment=False):
+        return self._ppo_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
 
 
 def rn_shape_population(cfg, theta, eps, worker, sign, next_state, reward, chains=1):

@@ -26,14 +26,13 @@ passes model files."""
 import copy
 import os
 
-import numpy as np
 import torch
 
+from . import transfer_common
 from .. import configs
 from ..agents import tasks
-from ..agents.nes_common import chain_keys, fresh_agent_init
+from ..agents.nes_common import fresh_agent_init
 from ..engine import HipNesEngine
-from ..envs.env_factory import EnvFactory
 from ..envs.reward_env import RewardEnv
 
 MODEL_NUM = 10             # models per mode (both scripts)
@@ -51,7 +50,7 @@ PPO_SETTINGS = {
 }
 # what the scripts set solved_reward to ("something big enough to prevent early out triggering")
 SOLVED_REWARD = {"MountainCarContinuous-v0": 100000, "HalfCheetah-v3": 100000}
-SCRIPT_DEFAULT = object()  # episodes_per_launch: DEFAULT_EPISODES_PER_LAUNCH of the env (None instead: one launch from the first episode to the final test)
+SCRIPT_DEFAULT = transfer_common.SCRIPT_DEFAULT  # episodes_per_launch: DEFAULT_EPISODES_PER_LAUNCH of the env
 # Episodes per segment launch of the drivers: the largest of {1, 2, 5, 10, 20, 50, 100, 200} whose segment stays under about 2 s.  Measured on an MI355X
 # (tools/bench_configs.py ppo_episode_time, profiles/ppo_episode_time.log; 10 models x 10 agents at PPO_SETTINGS, full-length episodes, one workgroup per
 # chain, so a segment lasts as long as its slowest chain).  MountainCarContinuous: 0.0124 s per episode without a learn call, 0.10 to 0.13 s with one, a
@@ -73,16 +72,7 @@ def base_config(env_name):
 
 
 def load_envs_and_config(model_file):
-    save_dict = torch.load(model_file, map_location="cpu")
-    config = save_dict['config']
-    config['device'] = 'cpu'
-    env_name = config['env_name']
-    config['envs'][env_name]['solved_reward'] = SOLVED_REWARD.get(env_name, 100000)
-    env_factory = EnvFactory(config=config)
-    reward_env = env_factory.generate_reward_env()
-    reward_env.load_state_dict(save_dict['model'])
-    real_env = env_factory.generate_real_env()
-    return reward_env, real_env, config
+    return transfer_common.load_envs_and_config(model_file, lambda env_name: SOLVED_REWARD.get(env_name, 100000))
 
 
 def _task_config(mode, env, config):
@@ -204,24 +194,10 @@ def _launch(mode, envs, real_env, config, env_name, agents_num, seed, model_indi
     task = tasks.select_task(cfg, engine, envs[0])
     chains = M * n_ag
     inner = task.make_inner(chains, want_episode_stats=True)
-    keys = np.concatenate([chain_keys(int(seed), int(mi), np.arange(n_ag), np.zeros(n_ag, np.int64)) for mi in model_indices])
-    keys_t = torch.from_numpy(keys.view(np.int64)).to(dev)
+    keys, keys_t = transfer_common.model_chain_keys(seed, model_indices, n_ag, dev)
     p_theta = max(inner.p_theta, 1)
-    if theta is None or M == 1:
-        # the real env, or one model: its weights are theta itself, sign 0 (the unperturbed checkpoint)
-        theta = torch.zeros(p_theta, dtype=torch.float32, device=dev) if theta is None else theta.to(device=dev, dtype=torch.float32)
-        worker = torch.zeros(chains, dtype=torch.int32, device=dev)
-        sign = torch.zeros(chains, dtype=torch.float32, device=dev)
-        eps = torch.zeros((1, theta.numel()), dtype=torch.float32, device=dev)
-    else:
-        # several models: chain (m, i) reads 0 + 1 * weights[m] (exact; a stored -0.0 becomes +0.0, which no sum downstream can tell apart)
-        thetas = [theta] + [_task_config(mode, e, config)[1] for e in envs[1:]]
-        if any(t.numel() != theta.numel() for t in thetas):
-            raise ValueError("train_test_agents_models: the models of one launch must have the same shapes")
-        eps = torch.stack([t.to(device=dev, dtype=torch.float32) for t in thetas])
-        theta = torch.zeros_like(eps[0])
-        worker = torch.arange(chains, dtype=torch.int32, device=dev) // n_ag
-        sign = torch.ones(chains, dtype=torch.float32, device=dev)
+    others = lambda: [_task_config(mode, e, config)[1] for e in envs[1:]]
+    theta, eps, worker, sign = transfer_common.models_as_population(theta, others, chains, n_ag, p_theta, dev)
     rows = []
     for mi in model_indices:
         g = torch.Generator(device=dev)
@@ -234,9 +210,5 @@ def _launch(mode, envs, real_env, config, env_name, agents_num, seed, model_indi
         agent_init[:, :task.cfg.action_dim] = float(task.cfg.action_std)            # what task.scores writes in front of its launch
         inner.run(theta, eps, worker, sign, agent_init, rng_keys=keys_t, episodes_per_launch=episodes_per_launch, on_segment=on_segment)
     engine.check_status(inner)
-    stats = inner.stats.cpu().numpy()
-    ep_mean, ep_len = inner.episode_test_mean.cpu().numpy(), inner.episode_len.cpu().numpy()
-    rewards = [ep_mean[i, :int(stats[i, 0])].tolist() for i in range(chains)]
-    lengths = [ep_len[i, :int(stats[i, 0])].tolist() for i in range(chains)]
     launch = dict(inner=inner, task=task, keys=keys, agent_init=agent_init, theta=theta, eps=eps, worker=worker, sign=sign)
-    return [(rewards[m * n_ag:(m + 1) * n_ag], lengths[m * n_ag:(m + 1) * n_ag]) for m in range(M)], launch
+    return transfer_common.inner_results(inner, n_ag), launch

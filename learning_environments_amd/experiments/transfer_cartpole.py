@@ -25,12 +25,12 @@ import copy
 import numpy as np
 import torch
 
+from . import transfer_common
 from .. import _lib, configs
 from ..agents import vary
-from ..agents.nes_common import chain_keys, linear_init_bounds
+from ..agents.nes_common import linear_init_bounds
 from ..config import ddqn_cfg_from_config, icm_layer_dims
 from ..engine import HipNesEngine, mlp_desc, mlp_num_params
-from ..envs.env_factory import EnvFactory
 from ..envs.reward_env import RewardEnv
 
 ENV_NAME = "CartPole-v0"
@@ -50,7 +50,7 @@ DUELING_SETTINGS = dict(test_episodes=1, train_episodes=1000, print_rate=100, lr
 # the "optimized ICM HPs" both scripts leave switched on
 ICM_SETTINGS = dict(beta=0.05, eta=0.03, feature_dim=32, hidden_size=128, lr=1e-5)
 SOLVED_REWARD = 100000     # "something big enough to prevent early out triggering"
-SCRIPT_DEFAULT = object()  # episodes_per_launch: DEFAULT_EPISODES_PER_LAUNCH of the script (None instead: one launch from the first episode to the final test)
+SCRIPT_DEFAULT = transfer_common.SCRIPT_DEFAULT  # episodes_per_launch: DEFAULT_EPISODES_PER_LAUNCH of the script
 # Episodes per segment launch.  Measured on an MI355X (tools/bench_configs.py dueling_episode_time, profiles/dueling_episode_time.log; one workgroup per
 # chain, so a segment takes what its slowest chain takes): a full-length learning episode (200 agent steps, each with a learn step, and the 200-step
 # test episode behind it) takes 0.0163 s at the vary_hp script's nominal chain (DDQN 64 x 1, batch 32) and 0.0671 s at the slowest chain its draw can
@@ -69,15 +69,7 @@ def base_config():
 
 
 def load_envs_and_config(model_file):
-    save_dict = torch.load(model_file, map_location="cpu")
-    config = save_dict['config']
-    config['device'] = 'cpu'
-    config['envs'][ENV_NAME]['solved_reward'] = SOLVED_REWARD
-    env_factory = EnvFactory(config=config)
-    reward_env = env_factory.generate_reward_env()
-    reward_env.load_state_dict(save_dict['model'])
-    real_env = env_factory.generate_real_env()
-    return reward_env, real_env, config
+    return transfer_common.load_envs_and_config(model_file, SOLVED_REWARD)
 
 
 def vary_hp(config, rng):
@@ -179,8 +171,7 @@ def _launch(mode, envs, real_env, config, script, agents_num, seed, model_indice
     section = cfgd["agents"][SECTION[script]]
     engine = HipNesEngine()
     dev = engine.device
-    keys = np.concatenate([chain_keys(int(seed), int(mi), np.arange(n_ag), np.zeros(n_ag, np.int64)) for mi in model_indices])
-    keys_t = torch.from_numpy(keys.view(np.int64)).to(dev)
+    keys, keys_t = transfer_common.model_chain_keys(seed, model_indices, n_ag, dev)
     own = {k: section[k] for k in ("lr", "batch_size", "hidden_size", "hidden_layer")}
     if hps is not None:
         if len(hps) != n_ag:
@@ -203,20 +194,8 @@ def _launch(mode, envs, real_env, config, script, agents_num, seed, model_indice
                  [h["hidden_layer"] for h in chain_hp])
     # the kernel stages the reward net it is given: state_dim -> hidden -> 1, for type 0 RewardEnv.build_reward_net's 1-input dummy (never evaluated)
     p_theta = mlp_num_params(mlp_desc(1 if cfg.reward_env_type == 0 else cfg.state_dim, cfg.se_hidden, cfg.se_layers, 1, cfg.se_act))
-    if theta is None or M == 1:
-        theta = torch.zeros(p_theta, dtype=torch.float32, device=dev) if theta is None else theta.to(device=dev, dtype=torch.float32)
-        worker = torch.zeros(chains, dtype=torch.int32, device=dev)
-        sign = torch.zeros(chains, dtype=torch.float32, device=dev)
-        eps = torch.zeros((1, theta.numel()), dtype=torch.float32, device=dev)
-    else:
-        # several models: chain (m, i) reads 0 + 1 * weights[m] (exact; a stored -0.0 becomes +0.0, which no sum downstream can tell apart)
-        thetas = [theta] + [_task_config(mode, e, config, script)[1] for e in envs[1:]]
-        if any(t.numel() != theta.numel() for t in thetas):
-            raise ValueError("train_test_agents_models: the models of one launch must have the same shapes")
-        eps = torch.stack([t.to(device=dev, dtype=torch.float32) for t in thetas])
-        theta = torch.zeros_like(eps[0])
-        worker = torch.arange(chains, dtype=torch.int32, device=dev) // n_ag
-        sign = torch.ones(chains, dtype=torch.float32, device=dev)
+    others = lambda: [_task_config(mode, e, config, script)[1] for e in envs[1:]]
+    theta, eps, worker, sign = transfer_common.models_as_population(theta, others, chains, n_ag, p_theta, dev)
     if theta.numel() != p_theta:
         raise ValueError("the reward net has %d parameters, the config describes one of %d" % (theta.numel(), p_theta))
     inner.draw_agent_init(keys_t)                         # fresh agents at every chain's own shapes, fresh ICMs
@@ -224,19 +203,9 @@ def _launch(mode, envs, real_env, config, script, agents_num, seed, model_indice
         inner.draw_icm_init(keys_t, torch.from_numpy(linear_init_bounds(icm_layer_dims(cfg))).to(dev))
     tapes = None
     if replay is not None:                                # the recorded agents (and ICMs) instead of fresh ones, the recorded draws instead of the chains' own
-        for name, rows in (("agent_init", replay["agent_init"]), ("icm_init", replay.get("icm_init"))):
-            if rows is not None and getattr(inner, name) is not None:
-                buf = getattr(inner, name)
-                buf.zero_()
-                for i, r in enumerate(rows):
-                    for m in range(M):
-                        buf[m * n_ag + i, :len(r)] = torch.as_tensor(np.asarray(r, np.float32)).to(dev)
+        transfer_common.replay_agents(inner, replay, n_ag, M, dev)
         tapes = _replay_tapes(replay, cfg, n_ag, M, dev)
     inner.run(theta, eps, worker, sign, None, rng_keys=keys_t, tapes=tapes, episodes_per_launch=episodes_per_launch, on_segment=on_segment)
     engine.check_status(inner)
-    stats = inner.stats.cpu().numpy()
-    ep_mean, ep_len = inner.episode_test_mean.cpu().numpy(), inner.episode_len.cpu().numpy()
-    rewards = [ep_mean[i, :int(stats[i, 0])].tolist() for i in range(chains)]
-    lengths = [ep_len[i, :int(stats[i, 0])].tolist() for i in range(chains)]
     launch = dict(inner=inner, cfg=cfg, keys=keys, hps=chain_hp, theta=theta, eps=eps, worker=worker, sign=sign)
-    return [(rewards[m * n_ag:(m + 1) * n_ag], lengths[m * n_ag:(m + 1) * n_ag]) for m in range(M)], launch
+    return transfer_common.inner_results(inner, n_ag), launch

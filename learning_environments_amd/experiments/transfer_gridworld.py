@@ -24,11 +24,10 @@ import copy
 import numpy as np
 import torch
 
+from . import transfer_common
 from .. import _lib
 from ..agents import tasks, vary
-from ..agents.nes_common import chain_keys
 from ..engine import HipNesEngine
-from ..envs.env_factory import EnvFactory
 from ..envs.reward_env import RewardEnv
 
 MODEL_NUM = 10             # models per mode (both scripts)
@@ -44,15 +43,7 @@ SOLVED_REWARD = 100000     # "something big enough to prevent early out triggeri
 
 
 def load_envs_and_config(model_file):
-    save_dict = torch.load(model_file, map_location="cpu")
-    config = save_dict['config']
-    config['device'] = 'cpu'
-    config['envs'][config['env_name']]['solved_reward'] = SOLVED_REWARD
-    env_factory = EnvFactory(config=config)
-    reward_env = env_factory.generate_reward_env()
-    reward_env.load_state_dict(save_dict['model'])
-    real_env = env_factory.generate_real_env()
-    return reward_env, real_env, config
+    return transfer_common.load_envs_and_config(model_file, SOLVED_REWARD)
 
 
 def vary_hp(config, units):
@@ -144,8 +135,7 @@ def _launch(mode, envs, real_env, config, script, agents_num, seed, model_indice
         tapes = dict(eps_uniform=_tape_tensor(replay["tapes"]["eps_uniform"], np.float64, dev),
                      rand_action=_tape_tensor(replay["tapes"]["rand_action"], np.int32, dev))
     inner = task.make_inner(chains, want_episode_stats=True)
-    keys = np.concatenate([chain_keys(int(seed), int(mi), np.arange(n_ag), np.zeros(n_ag, np.int64)) for mi in model_indices])
-    keys_t = torch.from_numpy(keys.view(np.int64)).to(dev)
+    keys, keys_t = transfer_common.model_chain_keys(seed, model_indices, n_ag, dev)
     # every agent's own alpha / gamma: a recorded draw, or (the vary_hp script) vary_hp's on the chain key's STREAM_VARY_HP draws 0 and 1
     hp = None
     if replay is not None and replay.get("hp") is not None:
@@ -158,26 +148,9 @@ def _launch(mode, envs, real_env, config, script, agents_num, seed, model_indice
     if hp is not None:
         inner.set_hp([h["alpha"] for h in hp], [h["gamma"] for h in hp])
     p_theta = max(inner.p_theta, 1)
-    if theta is None or M == 1:
-        # the real env, or one model: its weights are theta itself, sign 0 (the unperturbed checkpoint)
-        theta = torch.zeros(p_theta, dtype=torch.float32, device=dev) if theta is None else theta.to(device=dev, dtype=torch.float32)
-        worker = torch.zeros(chains, dtype=torch.int32, device=dev)
-        sign = torch.zeros(chains, dtype=torch.float32, device=dev)
-        eps = torch.zeros((1, theta.numel()), dtype=torch.float32, device=dev)
-    else:
-        # several models: chain (m, i) reads 0 + 1 * weights[m] (exact; a stored -0.0 becomes +0.0, which no sum downstream can tell apart)
-        thetas = [theta] + [_task_config(mode, e, config, script)[1] for e in envs[1:]]
-        if any(t.numel() != theta.numel() for t in thetas):
-            raise ValueError("train_test_agents_models: the models of one launch must have the same shapes")
-        eps = torch.stack([t.to(device=dev, dtype=torch.float32) for t in thetas])
-        theta = torch.zeros_like(eps[0])
-        worker = torch.arange(chains, dtype=torch.int32, device=dev) // n_ag
-        sign = torch.ones(chains, dtype=torch.float32, device=dev)
+    others = lambda: [_task_config(mode, e, config, script)[1] for e in envs[1:]]
+    theta, eps, worker, sign = transfer_common.models_as_population(theta, others, chains, n_ag, p_theta, dev)
     inner.run(theta, eps, worker, sign, rng_keys=keys_t, tapes=tapes)
     engine.check_status(inner)
-    stats = inner.stats.cpu().numpy()
-    ep_mean, ep_len = inner.episode_test_mean.cpu().numpy(), inner.episode_len.cpu().numpy()
-    rewards = [ep_mean[i, :int(stats[i, 0])].tolist() for i in range(chains)]
-    lengths = [ep_len[i, :int(stats[i, 0])].tolist() for i in range(chains)]
     launch = dict(inner=inner, task=task, keys=keys, hp=hp, theta=theta, eps=eps, worker=worker, sign=sign)
-    return [(rewards[m * n_ag:(m + 1) * n_ag], lengths[m * n_ag:(m + 1) * n_ag]) for m in range(M)], launch
+    return transfer_common.inner_results(inner, n_ag), launch

@@ -24,11 +24,10 @@ import copy
 import numpy as np
 import torch
 
+from . import transfer_common
 from .. import configs
 from ..agents import tasks, vary
-from ..agents.nes_common import chain_keys
 from ..engine import HipNesEngine
-from ..envs.env_factory import EnvFactory
 from ..envs.reward_env import RewardEnv
 
 MODEL_NUM = 10             # models per mode (both scripts)
@@ -49,7 +48,7 @@ ICM_SETTINGS = {
     "HalfCheetah-v3": dict(beta=0.001, eta=0.1, feature_dim=32, hidden_size=128, lr=1e-5),
 }
 SOLVED_REWARD = 100000     # "something big enough to prevent early out triggering"
-SCRIPT_DEFAULT = object()  # episodes_per_launch: DEFAULT_EPISODES_PER_LAUNCH of the env (None instead: one launch from the first episode to the final test)
+SCRIPT_DEFAULT = transfer_common.SCRIPT_DEFAULT  # episodes_per_launch: DEFAULT_EPISODES_PER_LAUNCH of the env
 # Episodes per segment launch.  Measured on an MI355X (tools/bench_configs.py td3_episode_time, profiles/td3_episode_time.log; one workgroup per chain, so
 # the time of a segment is the time of its slowest chain): a full-length learning episode of the slowest drawable chain (384 x 3, batch 768) takes 13.0 s
 # on MountainCarContinuous (500 agent steps) and 26.3 s on the HalfCheetah stand-in (1 000 steps); the nominal chain (128 x 2, batch 256) 0.42 s / 0.91 s.
@@ -68,15 +67,7 @@ def base_config(env_name):
 
 
 def load_envs_and_config(model_file):
-    save_dict = torch.load(model_file, map_location="cpu")
-    config = save_dict['config']
-    config['device'] = 'cpu'
-    config['envs'][config['env_name']]['solved_reward'] = SOLVED_REWARD
-    env_factory = EnvFactory(config=config)
-    reward_env = env_factory.generate_reward_env()
-    reward_env.load_state_dict(save_dict['model'])
-    real_env = env_factory.generate_real_env()
-    return reward_env, real_env, config
+    return transfer_common.load_envs_and_config(model_file, SOLVED_REWARD)
 
 
 def vary_hp(config, rng):
@@ -179,43 +170,20 @@ def _launch(mode, envs, real_env, config, env_name, agents_num, seed, model_indi
             theta = torch.as_tensor(replay["theta"], dtype=torch.float32)
     chains = M * n_ag
     inner = task.make_inner(chains, want_episode_stats=True)
-    keys = np.concatenate([chain_keys(int(seed), int(mi), np.arange(n_ag), np.zeros(n_ag, np.int64)) for mi in model_indices])
-    keys_t = torch.from_numpy(keys.view(np.int64)).to(dev)
+    keys, keys_t = transfer_common.model_chain_keys(seed, model_indices, n_ag, dev)
     if hps is not None:
         if len(hps) != n_ag:
             raise ValueError("hps: need %d entries, one per agent" % n_ag)
         task.fixed_hp = [dict(h) for h in hps] * M
     p_theta = max(inner.p_theta, 1)
-    if theta is None or M == 1:
-        theta = torch.zeros(p_theta, dtype=torch.float32, device=dev) if theta is None else theta.to(device=dev, dtype=torch.float32)
-        worker = torch.zeros(chains, dtype=torch.int32, device=dev)
-        sign = torch.zeros(chains, dtype=torch.float32, device=dev)
-        eps = torch.zeros((1, theta.numel()), dtype=torch.float32, device=dev)
-    else:
-        # several models: chain (m, i) reads 0 + 1 * weights[m] (exact; a stored -0.0 becomes +0.0, which no sum downstream can tell apart)
-        thetas = [theta] + [_task_config(mode, e, config)[1] for e in envs[1:]]
-        if any(t.numel() != theta.numel() for t in thetas):
-            raise ValueError("train_test_agents_models: the models of one launch must have the same shapes")
-        eps = torch.stack([t.to(device=dev, dtype=torch.float32) for t in thetas])
-        theta = torch.zeros_like(eps[0])
-        worker = torch.arange(chains, dtype=torch.int32, device=dev) // n_ag
-        sign = torch.ones(chains, dtype=torch.float32, device=dev)
+    others = lambda: [_task_config(mode, e, config)[1] for e in envs[1:]]
+    theta, eps, worker, sign = transfer_common.models_as_population(theta, others, chains, n_ag, p_theta, dev)
     task._fresh_agents(inner, keys_t)               # the draws (or hps), fresh agents at every chain's own shapes, fresh ICMs
     tapes = None
     if replay is not None:                          # the recorded agents (and ICMs) instead of fresh ones, the recorded draws instead of the chains' own
-        for name, rows in (("agent_init", replay["agent_init"]), ("icm_init", replay.get("icm_init"))):
-            if rows is not None and getattr(inner, name) is not None:
-                buf = getattr(inner, name)
-                buf.zero_()
-                for i, r in enumerate(rows):
-                    for m in range(M):
-                        buf[m * n_ag + i, :len(r)] = torch.as_tensor(np.asarray(r, np.float32)).to(dev)
+        transfer_common.replay_agents(inner, replay, n_ag, M, dev)
         tapes = _replay_tapes(replay, task.cfg, n_ag, M, dev)
     inner.run(theta, eps, worker, sign, None, rng_keys=keys_t, tapes=tapes, episodes_per_launch=episodes_per_launch, on_segment=on_segment)
     engine.check_status(inner)
-    stats = inner.stats.cpu().numpy()
-    ep_mean, ep_len = inner.episode_test_mean.cpu().numpy(), inner.episode_len.cpu().numpy()
-    rewards = [ep_mean[i, :int(stats[i, 0])].tolist() for i in range(chains)]
-    lengths = [ep_len[i, :int(stats[i, 0])].tolist() for i in range(chains)]
     launch = dict(inner=inner, task=task, keys=keys, hps=task.last_hp, theta=theta, eps=eps, worker=worker, sign=sign)
-    return [(rewards[m * n_ag:(m + 1) * n_ag], lengths[m * n_ag:(m + 1) * n_ag]) for m in range(M)], launch
+    return transfer_common.inner_results(inner, n_ag), launch

@@ -13,6 +13,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from segments_common import SENTINEL, _poison_finished, same_bits as _same_bits, single, snapshot, split  # noqa: E402
 from test_gpu_parity import _inner_cfg, _lib_cfg_copy, dev, eng, orc  # noqa: E402,F401  (cfg helpers and fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -29,18 +30,7 @@ OUT_NAMES = ("score", "stats", "status", "episode_test_mean", "episode_len", "fi
 
 
 def _snapshot(il):
-    torch.cuda.synchronize()
-    out = {k: getattr(il, k).cpu().numpy().copy() for k in OUT_NAMES}
-    out.update({"trace_" + k: v.cpu().numpy().copy() for k, v in il.trace.items()})
-    if il.icm:
-        out["icm_final"] = il.icm_final.cpu().numpy().copy()
-    return out
-
-
-def _same_bits(a, b, what):
-    for k in a:
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, (what, k)
-        assert a[k].tobytes() == b[k].tobytes(), (what, k, np.argwhere(a[k] != b[k])[:4].tolist())
+    return snapshot(il, OUT_NAMES)
 
 
 def _config(family, icm, virtual, agent_over, solved):
@@ -124,18 +114,11 @@ class Case(object):
 
     def single(self, eng):
         il = self.inner(eng, segments=False)             # lenv_dueling_se_inner_loop_icm (hp given: the generic kernel)
-        pos, kw = self.args()
-        il.run(*pos, **kw)
-        return il, _snapshot(il)
+        return il, single(il, *self.args(), OUT_NAMES)
 
     def split(self, eng, segments, between=None):
         il = self.inner(eng)
-        pos, kw = self.args()
-        for b, e in segments:
-            il.run_segment(*pos, b, e, **kw)
-            if between is not None:
-                between(il, b, e)
-        return il, _snapshot(il)
+        return il, split(il, *self.args(), segments, OUT_NAMES, between=between)
 
 
 def _check_vs_oracle(case, orc, snap, oracles=None):
@@ -184,26 +167,9 @@ def test_every_split_equals_the_single_launch_and_the_oracle(eng, orc, name):
         assert np.array_equal(rec[:, 7], ref["stats"][:, 1]) and np.array_equal(rec[:, 10], rec[:, 7]) and not rec[:, 16:].any()
 
 
-SENTINEL = 77
 # chain keys of the early-out case: with this seed the oracle's means (computed in the test, on the CPU) leave a solved_reward for which chains
 # leave in episode 2, in episode 3 (the middle segment), in episode 5, and never
 EARLY_KEY_SEED = 66
-
-
-def _poison_finished(names):
-    """between-segments hook: the output rows of chains that are finished get a sentinel (the caller owns the outputs; the workspace is left
-    alone), so that a later segment that writes them again -- even the same values -- shows."""
-    seen = {}
-
-    def hook(il, b, e):
-        torch.cuda.synchronize()
-        for c in np.flatnonzero(il.resume[:, 1].cpu().numpy() == 1):
-            if int(c) in seen:
-                continue
-            seen[int(c)] = {k: getattr(il, k)[c].cpu().numpy().copy() for k in names}
-            for k in names:
-                getattr(il, k)[c] = SENTINEL
-    return hook, seen
 
 
 def test_early_out_chains_finish_in_the_middle_segment_and_stay_untouched(eng, orc):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import ppo_ref
+import segments_common
 from learning_environments_amd import _lib
 from test_ppo_gpu import SMALL, _reward_env_and_real_env, assert_chain_equals_restatement, bits, make_cfg, make_inputs
 
@@ -46,18 +47,13 @@ class Run(object):
         return self.snapshot()
 
     def split(self, split, between=None):
-        for b, e in ranges(split):
-            self.il.run_segment(*self.pos, b, e, **self.kw)
-            if between is not None:
-                between(self.il, b, e)
+        segments_common.split(self.il, self.pos, self.kw, ranges(split), (), between=between)
         return self.snapshot()
 
     def snapshot(self):
-        """the outputs in the form tests/test_ppo_gpu.py's launch() returns them"""
-        torch.cuda.synchronize()
-        il = self.il
-        out = {k: getattr(il, k).cpu().numpy().copy() for k in OUT_NAMES}
-        out["trace"] = {k: v.cpu().numpy().copy() for k, v in il.trace.items()}
+        """the outputs in the form tests/test_ppo_gpu.py's launch() returns them: the trace arrays in a dict of their own"""
+        out = segments_common.snapshot(self.il, OUT_NAMES)
+        out["trace"] = {k[len("trace_"):]: out.pop(k) for k in sorted(out) if k.startswith("trace_")}
         return out
 
 
@@ -68,11 +64,7 @@ def flat(snap):
 
 
 def same_bits(a, b, what):
-    a, b = flat(a), flat(b)
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, (what, k)
-        assert a[k].tobytes() == b[k].tobytes(), (what, k, np.argwhere(a[k] != b[k])[:4].tolist())
+    segments_common.same_bits(flat(a), flat(b), what)
 
 
 CASES = {

@@ -17,6 +17,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from segments_common import SENTINEL, _poison_finished, same_bits as _same_bits, single, snapshot, split  # noqa: E402
 from test_gpu_parity import _td3_cfgs, _td3_compare, dev, eng, orc  # noqa: E402,F401  (the oracle comparison helper and its fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -39,18 +40,7 @@ EARLY_SOLVED = -58.0        # episode-2 means: -76.4 -93.8 -78.1 -55.4 -92.9 -91
 
 
 def _snapshot(il):
-    torch.cuda.synchronize()
-    out = {k: getattr(il, k).cpu().numpy().copy() for k in OUT_NAMES}
-    out.update({"trace_" + k: v.cpu().numpy().copy() for k, v in il.trace.items()})
-    if il.icm:
-        out["icm_final"] = il.icm_final.cpu().numpy().copy()
-    return out
-
-
-def _same_bits(a, b, what):
-    for k in a:
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape, (what, k)
-        assert a[k].tobytes() == b[k].tobytes(), (what, k, np.argwhere(a[k] != b[k])[:4].tolist())
+    return snapshot(il, OUT_NAMES)
 
 
 class Case(object):
@@ -139,18 +129,11 @@ class Case(object):
 
     def single(self, eng):
         il = self.inner(eng)
-        pos, kw = self.args()
-        il.run(*pos, **kw)
-        return il, _snapshot(il)
+        return il, single(il, *self.args(), OUT_NAMES)
 
     def split(self, eng, segments, between=None):
         il = self.inner(eng)
-        pos, kw = self.args()
-        for b, e in segments:
-            il.run_segment(*pos, b, e, **kw)
-            if between is not None:
-                between(il, b, e)
-        return il, _snapshot(il)
+        return il, split(il, *self.args(), segments, OUT_NAMES, between=between)
 
 
 def _check_vs_oracle(case, orc, il, snap):
@@ -207,25 +190,6 @@ def test_one_hidden_layer_maxima_where_the_old_entry_skips_the_product_queue(eng
         _same_bits(ref, case.split(eng, segments)[1], segments)
     case.cfg.kernel_variant = _lib.VARIANT_NO_DIRECT
     _same_bits(ref, case.single(eng)[1], "the old entry on the queued kernel")
-
-
-SENTINEL = 77
-
-
-def _poison_finished(names):
-    """between-segments hook: the output rows of chains that are finished get a sentinel (the caller owns the outputs; the workspace is left
-    alone), so that a later segment that writes them again -- even the same values -- shows."""
-    seen = {}
-
-    def hook(il, b, e):
-        torch.cuda.synchronize()
-        for c in np.flatnonzero(il.resume[:, 1].cpu().numpy() == 1):
-            if int(c) in seen:
-                continue
-            seen[int(c)] = {k: getattr(il, k)[c].cpu().numpy().copy() for k in names}
-            for k in names:
-                getattr(il, k)[c] = SENTINEL
-    return hook, seen
 
 
 def test_early_out_chains_finish_in_their_segment_and_stay_untouched(eng, orc, golden):

@@ -123,13 +123,29 @@ def _td3_loop(cfgd, chains, seed=0, **over):
     return il, (theta, None, None, None, init), dict(rng_keys=keys)
 
 
-def run_td3_segments(name, cfgd, chains, episodes, splits, runs=7):
-    """The cost of splitting: one workload as one launch of lenv_td3_rn_inner_loop_icm (the generic kernel: kernel_variant GENERIC), as ONE
-    segment launch and as `splits` segment launches of lenv_td3_rn_inner_loop_segment (with the host's read of the finished words behind each),
-    `runs` timed runs each in alternation after a warm-up of each; medians, spreads and ratios to the old entry; the three must agree bit for bit."""
-    il, pos, kw = _td3_loop(cfgd, chains, train_episodes=episodes)
+def _timed_segments(il, pos, kw, episodes, after=None):
+    """Segment launches of ONE episode each, every one timed on its own: the seconds per launch.  after(): called behind each, outside its time."""
+    times = []
+    for e in range(episodes):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        il.run_segment(*pos, e, e + 1, **kw)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+        if after is not None:
+            after()
+    return times
+
+
+def run_segments(name, loop, final, episodes, splits, runs=7, boundary_wait=False):
+    """The cost of splitting: the workload of `loop` = (inner loop, run arguments, keyword arguments) as one launch of the family's old entry,
+    as ONE segment launch and as `splits` segment launches (with the host's read of the finished words behind each), `runs` timed runs each in
+    alternation after a warm-up of each; medians, the runs' ranges and spreads (max - min) and ratios to the old entry; the three must agree
+    bit for bit in every output and in `final`, the final-parameter buffer.  boundary_wait: also where a split series can lose time."""
+    il, pos, kw = loop
     per = -(-episodes // splits)
-    forms = (("old_entry", None), ("one_segment", episodes), ("%d_segments" % splits, per))
+    last = "%d_segments" % splits
+    forms = (("old_entry", None), ("one_segment", episodes), (last, per))
     times, snaps = {k: [] for k, _ in forms}, {}
     for it in range(runs + 1):
         for label, epl in forms:
@@ -139,14 +155,32 @@ def run_td3_segments(name, cfgd, chains, episodes, splits, runs=7):
             torch.cuda.synchronize()
             if it:
                 times[label].append(time.perf_counter() - t0)
-            snaps[label] = [t.clone() for t in (il.score, il.stats, il.status, il.episode_test_mean, il.episode_len, il.final_returns, il.final_params)]
+            snaps[label] = [t.clone() for t in (il.score, il.stats, il.status, il.episode_test_mean, il.episode_len, il.final_returns, getattr(il, final))]
     same = all(all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(snaps["old_entry"], snaps[k])) for k in snaps)
     med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    lo, hi = min(times["old_entry"]), max(times["old_entry"])
     st = il.stats.cpu().numpy()
-    out = dict(config=name, chains=chains, episodes=episodes, runs_each=runs, s_median=med, s_spread={k: max(v) - min(v) for k, v in times.items()},
-               ratio_to_old_entry={k: med[k] / med["old_entry"] for k in med}, bit_identical=bool(same), status_ok=bool(int(il.status.min()) == 0),
-               train_steps_per_chain=float(st[:, 1].mean()), learn_steps_per_chain=float(st[:, 2].mean()), test_steps_per_chain=float(st[:, 3].mean()),
-               workspace_MiB=il.ws_bytes / 2.0 ** 20)
+    learn = float(st[:, 2].mean())
+    out = dict(config=name, chains=il.chains, episodes=episodes, runs_each=runs, s_median=med, s_min={k: min(v) for k, v in times.items()},
+               s_max={k: max(v) for k, v in times.items()}, s_spread={k: max(v) - min(v) for k, v in times.items()},
+               s_samples={k: [round(x, 5) for x in v] for k, v in times.items()}, ratio_to_old_entry={k: med[k] / med["old_entry"] for k in med},
+               ms_per_boundary=1e3 * (med[last] - med["old_entry"]) / max(1, splits - 1), split_median_inside_old_entry_range=bool(lo <= med[last] <= hi),
+               bit_identical=bool(same), status_ok=bool(int(il.status.min()) == 0), train_steps_per_chain=float(st[:, 1].mean()),
+               train_steps_max=int(st[:, 1].max()), learn_steps_per_chain=learn, learn_calls_per_chain=learn,
+               test_steps_per_chain=float(st[:, 3].mean()), workspace_MiB=il.ws_bytes / 2.0 ** 20)
+    if boundary_wait:
+        assert same, "the three forms of the launch differ"
+        # where a split series can lose time: a workgroup per chain and every chain resident, so a launch lasts as long as its slowest chain -- one launch
+        # max_c sum_e steps(c, e), a series sum_seg max_c sum_(e in seg) steps(c, e): the chains wait for each other at every boundary.  steps = the
+        # episode's agent steps plus `w` times its test steps (CartPole with one test episode: the test return IS its length), for w = 0 and 0.2
+        ln = il.episode_len.cpu().numpy().astype(float)
+        tl = il.episode_test_mean.cpu().numpy() if il.cfg.test_episodes == 1 and il.cfg.env_id == 0 else 0.0 * ln
+        model = {}
+        for w in (0.0, 0.2):
+            S = ln + w * tl
+            model["test_step_weight_%.1f" % w] = sum(S[:, b:b + per].sum(1).max() for b in range(0, episodes, per)) / S.sum(1).max()
+        out["boundary_wait_model_ratio"] = model
+        out["slowest_chain_per_segment"] = [int(ln[:, b:b + per].sum(1).argmax()) for b in range(0, episodes, per)]
     print(json.dumps(out))
     return out
 
@@ -157,13 +191,7 @@ def run_td3_episode_time(name, cfgd, shape, chains=8, timed=2):
     time does not depend on the number of chains while they fit the CUs."""
     H, L, B = shape
     il, pos, kw = _td3_loop(cfgd, chains, train_episodes=2 + timed, init_episodes=1, hidden=H, layers=L, batch_size=B)
-    times = []
-    for e in range(2 + timed):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        il.run_segment(*pos, e, e + 1, **kw)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
+    times = _timed_segments(il, pos, kw, 2 + timed)
     st = il.stats.cpu().numpy()
     fin, status = il.segment_state()
     out = dict(config=name, hidden=H, layers=L, batch=B, chains=chains, s_per_learning_episode=sorted(times[2:])[len(times[2:]) // 2],
@@ -207,51 +235,6 @@ def _cartpole_transfer_config(script, episodes):
     return c
 
 
-def run_dueling_segments(name, cfgd, chains, shape, episodes, splits, runs=7):
-    """The cost of splitting the DDQN / DuelingDDQN inner loop: one workload as one launch of lenv_dueling_se_inner_loop_hp / _icm (per-chain
-    hyper-parameters: the generic kernel), as ONE segment launch and as `splits` segment launches of lenv_dueling_se_inner_loop_segment (with the
-    host's read of the finished words behind each), `runs` timed runs each in alternation after a warm-up of each; medians, the runs' ranges
-    and ratios to the old entry; the three must agree bit for bit."""
-    il, pos, kw = _dueling_loop(cfgd, chains, shape)
-    per = -(-episodes // splits)
-    forms = (("old_entry", None), ("one_segment", episodes), ("%d_segments" % splits, per))
-    times, snaps = {k: [] for k, _ in forms}, {}
-    for it in range(runs + 1):
-        for label, epl in forms:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            il.run(*pos, episodes_per_launch=epl, **kw)
-            torch.cuda.synchronize()
-            if it:
-                times[label].append(time.perf_counter() - t0)
-            snaps[label] = [t.clone() for t in (il.score, il.stats, il.status, il.episode_test_mean, il.episode_len, il.final_returns, il.final_online)]
-    same = all(all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(snaps["old_entry"], snaps[k])) for k in snaps)
-    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
-    lo, hi = min(times["old_entry"]), max(times["old_entry"])
-    last = "%d_segments" % splits
-    st = il.stats.cpu().numpy()
-    out = dict(config=name, chains=chains, episodes=episodes, runs_each=runs, s_median=med, s_min={k: min(v) for k, v in times.items()},
-               s_max={k: max(v) for k, v in times.items()}, s_spread={k: max(v) - min(v) for k, v in times.items()},
-               ratio_to_old_entry={k: med[k] / med["old_entry"] for k in med}, split_median_inside_old_entry_range=bool(lo <= med[last] <= hi),
-               bit_identical=bool(same), status_ok=bool(int(il.status.min()) == 0), train_steps_per_chain=float(st[:, 1].mean()),
-               train_steps_max=int(st[:, 1].max()), learn_steps_per_chain=float(st[:, 2].mean()), test_steps_per_chain=float(st[:, 3].mean()),
-               workspace_MiB=il.ws_bytes / 2.0 ** 20)
-    assert same, "the three forms of the launch differ"
-    # where a split series can lose time: a workgroup per chain and every chain resident, so a launch lasts as long as its slowest chain -- one launch
-    # max_c sum_e steps(c, e), a series sum_seg max_c sum_(e in seg) steps(c, e): the chains wait for each other at every boundary.  steps = the
-    # episode's agent steps plus `w` times its test steps (CartPole with one test episode: the test return IS its length), for w = 0 and 0.2
-    ln = il.episode_len.cpu().numpy().astype(float)
-    tl = il.episode_test_mean.cpu().numpy() if il.cfg.test_episodes == 1 and il.cfg.env_id == 0 else 0.0 * ln
-    model = {}
-    for w in (0.0, 0.2):
-        S = ln + w * tl
-        model["test_step_weight_%.1f" % w] = sum(S[:, b:b + per].sum(1).max() for b in range(0, episodes, per)) / S.sum(1).max()
-    out["boundary_wait_model_ratio"] = model
-    out["slowest_chain_per_segment"] = [int(ln[:, b:b + per].sum(1).argmax()) for b in range(0, episodes, per)]
-    print(json.dumps(out))
-    return out
-
-
 def run_dueling_episode_time(name, cfgd, shape, chains=8, episodes=300, lr=1e-3):
     """Seconds per FULL-LENGTH learning episode (max_steps agent steps, each with a learn step) of a chain at `shape` = (hidden, layers, batch):
     segment launches of one episode each, every one timed.  CartPole episodes end when the pole falls, so a launch is full-length only once an
@@ -261,13 +244,7 @@ def run_dueling_episode_time(name, cfgd, shape, chains=8, episodes=300, lr=1e-3)
     il, pos, kw = _dueling_loop(cfgd, chains, shape, lr=lr)
     E, full_len = il.cfg.train_episodes, il.cfg.max_steps
     assert E == episodes
-    times = []
-    for e in range(E):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        il.run_segment(*pos, e, e + 1, **kw)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
+    times = _timed_segments(il, pos, kw, E)
     fin, status = il.segment_state()
     longest = il.episode_len.cpu().numpy().max(axis=0)
     full = sorted(t for t, n in zip(times[2:], longest[2:]) if n == full_len)
@@ -308,35 +285,6 @@ def _ppo_loop(cfgd, chains, models=1, seed=0, **over):
     return il, pos, dict(rng_keys=keys)
 
 
-def run_ppo_segments(name, cfgd, chains, episodes, splits, runs=7):
-    """The cost of splitting: one workload as one launch of lenv_ppo_rn_inner_loop, as ONE segment launch and as `splits` segment launches of
-    lenv_ppo_rn_inner_loop_segment (with the host's read of the finished words behind each), `runs` timed runs each in alternation after a warm-up
-    of each; medians, spreads (max - min) and ratios to the old entry; the three must agree bit for bit."""
-    il, pos, kw = _ppo_loop(cfgd, chains, train_episodes=episodes)
-    per = -(-episodes // splits)
-    forms = (("old_entry", None), ("one_segment", episodes), ("%d_segments" % splits, per))
-    times, snaps = {k: [] for k, _ in forms}, {}
-    for it in range(runs + 1):
-        for label, epl in forms:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            il.run(*pos, episodes_per_launch=epl, **kw)
-            torch.cuda.synchronize()
-            if it:
-                times[label].append(time.perf_counter() - t0)
-            snaps[label] = [t.clone() for t in (il.score, il.stats, il.status, il.episode_test_mean, il.episode_len, il.final_returns, il.final_params)]
-    same = all(all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(snaps["old_entry"], snaps[k])) for k in snaps)
-    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
-    st = il.stats.cpu().numpy()
-    out = dict(config=name, chains=chains, episodes=episodes, runs_each=runs, s_median=med, s_spread={k: max(v) - min(v) for k, v in times.items()},
-               s_samples={k: [round(x, 5) for x in v] for k, v in times.items()}, ratio_to_old_entry={k: med[k] / med["old_entry"] for k in med},
-               ms_per_boundary=1e3 * (med["%d_segments" % splits] - med["old_entry"]) / max(1, splits - 1), bit_identical=bool(same),
-               status_ok=bool(int(il.status.min()) == 0), train_steps_per_chain=float(st[:, 1].mean()), learn_calls_per_chain=float(st[:, 2].mean()),
-               test_steps_per_chain=float(st[:, 3].mean()), workspace_MiB=il.ws_bytes / 2.0 ** 20)
-    print(json.dumps(out))
-    return out
-
-
 def run_ppo_episode_time(name, env_name, episodes, models=10, agents=10, seed=0):
     """Seconds per episode of the PPO transfer scripts' chains: models x agents chains at experiments/transfer_algo.py's PPO_SETTINGS of the env on a
     RewardEnv of the real env at full episode length, `episodes` segment launches of ONE episode each, every one timed on its own (the first is
@@ -348,16 +296,9 @@ def run_ppo_episode_time(name, env_name, episodes, models=10, agents=10, seed=0)
     cfgd["envs"][env_name]["solved_reward"] = ta.SOLVED_REWARD[env_name]
     chains = models * agents
     il, pos, kw = _ppo_loop(cfgd, chains, models=models, seed=seed, train_episodes=episodes)
-    times, learned, calls = [], [], 0
-    for e in range(episodes):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        il.run_segment(*pos, e, e + 1, **kw)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
-        now = int(il.stats[:, 2].sum())
-        learned.append(now > calls)
-        calls = now
+    calls = [0]
+    times = _timed_segments(il, pos, kw, episodes, after=lambda: calls.append(int(il.stats[:, 2].sum())))
+    learned = [b > a for a, b in zip(calls[:-1], calls[1:])]
     fin, status = il.segment_state()
     st = il.stats.cpu().numpy()
     med = lambda v: sorted(v)[len(v) // 2] if v else None
@@ -585,7 +526,8 @@ if __name__ == "__main__":
         c = configs.fixed_work(configs.cmc_syn_env_td3(16), 60)
         c["agents"]["td3"]["init_episodes"] = 6
         c["envs"]["MountainCarContinuous-v0"]["max_steps"] = 200
-        run_td3_segments("MountainCarContinuous SE + TD3 (B 256) 48 chains, 60 episodes x 100 agent steps: 1 launch / 1 segment / 6 segments", c, 48, 60, 6)
+        run_segments("MountainCarContinuous SE + TD3 (B 256) 48 chains, 60 episodes x 100 agent steps: 1 launch / 1 segment / 6 segments",
+                     _td3_loop(c, 48, train_episodes=60), "final_params", 60, 6)
     if "td3_episode_time" in which:
         # the TD3 *_transfer_vary_hp scripts' chains (a RewardEnv on the real env, full-length episodes): the nominal shape and the largest one
         # their hyper-parameter draw can give (hidden 384, 3 layers, batch 768)
@@ -599,11 +541,11 @@ if __name__ == "__main__":
         # the CartPole vary_hp transfer script's nominal DDQN chain (4-64-2 relu, batch 32, lr 2.5e-4, eps 1.0 -> 0.1 at 0.9 per episode, one init
         # episode, one test episode per training episode) on the published CartPole RewardEnv (type 2, reward net 4-64-1), 48 chains, 240 episodes of
         # up to 200 steps: the old entry, one segment, six segments
-        run_dueling_segments("CartPole RN + DDQN 64x1 B 32, 48 chains, 240 episodes of up to 200 steps: 1 launch / 1 segment / 6 segments",
-                             _cartpole_transfer_config("vary_hp", 240), 48, (64, 1, 32), 240, 6)
+        run_segments("CartPole RN + DDQN 64x1 B 32, 48 chains, 240 episodes of up to 200 steps: 1 launch / 1 segment / 6 segments",
+                     _dueling_loop(_cartpole_transfer_config("vary_hp", 240), 48, (64, 1, 32)), "final_online", 240, 6, boundary_wait=True)
         # the same with ONE chain (chain 0 of the 48): no chain waits for another at a boundary, what is left is the cost of splitting itself
-        run_dueling_segments("CartPole RN + DDQN 64x1 B 32, 1 chain, 240 episodes of up to 200 steps: 1 launch / 1 segment / 6 segments",
-                             _cartpole_transfer_config("vary_hp", 240), 1, (64, 1, 32), 240, 6)
+        run_segments("CartPole RN + DDQN 64x1 B 32, 1 chain, 240 episodes of up to 200 steps: 1 launch / 1 segment / 6 segments",
+                     _dueling_loop(_cartpole_transfer_config("vary_hp", 240), 1, (64, 1, 32)), "final_online", 240, 6, boundary_wait=True)
     if "dueling_episode_time" in which:
         # the CartPole transfer scripts' chains (a RewardEnv on the real env, episodes of up to 200 steps): the nominal shape and the largest one
         # the vary_hp script's draw can give (hidden 192, 2 layers, batch 96), for the plain-DQN agent (vary_hp script) and the dueling one (algo
@@ -615,9 +557,11 @@ if __name__ == "__main__":
         # the README's PPO shape (default_config_pendulum_reward_env.yaml, PPO 64 x 2 relu, a learn call of 10 epochs x 1 001 rows every five episodes)
         # on 48 chains, 60 episodes of 200 steps: the old entry, one segment, six segments of ten episodes
         c = configs.fixed_work(configs.pendulum_reward_env_ppo(16, train_episodes=60), 60)
-        run_ppo_segments("Pendulum RN + PPO 64x2, 48 chains, 60 episodes x 200 steps: 1 launch / 1 segment / 6 segments", c, 48, 60, 6)
+        run_segments("Pendulum RN + PPO 64x2, 48 chains, 60 episodes x 200 steps: 1 launch / 1 segment / 6 segments",
+                     _ppo_loop(c, 48, train_episodes=60), "final_params", 60, 6)
         # the same with ONE chain: no chain waits for another at a boundary, what is left is the cost of splitting itself
-        run_ppo_segments("Pendulum RN + PPO 64x2, 1 chain, 60 episodes x 200 steps: 1 launch / 1 segment / 6 segments", c, 1, 60, 6)
+        run_segments("Pendulum RN + PPO 64x2, 1 chain, 60 episodes x 200 steps: 1 launch / 1 segment / 6 segments",
+                     _ppo_loop(c, 1, train_episodes=60), "final_params", 60, 6)
     if "ppo_episode_time" in which:
         # the PPO *_transfer_algo scripts' chains: 10 models x 10 agents at the scripts' settings, full-length episodes.  MountainCarContinuous: a
         # learn call (1 999 rows x 80 epochs) about every tenth episode; the HalfCheetah stand-in: one (1 001 rows x 10 epochs) in every episode
