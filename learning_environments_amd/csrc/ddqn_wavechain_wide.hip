@@ -21,6 +21,7 @@
 // step (SE step, greedy action, test episodes) runs redundantly on every member, as in dueling_wavechain.hip.
 #include "lenv_wavechain.cuh"
 #include "lenv_wavechain_host.h"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -851,12 +852,6 @@ __global__ __launch_bounds__(NT) void ddqn_wavechain_wide_kernel(const WwArgs a)
     if (a.out.status && status != 0) atomicMin(&a.out.status[chain], status);
 }
 
-__global__ void ww_team_reset_kernel(float *arena, int64_t arena_stride, int64_t a_bar, int64_t chains)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < chains) { unsigned *b = reinterpret_cast<unsigned *>(arena + c * arena_stride + a_bar); b[0] = 0u; b[8] = 0u; }
-}
-
 }  // namespace lenv
 
 using namespace lenv;
@@ -872,24 +867,22 @@ int lenv_wc_ddqn_wide_shape(const lenv_ddqn_cfg *cfg)
            !cfg->q_layer_norm && cfg->test_episodes == T && cfg->synthetic_env_type == 0 && cfg->test_mode == 0 && !cfg->icm_enabled;
 }
 
-static void ww_offsets(const lenv_ddqn_cfg *cfg, int64_t rb_cap, int RS, WwArgs &a, int64_t *total)
+// one chain's arena: places the buffers in `a`, returns its floats
+static int64_t ww_offsets(const lenv_ddqn_cfg *cfg, int64_t rb_cap, int RS, WwArgs &a)
 {
     using namespace ww;
-    int64_t off = 0;
-    auto take = [&](int64_t n) { int64_t r = off; off += (n + 3) & ~(int64_t)3; return r; };
-    a.a_par = take(4 * (int64_t)PW); a.a_w2n = take((int64_t)H * H); a.a_dump = take(4 * (int64_t)B * H); a.a_qx = take(3 * (int64_t)B * A);
-    a.a_se = take(3 * (int64_t)(K + 1) * Hse); a.a_replay = take(rb_cap * RS);
-    a.a_meter = take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
-    a.a_bar = take(16); a.a_ids = take(16);
-    *total = (off + 63) & ~(int64_t)63;
+    lenv_host::ArenaCursor c;
+    a.a_par = c.take(4 * (int64_t)PW); a.a_w2n = c.take((int64_t)H * H); a.a_dump = c.take(4 * (int64_t)B * H); a.a_qx = c.take(3 * (int64_t)B * A);
+    a.a_se = c.take(3 * (int64_t)(K + 1) * Hse); a.a_replay = c.take(rb_cap * RS);
+    a.a_meter = c.take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
+    a.a_bar = c.take(16); a.a_ids = c.take(16);
+    return c.total();
 }
 
 int64_t lenv_wc_ddqn_wide_arena_floats(const lenv_ddqn_cfg *cfg, int64_t rb_cap, int RS)
 {
     WwArgs a;
-    int64_t total;
-    ww_offsets(cfg, rb_cap, RS, a, &total);
-    return total;
+    return ww_offsets(cfg, rb_cap, RS, a);
 }
 
 static size_t ww_lds_bytes() { return (size_t)ww::L_END * sizeof(float); }
@@ -898,12 +891,7 @@ static size_t ww_lds_bytes() { return (size_t)ww::L_END * sizeof(float); }
 // per CU at this kernel's LDS footprint), else 1.  cfg->team_size caps the choice (0 = automatic, 1 = the plain launch).
 int lenv_wc_ddqn_wide_team(const lenv_ddqn_cfg *cfg, int64_t chains)
 {
-    const int want = cfg->team_size > 0 ? cfg->team_size : 4;
-    if (want == 1 || chains < 1) return 1;
-    const int64_t padded = 8 * ((chains + 7) / 8);
-    for (int G : { 4, 2 })
-        if (G <= want && lenv_team_grid_resident(reinterpret_cast<const void *>(ddqn_wavechain_wide_kernel), NT, ww_lds_bytes(), padded * G)) return G;
-    return 1;
+    return lenv_host::pick_team({ 4, 2 }, cfg->team_size, 0, chains, reinterpret_cast<const void *>(ddqn_wavechain_wide_kernel), NT, ww_lds_bytes());
 }
 
 int lenv_wc_ddqn_wide_launch(const lenv_ddqn_cfg *cfg, const float *theta, const float *eps, const int32_t *worker, const float *sign,
@@ -912,23 +900,12 @@ int lenv_wc_ddqn_wide_launch(const lenv_ddqn_cfg *cfg, const float *theta, const
 {
     WwArgs a;
     a.cfg = *cfg;
-    a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.agent_init = agent_init; a.rng_keys = rng_keys;
+    lenv_host::fill_population(a, theta, eps, worker, sign, agent_init, rng_keys);
     a.arena = arena; a.arena_stride = arena_stride; a.out = *out; a.rb_cap = rb_cap; a.RS = RS; a.P = P; a.P_se = P_se;
     for (int i = 0; i < 3; ++i) a.se_net_size[i] = se_net_size[i];
     if (P != ww::NPAR || RS < 2 * ww::S + 3) return LENV_ERR_UNSUPPORTED;
-    int64_t total;
-    ww_offsets(cfg, rb_cap, RS, a, &total);
-    if (total > arena_stride) return LENV_ERR_WORKSPACE;
-    const size_t lds_bytes = ww_lds_bytes();
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(ddqn_wavechain_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-        return LENV_ERR_LAUNCH;
+    if (ww_offsets(cfg, rb_cap, RS, a) > arena_stride) return LENV_ERR_WORKSPACE;
     a.chains = chains;
     a.G = lenv_wc_ddqn_wide_team(cfg, chains);
-    unsigned grid = (unsigned)chains;
-    if (a.G > 1) {
-        grid = (unsigned)(8 * ((chains + 7) / 8) * a.G);
-        hipLaunchKernelGGL(ww_team_reset_kernel, dim3((unsigned)((chains + 255) / 256)), dim3(256), 0, stream, arena, arena_stride, a.a_bar, chains);
-    }
-    hipLaunchKernelGGL(ddqn_wavechain_wide_kernel, dim3(grid), dim3(NT), lds_bytes, stream, a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch_team(ddqn_wavechain_wide_kernel, NT, ww_lds_bytes(), stream, a);
 }

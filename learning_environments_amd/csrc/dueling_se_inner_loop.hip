@@ -19,6 +19,7 @@
 #include "lenv_ln.cuh"
 #include "lenv_icm.cuh"
 #include "lenv_wavechain_host.h"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -1001,12 +1002,11 @@ static int dueling_layout(const lenv_ddqn_cfg *cfg, DuelArgs &a, size_t *lds_byt
     if (cap > cfg->rb_size) cap = cfg->rb_size;
     a.rb_cap = cap < 1 ? 1 : cap;
     a.A = duel_arena(S, H, F, L, B, T, a.P, ln);
-    int64_t off = a.A.end;
-    auto take = [&](int64_t n) { int64_t r = off; off += (n + 3) & ~(int64_t)3; return r; };
-    a.a_replay = take(a.rb_cap * a.RS);
-    a.a_meter = take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
+    lenv_host::ArenaCursor c{a.A.end};
+    a.a_replay = c.take(a.rb_cap * a.RS);
+    a.a_meter = c.take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
     // several hidden layers: the SEs' hidden-to-hidden blocks, or (RewardEnv mode) the whole reward net
-    a.a_se_mid = take(cfg->se_layers > 1 ? (cfg->synthetic_env_type == 1 ? (int64_t)a.P_se : 3 * (int64_t)(cfg->se_layers - 1) * ((int64_t)Hse * Hse + Hse)) : 0);
+    a.a_se_mid = c.take(cfg->se_layers > 1 ? (cfg->synthetic_env_type == 1 ? (int64_t)a.P_se : 3 * (int64_t)(cfg->se_layers - 1) * ((int64_t)Hse * Hse + Hse)) : 0);
     a.P_icm = 0;
     for (int i = 0; i < IB_COUNT; ++i) a.a_icm[i] = 0;
     if (cfg->icm_enabled) {
@@ -1017,9 +1017,9 @@ static int dueling_layout(const lenv_ddqn_cfg *cfg, DuelArgs &a, size_t *lds_byt
         a.P_icm = n.P;
         int64_t sz[IB_COUNT];
         icm_buffer_sizes(n, B, sz);
-        for (int i = 0; i < IB_COUNT; ++i) a.a_icm[i] = take(sz[i]);
+        for (int i = 0; i < IB_COUNT; ++i) a.a_icm[i] = c.take(sz[i]);
     }
-    a.arena_stride = (off + 63) & ~(int64_t)63;
+    a.arena_stride = c.total();
     {   // the wave-chain kernel (dueling_wavechain.hip) keeps its own arena layout inside the same workspace
         const int wshape = lenv_wc_dueling_shape(cfg);
         if (wshape) {
@@ -1103,28 +1103,19 @@ static int dueling_launch(const lenv_ddqn_cfg *cfg, const lenv_chain_hp *hp, con
                           int64_t chains, void *workspace, size_t workspace_bytes, const lenv_inner_out *out, bool segment, int32_t ep_begin,
                           int32_t ep_end, int64_t *resume, void *stream)
 {
-    if (!cfg || !theta || !agent_init || !out || !out->score || !workspace || chains < 0) return LENV_ERR_INVALID;
-    if (cfg->icm_enabled && (!icm || !icm->icm_init)) return LENV_ERR_INVALID;
-    if (hp && (!hp->lr || !hp->batch_size || !hp->q_hidden || !hp->q_layers)) return LENV_ERR_INVALID;
-    if (eps && (!worker || !sign)) return LENV_ERR_INVALID;
-    if (cfg->rng_mode == LENV_RNG_TAPE && !tapes) return LENV_ERR_INVALID;
-    if (cfg->rng_mode == LENV_RNG_COUNTER && !rng_keys) return LENV_ERR_INVALID;
-    if (segment && (!resume || ep_begin < 0 || ep_begin >= ep_end || ep_end > cfg->train_episodes)) return LENV_ERR_INVALID;
+    const lenv_host::Segment seg{segment, ep_begin, ep_end, resume};
+    if (!lenv_host::launch_args_ok(cfg, hp, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, out, seg)) return LENV_ERR_INVALID;
+    if (!theta || !lenv_host::icm_args_ok(cfg, icm)) return LENV_ERR_INVALID;
     if (chains == 0) return LENV_OK;
     DuelArgs a;
     size_t lds_bytes;
     const int rc = dueling_layout(cfg, a, &lds_bytes);
     if (rc != LENV_OK) return rc;
     if (workspace_bytes < (size_t)chains * a.arena_stride * sizeof(float)) return LENV_ERR_WORKSPACE;
-    a.cfg = *cfg;
-    a.ep_begin = segment ? ep_begin : 0; a.ep_end = segment ? ep_end : cfg->train_episodes; a.resume = segment ? resume : nullptr;
-    a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.agent_init = agent_init; a.rng_keys = rng_keys;
-    if (tapes) a.tapes = *tapes; else a.tapes = lenv_tapes{};
-    a.arena = static_cast<float *>(workspace);
-    a.out = *out;
-    a.hp_lr = hp ? hp->lr : nullptr; a.hp_batch = hp ? hp->batch_size : nullptr;
-    a.hp_hidden = hp ? hp->q_hidden : nullptr; a.hp_layers = hp ? hp->q_layers : nullptr;
-    a.icm_init = cfg->icm_enabled ? icm->icm_init : nullptr; a.icm_final = cfg->icm_enabled ? icm->icm_final : nullptr;
+    lenv_host::fill_args(a, cfg, theta, eps, worker, sign, agent_init, rng_keys, tapes, workspace, out);
+    lenv_host::fill_segment(a, cfg, seg);
+    lenv_host::fill_hp(a, hp);
+    lenv_host::fill_icm(a, cfg, icm);
     void (*kern)(const DuelArgs) = cfg->icm_enabled ? dueling_se_inner_kernel<true> : dueling_se_inner_kernel<false>;
     if (segment) kern = cfg->icm_enabled ? dueling_se_inner_kernel<true, 0, true> : dueling_se_inner_kernel<false, 0, true>;
     else {
@@ -1154,10 +1145,7 @@ static int dueling_launch(const lenv_ddqn_cfg *cfg, const lenv_chain_hp *hp, con
             else if (matches(kDuelShapes[2])) kern = dueling_se_inner_kernel<false, 2>;
         }
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, stream, a);
 }
 
 extern "C" int lenv_dueling_se_inner_loop_icm(const lenv_ddqn_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta,

@@ -21,6 +21,7 @@
 #define WCT_FUSED_OPT
 #endif
 #include "lenv_wavechain_host.h"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -1226,7 +1227,7 @@ __global__ __launch_bounds__(NT) void dueling_wavechain_kernel(const WcArgs a)
     int train_steps = 0, n_act = 0, learn_it = 0, n_test_ep = 0, test_steps = 0, episodes_run = 0;
     double eps_g = cfg.eps_init, b1pow = 1.0, b2pow = 1.0;
     const int rb_cap = (int)a.rb_cap;
-    // ---- team barrier (G = 2; wc::team_barrier): the chain's counter and the launch's give-up word are zeroed by wct_team_reset_kernel
+    // ---- team barrier (G = 2; wc::team_barrier): the chain's counter and the launch's give-up word are zeroed by wc_team_reset_kernel
     TeamSync tsync{ team_bar, reinterpret_cast<unsigned *>(a.arena + a.a_bar) + 8, ictrl + 5, 0u, G, false, false };
     bool team_dead = false;
     auto team_barrier = [&]() {
@@ -1636,35 +1637,33 @@ static size_t wc_lds_bytes(const WcShape &sp)
     return f * sizeof(float);
 }
 
-// floats of one chain's arena in the wave-chain layout (the workspace query of the generic path takes the maximum of both)
-int64_t lenv_wc_dueling_arena_floats(const lenv_ddqn_cfg *cfg, int shape, int64_t rb_cap, int RS, int P_se)
+// one chain's arena: the ONE place that sizes the workspace (lenv_wc_dueling_arena_floats) and places the buffers (lenv_wc_dueling_launch); returns its floats
+static int64_t wc_offsets(const lenv_ddqn_cfg *cfg, int shape, int64_t rb_cap, int RS, WcArgs &a)
 {
     const WcShape &sp = kWcShapes[shape];
     const int S = sp.S, B = WC_B, T = sp.T, K = sp.S + sp.A;
-    int64_t off = 0;
-    auto take = [&](int64_t n) { int64_t r = off; off += (n + 3) & ~(int64_t)3; return r; };
-    take(5 * (int64_t)wcp::PW); take((int64_t)B * S); take((int64_t)(B > T ? B : T) * S); take((int64_t)WC_NDUMP * 4 * wc::BLK);
-    take(3 * (int64_t)(K + 1) * sp.Hse); take(rb_cap * RS); take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
-    take(3 * (int64_t)B * (1 + sp.A)); take(16); take(2 * (int64_t)(B > T ? B : T) * S);      // team exchange, barrier word, per-member scratch rows
-    (void)P_se;
-    return (off + 63) & ~(int64_t)63;
+    lenv_host::ArenaCursor c;
+    a.a_par = c.take(5 * (int64_t)wcp::PW); a.a_xs = c.take((int64_t)B * S); a.a_xs2 = c.take((int64_t)(B > T ? B : T) * S);
+    a.a_dump = c.take((int64_t)WC_NDUMP * 4 * wc::BLK); a.a_se = c.take(3 * (int64_t)(K + 1) * sp.Hse); a.a_replay = c.take(rb_cap * RS);
+    a.a_meter = c.take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
+    a.a_gx = c.take(3 * (int64_t)B * (1 + sp.A)); a.a_bar = c.take(16); a.a_xtm = c.take(2 * (int64_t)(B > T ? B : T) * S);      // team exchange, barrier word, per-member scratch rows
+    return c.total();
 }
 
-namespace lenv {
-__global__ void wct_team_reset_kernel(float *arena, int64_t arena_stride, int64_t a_bar, int64_t chains)
+// floats of one chain's arena in the wave-chain layout (the workspace query of the generic path takes the maximum of both)
+int64_t lenv_wc_dueling_arena_floats(const lenv_ddqn_cfg *cfg, int shape, int64_t rb_cap, int RS, int P_se)
 {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < chains) { unsigned *b = reinterpret_cast<unsigned *>(arena + c * arena_stride + a_bar); b[0] = 0u; b[8] = 0u; }
-}
+    WcArgs a;
+    return wc_offsets(cfg, shape, rb_cap, RS, a);
 }
 
 // Workgroups per chain: 2 when all 8 * ceil(chains / 8) * 2 workgroups are resident at once (occupancy API: one per CU at this
 // kernel's LDS footprint) -- the members wait for each other --, else 1.  cfg->team_size 1 forces one workgroup per chain.
 int lenv_wc_dueling_team(const lenv_ddqn_cfg *cfg, int shape, int64_t chains)
 {
-    if (cfg->team_size == 1 || chains < 1 || shape <= 0) return 1;
+    if (shape <= 0) return 1;
     void (*kern)(const WcArgs) = shape == 2 ? dueling_wavechain_kernel<2> : dueling_wavechain_kernel<1>;
-    return lenv_team_grid_resident(reinterpret_cast<const void *>(kern), wc::NT, wc_lds_bytes(kWcShapes[shape]), 8 * ((chains + 7) / 8) * 2) ? 2 : 1;
+    return lenv_host::pick_team({ 2 }, cfg->team_size, 0, chains, reinterpret_cast<const void *>(kern), wc::NT, wc_lds_bytes(kWcShapes[shape]));
 }
 
 int lenv_wc_dueling_launch(int shape, const lenv_ddqn_cfg *cfg, const float *theta, const float *eps, const int32_t *worker,
@@ -1675,31 +1674,15 @@ int lenv_wc_dueling_launch(int shape, const lenv_ddqn_cfg *cfg, const float *the
     const WcShape &sp = kWcShapes[shape];
     WcArgs a;
     a.cfg = *cfg;
-    a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.agent_init = agent_init; a.rng_keys = rng_keys;
+    lenv_host::fill_population(a, theta, eps, worker, sign, agent_init, rng_keys);
     a.arena = arena; a.arena_stride = arena_stride; a.out = *out; a.rb_cap = rb_cap; a.RS = RS; a.P = P; a.P_se = P_se;
     for (int i = 0; i < 3; ++i) a.se_net_size[i] = se_net_size[i];
-    const int S = sp.S, B = WC_B, T = sp.T, K = sp.S + sp.A;
-    int64_t off = 0;
-    auto take = [&](int64_t n) { int64_t r = off; off += (n + 3) & ~(int64_t)3; return r; };
-    a.a_par = take(5 * (int64_t)wcp::PW); a.a_xs = take((int64_t)B * S); a.a_xs2 = take((int64_t)(B > T ? B : T) * S);
-    a.a_dump = take((int64_t)WC_NDUMP * 4 * wc::BLK); a.a_se = take(3 * (int64_t)(K + 1) * sp.Hse); a.a_replay = take(rb_cap * RS);
-    a.a_meter = take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
-    a.a_gx = take(3 * (int64_t)B * (1 + sp.A)); a.a_bar = take(16); a.a_xtm = take(2 * (int64_t)(B > T ? B : T) * S);
-    if (off > arena_stride) return LENV_ERR_WORKSPACE;
+    if (wc_offsets(cfg, shape, rb_cap, RS, a) > arena_stride) return LENV_ERR_WORKSPACE;
     const size_t lds_bytes = wc_lds_bytes(sp);
     if (lds_bytes > 160 * 1024) return LENV_ERR_UNSUPPORTED;
-    void (*kern)(const WcArgs) = shape == 2 ? dueling_wavechain_kernel<2> : dueling_wavechain_kernel<1>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-        return LENV_ERR_LAUNCH;
     a.chains = chains;
     a.G = lenv_wc_dueling_team(cfg, shape, chains);
-    unsigned grid = (unsigned)chains;
-    if (a.G > 1) {
-        grid = (unsigned)(8 * ((chains + 7) / 8) * a.G);
-        hipLaunchKernelGGL(wct_team_reset_kernel, dim3((unsigned)((chains + 255) / 256)), dim3(256), 0, stream, arena, arena_stride, a.a_bar, chains);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(wc::NT), lds_bytes, stream, a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch_team(shape == 2 ? dueling_wavechain_kernel<2> : dueling_wavechain_kernel<1>, wc::NT, lds_bytes, stream, a);
 }
 
 #ifdef LENV_PHASE_TIMING

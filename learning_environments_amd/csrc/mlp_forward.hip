@@ -3,6 +3,7 @@
 // envs/reward_env.py:81-110).  One workgroup per input row; lane = output unit of the current layer, every dot product a
 // sequential fmaf chain in index order with the bias added last (canonical order of oracle/lenv_oracle.h).
 #include "lenv_device.cuh"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -166,10 +167,7 @@ extern "C" int lenv_mlp_forward(const lenv_mlp_desc *d, const float *params, con
     const int W = d->hidden > d->in_dim ? d->hidden : d->in_dim;
     const size_t lds_bytes = 2 * (size_t)((W + 3) & ~3) * sizeof(float) + 16;
     if (lds_bytes > 160 * 1024) return LENV_ERR_UNSUPPORTED;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(mlp_forward_kernel, dim3((unsigned)rows), dim3(MF_NT), lds_bytes, static_cast<hipStream_t>(stream), *d, params, x, rows, y);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(mlp_forward_kernel, dim3((unsigned)rows), dim3(MF_NT), lds_bytes, stream, *d, params, x, rows, y);
 }
 
 extern "C" int lenv_cheetah_standin_reset(const uint64_t *keys, const int64_t *episode, int64_t n, double *state, float *obs,

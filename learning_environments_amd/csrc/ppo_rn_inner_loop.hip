@@ -23,6 +23,7 @@
 // config.ppo_cfg_from_config refuses) and in a reward net with two or more hidden layers.  CPU restatement: tests/ppo_ref.c.
 #include "lenv_gemm.cuh"
 #include "lenv_rn.cuh"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -176,16 +177,15 @@ static int ppo_layout(const lenv_ppo_cfg *cfg, PpoArgs &a, size_t *lds_bytes)
     a.oA = PP_STD; a.oC = a.oA + ((ma.P + 3) & ~3); a.PP = a.oC + ((mc.P + 3) & ~3);
     a.P_rn = (int)lenv_rn_num_params(t, S, cfg->info_dim, Hrn, cfg->rn_layers);
     a.P_rn_lds = rn_theta_in_lds(t, cfg->rn_layers) ? a.P_rn : 0;             // deeper reward nets are staged in the arena
-    int64_t off = 0;
-    auto take = [&](int64_t n) { int64_t r = off; off += (n + 3) & ~(int64_t)3; return r; };
-    a.a_params = take(a.PP); a.a_m = take(a.PP); a.a_v = take(a.PP); a.a_grad = take(a.PP);
-    a.a_x = take(N * S); a.a_act = take(N * A); a.a_rew = take(N); a.a_done = take(N); a.a_ret = take(N); a.a_oldlp = take(N);
-    a.a_mean = take(N * A); a.a_val = take(N); a.a_dz = take(N * A); a.a_gs = take(N * A); a.a_dv = take(N);
-    for (int l = 0; l < PP_MAXL; ++l) { a.a_ha[l] = take(l < L ? N * H : 0); a.a_hc[l] = take(l < L ? N * H : 0); }
-    a.a_d[0] = take(N * H); a.a_d[1] = take(N * H);
-    a.a_meter = take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
-    a.a_rn = take(rn_theta_in_lds(t, cfg->rn_layers) ? 0 : a.P_rn);
-    a.arena_stride = (off + 63) & ~(int64_t)63;
+    lenv_host::ArenaCursor c;
+    a.a_params = c.take(a.PP); a.a_m = c.take(a.PP); a.a_v = c.take(a.PP); a.a_grad = c.take(a.PP);
+    a.a_x = c.take(N * S); a.a_act = c.take(N * A); a.a_rew = c.take(N); a.a_done = c.take(N); a.a_ret = c.take(N); a.a_oldlp = c.take(N);
+    a.a_mean = c.take(N * A); a.a_val = c.take(N); a.a_dz = c.take(N * A); a.a_gs = c.take(N * A); a.a_dv = c.take(N);
+    for (int l = 0; l < PP_MAXL; ++l) { a.a_ha[l] = c.take(l < L ? N * H : 0); a.a_hc[l] = c.take(l < L ? N * H : 0); }
+    a.a_d[0] = c.take(N * H); a.a_d[1] = c.take(N * H);
+    a.a_meter = c.take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
+    a.a_rn = c.take(rn_theta_in_lds(t, cfg->rn_layers) ? 0 : a.P_rn);
+    a.arena_stride = c.total();
     const size_t lds_floats = GemmShape<PP_MAXI>::PS_FLOATS + GemmShape<PP_MAXI>::QS_FLOATS + GEMM_QUEUE_MAX * sizeof(GemmCmd) / sizeof(float) +
                               ((a.P_rn_lds + 3) & ~3) + 2 * ((Hrn + 3) & ~3) + 2 * PP_MAXW + 64 + 48 + 20 + 20 + 8 + 8 + 64 + 2 + 2 * (20 + 20 + PP_MAXT) + 16;
     *lds_bytes = lds_floats * sizeof(float);
@@ -249,26 +249,20 @@ static int ppo_launch(const lenv_ppo_cfg *cfg, const float *theta, const float *
                       const float *agent_init, const uint64_t *rng_keys, const lenv_ppo_tapes *tapes, int64_t chains, void *workspace,
                       size_t workspace_bytes, const lenv_ppo_out *out, bool segment, int32_t ep_begin, int32_t ep_end, int64_t *resume, void *stream)
 {
-    if (!cfg || !agent_init || !out || !out->score || !workspace || chains < 0) return LENV_ERR_INVALID;
+    const lenv_host::Segment seg{segment, ep_begin, ep_end, resume};
+    if (!lenv_host::launch_args_ok(cfg, nullptr, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, out, seg)) return LENV_ERR_INVALID;
     if (!theta && cfg->reward_env_type != 0) return LENV_ERR_INVALID;
-    if (eps && (!worker || !sign)) return LENV_ERR_INVALID;
-    if (cfg->rng_mode == LENV_RNG_TAPE && (!tapes || !tapes->act_noise || !tapes->test_noise || !tapes->train_reset || !tapes->test_reset)) return LENV_ERR_INVALID;
-    if (cfg->rng_mode == LENV_RNG_COUNTER && !rng_keys) return LENV_ERR_INVALID;
+    if (cfg->rng_mode == LENV_RNG_TAPE && (!tapes->act_noise || !tapes->test_noise || !tapes->train_reset || !tapes->test_reset)) return LENV_ERR_INVALID;
     if (cfg->rng_mode != LENV_RNG_COUNTER && cfg->rng_mode != LENV_RNG_TAPE) return LENV_ERR_INVALID;
     if (out->trace_reward && out->trace_cap > 0 && (!out->trace_action || !out->trace_state || !out->trace_next_state)) return LENV_ERR_INVALID;
-    if (segment && (!resume || ep_begin < 0 || ep_begin >= ep_end || ep_end > cfg->train_episodes)) return LENV_ERR_INVALID;
-    PpoArgs a;
+    PpoArgs a;                    // (the layout runs before the chains == 0 return here: an unsupported cfg is refused with zero chains too)
     size_t lds_bytes;
     const int rc = ppo_layout(cfg, a, &lds_bytes);
     if (rc != LENV_OK) return rc;
     if (chains == 0) return LENV_OK;
     if (workspace_bytes < (size_t)chains * a.arena_stride * sizeof(float)) return LENV_ERR_WORKSPACE;
-    a.cfg = *cfg;
-    a.ep_begin = segment ? ep_begin : 0; a.ep_end = segment ? ep_end : cfg->train_episodes; a.resume = segment ? resume : nullptr;
-    a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.agent_init = agent_init; a.rng_keys = rng_keys;
-    if (tapes) a.tapes = *tapes; else a.tapes = lenv_ppo_tapes{};
-    a.arena = static_cast<float *>(workspace);
-    a.out = *out;
+    lenv_host::fill_args(a, cfg, theta, eps, worker, sign, agent_init, rng_keys, tapes, workspace, out);
+    lenv_host::fill_segment(a, cfg, seg);
     if (a.out.trace_cap <= 0) a.out.trace_reward = nullptr;
     if (a.out.learn_cap <= 0) a.out.learn_step = nullptr;
     void (*kern)(const PpoArgs) = cfg->env_id == LENV_ENV_PENDULUM ? ppo_rn_inner_kernel<LENV_ENV_PENDULUM>
@@ -276,10 +270,7 @@ static int ppo_launch(const lenv_ppo_cfg *cfg, const float *theta, const float *
     if (segment)
         kern = cfg->env_id == LENV_ENV_PENDULUM ? ppo_rn_segment_kernel<LENV_ENV_PENDULUM>
                : (cfg->env_id == LENV_ENV_CMC ? ppo_rn_segment_kernel<LENV_ENV_CMC> : ppo_rn_segment_kernel<LENV_ENV_CHEETAH_STANDIN>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, stream, a);
 }
 
 extern "C" int lenv_ppo_rn_inner_loop(const lenv_ppo_cfg *cfg, const float *theta, const float *eps, const int32_t *worker, const float *sign,

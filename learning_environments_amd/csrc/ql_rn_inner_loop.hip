@@ -13,6 +13,7 @@
 // strictly sequential scalar walk (<= train_episodes*max_steps steps) executed by lane 0 on the LDS-resident fp64 Q-table.
 // Integer/fp64 work is exact by construction; phi uses the canonical sequential-fmaf order of oracle/lenv_oracle.h.
 #include "lenv_device.cuh"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -431,10 +432,7 @@ extern "C" int lenv_ql_rn_inner_loop_hp(const lenv_ql_cfg *cfg, const double *al
     if (cfg->agent_kind != 0 && cfg->agent_kind != 1) return LENV_ERR_UNSUPPORTED;
     void (*kern)(const QlArgs) = cfg->agent_kind == 1 ? (cfg->count_based ? ql_rn_inner_kernel<1, true> : ql_rn_inner_kernel<1, false>)
                                                       : (cfg->count_based ? ql_rn_inner_kernel<0, true> : ql_rn_inner_kernel<0, false>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)chains), dim3(64), lds_bytes, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(kern, dim3((unsigned)chains), dim3(64), lds_bytes, stream, a);
 }
 
 extern "C" int lenv_ql_rn_inner_loop(const lenv_ql_cfg *cfg, const float *theta, const float *eps, const int32_t *worker,
@@ -468,8 +466,5 @@ extern "C" int lenv_rn_shape_population(const lenv_ql_cfg *cfg, const float *the
     a.P = ql_rn_params(cfg);
     const size_t lds_bytes = sizeof(float) * ((size_t)cfg->n_states * (1 + cfg->n_actions)) + 16 + (cfg->rn_layers > 1 ? sizeof(float) * 2 * 64 * (size_t)cfg->rn_hidden : 0);
     if (lds_bytes > 160 * 1024) return LENV_ERR_UNSUPPORTED;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rn_shape_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(rn_shape_kernel, dim3((unsigned)chains), dim3(64), lds_bytes, static_cast<hipStream_t>(stream), a, phi_out, shaped_out);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(rn_shape_kernel, dim3((unsigned)chains), dim3(64), lds_bytes, stream, a, phi_out, shaped_out);
 }

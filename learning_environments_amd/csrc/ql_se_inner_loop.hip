@@ -20,6 +20,7 @@
 // with one workgroup barrier behind each.  Every dot product is the canonical order of oracle/lenv_oracle.h (orc_mlp_forward) and of
 // se_step_kernel, so the SE outputs equal lenv_se_step_population's bit for bit.  docs/notebook_ql_se.md has the layout's reasoning.
 #include "lenv_device.cuh"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -451,8 +452,5 @@ extern "C" int lenv_ql_se_inner_loop(const lenv_ql_cfg *cfg, const float *theta,
     nt = (nt + 63) & ~63;
     if (nt > QSE_NT_MAX) nt = QSE_NT_MAX;
     void (*kern)(const QlSeArgs) = wlds ? ql_se_inner_kernel<true> : ql_se_inner_kernel<false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)chains), dim3((unsigned)nt), lds_bytes, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(kern, dim3((unsigned)chains), dim3((unsigned)nt), lds_bytes, stream, a);
 }

@@ -7,6 +7,7 @@
 // loop in registers and writes q(s)[a] and y = r + gamma*Q_target(s')[argmax Q(s')]*(1-done).
 // hidden_layer == 1 only (all BASELINE DDQN configs); canonical arithmetic order of oracle/lenv_oracle.h.
 #include "lenv_device.cuh"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -99,9 +100,5 @@ extern "C" int lenv_qnet_td_forward(const lenv_mlp_desc *q, const float *online,
     a.RP = (q->in_dim + 1 + q->out_dim + 3) & ~3;
     const size_t lds_bytes = 2 * ((size_t)q->hidden * a.RP + ((q->out_dim + 3) & ~3)) * sizeof(float);
     if (lds_bytes > 160 * 1024 || chains > 65535) return LENV_ERR_UNSUPPORTED;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(qnet_td_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(qnet_td_kernel, dim3((unsigned)((batch + TD_NT - 1) / TD_NT), (unsigned)chains), dim3(TD_NT), lds_bytes,
-                       static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(qnet_td_kernel, dim3((unsigned)((batch + TD_NT - 1) / TD_NT), (unsigned)chains), dim3(TD_NT), lds_bytes, stream, a);
 }

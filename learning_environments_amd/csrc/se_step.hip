@@ -7,6 +7,7 @@
 // Lane = hidden unit for the hidden layers; the output layer is a sequential fmaf chain per output
 // (canonical order of oracle/lenv_oracle.h), so results are bit-identical to the oracle.
 #include "lenv_device.cuh"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -152,8 +153,5 @@ extern "C" int lenv_se_step_population(const lenv_mlp_desc *sn, const lenv_mlp_d
     const size_t lds_floats = ((a.P + 3) & ~(int64_t)3) + ((sn->in_dim + 3) & ~3) + 6 * (size_t)sn->hidden + 16;
     const size_t lds_bytes = lds_floats * sizeof(float);
     if (lds_bytes > 160 * 1024) return LENV_ERR_UNSUPPORTED;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(se_step_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(se_step_kernel, dim3((unsigned)chains), dim3(SE_NT), lds_bytes, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(se_step_kernel, dim3((unsigned)chains), dim3(SE_NT), lds_bytes, stream, a);
 }

@@ -20,6 +20,7 @@
 // (TimeLimit: done at max_steps) and shapes the reward with its perturbed reward net, as the DDQN kernel's RENV path does.
 #include "lenv_gemm.cuh"
 #include "lenv_ln.cuh"
+#include "lenv_host.h"
 
 // Diagnostic build only (-DLENV_PHASE_TIMING): per-phase shader-clock totals of chain 0, never in the shipped library.
 #ifdef LENV_PHASE_TIMING
@@ -793,22 +794,21 @@ static int td3d_layout(const lenv_td3d_cfg *cfg, Td3dArgs &a, size_t *lds_bytes,
     a.rb_cap = cap < 1 ? 1 : cap;
     const int RB = B > T ? B : T;                               // rows of the batch buffers
     const bool ln = cfg->use_layer_norm && L >= 2;
-    int64_t off = 0;
-    auto take = [&](int64_t n) { int64_t r = off; off += (n + 3) & ~(int64_t)3; return r; };
-    a.a_params = take(a.P); a.a_targets = take(a.P); a.a_m = take(a.P); a.a_v = take(a.P); a.a_grad = take(a.P);
-    a.a_replay = take(a.rb_cap * a.RS);
-    a.a_xc = take((int64_t)RB * SA); a.a_xn = take((int64_t)RB * SA); a.a_xa = take((int64_t)RB * SA);
+    lenv_host::ArenaCursor c;
+    a.a_params = c.take(a.P); a.a_targets = c.take(a.P); a.a_m = c.take(a.P); a.a_v = c.take(a.P); a.a_grad = c.take(a.P);
+    a.a_replay = c.take(a.rb_cap * a.RS);
+    a.a_xc = c.take((int64_t)RB * SA); a.a_xn = c.take((int64_t)RB * SA); a.a_xa = c.take((int64_t)RB * SA);
     for (int l = 0; l < TD_MAXL; ++l) {
-        a.a_hc1[l] = take((int64_t)RB * H); a.a_hc2[l] = take((int64_t)RB * H); a.a_ha[l] = take((int64_t)RB * H); a.a_ht[l] = take((int64_t)RB * H);
+        a.a_hc1[l] = c.take((int64_t)RB * H); a.a_hc2[l] = c.take((int64_t)RB * H); a.a_ha[l] = c.take((int64_t)RB * H); a.a_ht[l] = c.take((int64_t)RB * H);
         a.a_xh1[l] = a.a_xh2[l] = a.a_xha[l] = 0;
-        if (ln && l >= 1) { a.a_xh1[l] = take((int64_t)RB * H); a.a_xh2[l] = take((int64_t)RB * H); a.a_xha[l] = take((int64_t)RB * H); }
+        if (ln && l >= 1) { a.a_xh1[l] = c.take((int64_t)RB * H); a.a_xh2[l] = c.take((int64_t)RB * H); a.a_xha[l] = c.take((int64_t)RB * H); }
     }
-    a.a_rs1 = take((int64_t)TD_MAXL * B); a.a_rs2 = take((int64_t)TD_MAXL * B); a.a_rsa = take((int64_t)TD_MAXL * B);
-    a.a_d[0] = take((int64_t)RB * H); a.a_d[1] = take((int64_t)RB * H);
-    a.a_dx = take((int64_t)RB * SA); a.a_raw = take((int64_t)RB * A); a.a_ys = take((int64_t)RB * A); a.a_dz = take((int64_t)RB * A);
-    a.a_meter = take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
-    a.a_se = take(a.P_se);
-    a.arena_stride = (off + 63) & ~(int64_t)63;
+    a.a_rs1 = c.take((int64_t)TD_MAXL * B); a.a_rs2 = c.take((int64_t)TD_MAXL * B); a.a_rsa = c.take((int64_t)TD_MAXL * B);
+    a.a_d[0] = c.take((int64_t)RB * H); a.a_d[1] = c.take((int64_t)RB * H);
+    a.a_dx = c.take((int64_t)RB * SA); a.a_raw = c.take((int64_t)RB * A); a.a_ys = c.take((int64_t)RB * A); a.a_dz = c.take((int64_t)RB * A);
+    a.a_meter = c.take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
+    a.a_se = c.take(a.P_se);
+    a.arena_stride = c.total();
     const size_t lds_floats = GemmShape<TD_MAXI>::PS_FLOATS + GemmShape<TD_MAXI>::QS_FLOATS + GEMM_QUEUE_MAX * sizeof(GemmCmd) / sizeof(float) + 2 * TD_MAXW +
                               8 * (size_t)B + 64 + 2 + 2 * (4 + 4 * (size_t)T + T) + 3 * (size_t)T + 8 + 8 + 32 + 16 + 16 + 16;
     *lds_bytes = lds_floats * sizeof(float);
@@ -869,33 +869,22 @@ static int td3d_launch(const lenv_td3d_cfg *cfg, const lenv_td3d_rn_cfg *rn, con
                        const lenv_td3d_tapes *tapes, int64_t chains, void *workspace, size_t workspace_bytes,
                        const lenv_td3_out *out, void *stream)
 {
-    if (hp && (!hp->lr || !hp->batch_size || !hp->q_hidden || !hp->q_layers)) return LENV_ERR_INVALID;
-    if (!cfg || !theta || !agent_init || !out || !out->score || !workspace || chains < 0) return LENV_ERR_INVALID;
-    if (eps && (!worker || !sign)) return LENV_ERR_INVALID;
-    if (cfg->rng_mode == LENV_RNG_TAPE && !tapes) return LENV_ERR_INVALID;
-    if (cfg->rng_mode == LENV_RNG_COUNTER && !rng_keys) return LENV_ERR_INVALID;
+    if (!lenv_host::launch_args_ok(cfg, hp, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, out, lenv_host::Segment{}) || !theta)
+        return LENV_ERR_INVALID;
     if (chains == 0) return LENV_OK;
     Td3dArgs a;
     size_t lds_bytes;
     const int rc = td3d_layout(cfg, a, &lds_bytes, rn);
     if (rc != LENV_OK) return rc;
     if (workspace_bytes < (size_t)chains * a.arena_stride * sizeof(float)) return LENV_ERR_WORKSPACE;
-    a.cfg = *cfg;
-    a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.agent_init = agent_init; a.rng_keys = rng_keys;
-    if (tapes) a.tapes = *tapes; else a.tapes = lenv_td3d_tapes{};
-    a.arena = static_cast<float *>(workspace);
-    a.out = *out;
-    a.hp_lr = hp ? hp->lr : nullptr; a.hp_batch = hp ? hp->batch_size : nullptr;
-    a.hp_hidden = hp ? hp->q_hidden : nullptr; a.hp_layers = hp ? hp->q_layers : nullptr;
+    lenv_host::fill_args(a, cfg, theta, eps, worker, sign, agent_init, rng_keys, tapes, workspace, out);
+    lenv_host::fill_hp(a, hp);
     a.rn = rn ? *rn : lenv_td3d_rn_cfg{};
     void (*kern)(const Td3dArgs) = nullptr;
     if (cfg->env_id == LENV_ENV_CARTPOLE) kern = rn ? td3_discrete_inner_kernel<LENV_ENV_CARTPOLE, true> : td3_discrete_inner_kernel<LENV_ENV_CARTPOLE>;
     else if (cfg->env_id == LENV_ENV_ACROBOT) kern = rn ? td3_discrete_inner_kernel<LENV_ENV_ACROBOT, true> : td3_discrete_inner_kernel<LENV_ENV_ACROBOT>;
     else kern = rn ? td3_discrete_inner_kernel<LENV_ENV_MOUNTAINCAR, true> : td3_discrete_inner_kernel<LENV_ENV_MOUNTAINCAR>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, stream, a);
 }
 
 extern "C" int lenv_td3d_inner_loop(const lenv_td3d_cfg *cfg, const lenv_chain_hp *hp, const float *theta, const float *eps,

@@ -19,6 +19,7 @@
 #include "lenv_ln.cuh"
 #include "lenv_icm.cuh"
 #include "lenv_wavechain_host.h"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -1538,25 +1539,24 @@ static int td3_layout(const lenv_td3_cfg *cfg, Td3Args &a, size_t *lds_bytes)
     if (cap > cfg->rb_size) cap = cfg->rb_size;
     a.rb_cap = cap < 1 ? 1 : cap;
     const int RB = B > T ? B : T;                               // rows of the batch buffers
-    int64_t off = 0;
-    auto take = [&](int64_t n) { int64_t r = off; off += (n + 3) & ~(int64_t)3; return r; };
-    a.a_params = take(a.P); a.a_targets = take(a.P); a.a_m = take(a.P); a.a_v = take(a.P); a.a_grad = take(a.P);
-    a.a_replay = take(a.rb_cap * a.RS);
-    a.a_xc = take((int64_t)RB * T3_SA); a.a_xn = take((int64_t)RB * T3_SA); a.a_xa = take((int64_t)RB * T3_SA);
-    for (int l = 0; l < T3_MAXL; ++l) { a.a_hc1[l] = take((int64_t)RB * H); a.a_hc2[l] = take((int64_t)RB * H); a.a_ha[l] = take((int64_t)RB * H); a.a_ht[l] = take((int64_t)RB * H); }
-    a.a_d[0] = take((int64_t)RB * H); a.a_d[1] = take((int64_t)RB * H);
-    a.a_dx = take((int64_t)RB * T3_SA); a.a_act = take((int64_t)RB * T3_A); a.a_th = take((int64_t)RB * T3_A); a.a_dz = take((int64_t)RB * T3_A);
-    a.a_meter = take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
+    lenv_host::ArenaCursor c;
+    a.a_params = c.take(a.P); a.a_targets = c.take(a.P); a.a_m = c.take(a.P); a.a_v = c.take(a.P); a.a_grad = c.take(a.P);
+    a.a_replay = c.take(a.rb_cap * a.RS);
+    a.a_xc = c.take((int64_t)RB * T3_SA); a.a_xn = c.take((int64_t)RB * T3_SA); a.a_xa = c.take((int64_t)RB * T3_SA);
+    for (int l = 0; l < T3_MAXL; ++l) { a.a_hc1[l] = c.take((int64_t)RB * H); a.a_hc2[l] = c.take((int64_t)RB * H); a.a_ha[l] = c.take((int64_t)RB * H); a.a_ht[l] = c.take((int64_t)RB * H); }
+    a.a_d[0] = c.take((int64_t)RB * H); a.a_d[1] = c.take((int64_t)RB * H);
+    a.a_dx = c.take((int64_t)RB * T3_SA); a.a_act = c.take((int64_t)RB * T3_A); a.a_th = c.take((int64_t)RB * T3_A); a.a_dz = c.take((int64_t)RB * T3_A);
+    a.a_meter = c.take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
     {   // use_layer_norm: normalised rows / 1 / sqrt(var + eps) of the LayerNorm positions of the passes that are differentiated
         const bool ln = a.actor.ln != 0;
-        for (int n = 0; n < 3; ++n) for (int l = 0; l < T3_MAXL; ++l) a.a_xh[n][l] = take(ln && l >= 1 && l < L ? (int64_t)RB * H : 0);
-        a.a_rstd = take(ln ? 3 * (int64_t)T3_MAXL * B : 0);
+        for (int n = 0; n < 3; ++n) for (int l = 0; l < T3_MAXL; ++l) a.a_xh[n][l] = c.take(ln && l >= 1 && l < L ? (int64_t)RB * H : 0);
+        a.a_rstd = c.take(ln ? 3 * (int64_t)T3_MAXL * B : 0);
     }
     a.a_se = a.a_seT = a.a_xse = a.a_nse = 0;
     if (cfg->virtual_env) {
         if ((int64_t)RB * H < Hrn) return LENV_ERR_UNSUPPORTED;          // the SE's hidden rows reuse the agent's temporaries
-        a.a_se = take(a.P_rn); a.a_seT = take(a.P_rn); a.a_xse = take(T3_SA); a.a_nse = take(T3_S + 2);
-    } else if (cfg->rn_layers > 1) a.a_se = take(a.P_rn);
+        a.a_se = c.take(a.P_rn); a.a_seT = c.take(a.P_rn); a.a_xse = c.take(T3_SA); a.a_nse = c.take(T3_S + 2);
+    } else if (cfg->rn_layers > 1) a.a_se = c.take(a.P_rn);
     a.P_icm = 0;
     for (int i = 0; i < IB_COUNT; ++i) a.a_icm[i] = 0;
     if (cfg->icm_enabled) {
@@ -1566,9 +1566,9 @@ static int td3_layout(const lenv_td3_cfg *cfg, Td3Args &a, size_t *lds_bytes)
         a.P_icm = n.P;
         int64_t sz[IB_COUNT];
         icm_buffer_sizes(n, B, sz);
-        for (int i = 0; i < IB_COUNT; ++i) a.a_icm[i] = take(sz[i]);
+        for (int i = 0; i < IB_COUNT; ++i) a.a_icm[i] = c.take(sz[i]);
     }
-    a.arena_stride = (off + 63) & ~(int64_t)63;
+    a.arena_stride = c.total();
     if (lenv_wc_td3_shape(cfg)) {                             // the wave-chain kernel (td3_wavechain.hip) keeps its own arena layout
         const int64_t wfl = lenv_wc_td3_arena_floats(cfg, a.rb_cap, a.RS);
         if (wfl > a.arena_stride) a.arena_stride = wfl;
@@ -1657,29 +1657,19 @@ static int td3_launch(const lenv_td3_cfg *cfg, const lenv_chain_hp *hp, const le
                       int64_t chains, void *workspace, size_t workspace_bytes, const lenv_td3_out *out, bool segment, int32_t ep_begin,
                       int32_t ep_end, int64_t *resume, void *stream)
 {
-    if (hp && (!hp->lr || !hp->batch_size || !hp->q_hidden || !hp->q_layers)) return LENV_ERR_INVALID;
-    if (cfg && cfg->icm_enabled && (!icm || !icm->icm_init)) return LENV_ERR_INVALID;
-    if (!cfg || !agent_init || !out || !out->score || !workspace || chains < 0) return LENV_ERR_INVALID;
-    if (!theta && cfg->reward_env_type != 0) return LENV_ERR_INVALID;
-    if (eps && (!worker || !sign)) return LENV_ERR_INVALID;
-    if (cfg->rng_mode == LENV_RNG_TAPE && !tapes) return LENV_ERR_INVALID;
-    if (cfg->rng_mode == LENV_RNG_COUNTER && !rng_keys) return LENV_ERR_INVALID;
-    if (segment && (!resume || ep_begin < 0 || ep_begin >= ep_end || ep_end > cfg->train_episodes)) return LENV_ERR_INVALID;
+    const lenv_host::Segment seg{segment, ep_begin, ep_end, resume};
+    if (!lenv_host::launch_args_ok(cfg, hp, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, out, seg)) return LENV_ERR_INVALID;
+    if ((!theta && cfg->reward_env_type != 0) || !lenv_host::icm_args_ok(cfg, icm)) return LENV_ERR_INVALID;
     if (chains == 0) return LENV_OK;
     Td3Args a;
     size_t lds_bytes;
     const int rc = td3_layout(cfg, a, &lds_bytes);
     if (rc != LENV_OK) return rc;
     if (workspace_bytes < (size_t)chains * a.arena_stride * sizeof(float)) return LENV_ERR_WORKSPACE;
-    a.cfg = *cfg;
-    a.ep_begin = segment ? ep_begin : 0; a.ep_end = segment ? ep_end : cfg->train_episodes; a.resume = segment ? resume : nullptr;
-    a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.agent_init = agent_init; a.rng_keys = rng_keys;
-    if (tapes) a.tapes = *tapes; else a.tapes = lenv_td3_tapes{};
-    a.arena = static_cast<float *>(workspace);
-    a.out = *out;
-    a.hp_lr = hp ? hp->lr : nullptr; a.hp_batch = hp ? hp->batch_size : nullptr;
-    a.hp_hidden = hp ? hp->q_hidden : nullptr; a.hp_layers = hp ? hp->q_layers : nullptr;
-    a.icm_init = cfg->icm_enabled ? icm->icm_init : nullptr; a.icm_final = cfg->icm_enabled ? icm->icm_final : nullptr;
+    lenv_host::fill_args(a, cfg, theta, eps, worker, sign, agent_init, rng_keys, tapes, workspace, out);
+    lenv_host::fill_segment(a, cfg, seg);
+    lenv_host::fill_hp(a, hp);
+    lenv_host::fill_icm(a, cfg, icm);
     void (*kern)(const Td3Args) = nullptr;
     // narrow one-hidden-layer agent nets (every chain's: cfg carries the maxima of a *_vary launch) without LayerNorm / ICM whose activation
     // matrix fits the idle staging buffers: the DIRECT instantiations (kernel_variant NO_DIRECT keeps the product queue: A/B runs, tests)
@@ -1718,10 +1708,7 @@ static int td3_launch(const lenv_td3_cfg *cfg, const lenv_chain_hp *hp, const le
             else if (matches(kTd3Shapes[4])) kern = td3_rn_inner_kernel<false, LENV_ENV_CMC, 4>;
         }
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return LENV_ERR_LAUNCH;
-    hipLaunchKernelGGL(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, stream, a);
 }
 
 extern "C" int lenv_td3_rn_inner_loop_icm(const lenv_td3_cfg *cfg, const lenv_chain_hp *hp, const lenv_icm_io *icm, const float *theta,

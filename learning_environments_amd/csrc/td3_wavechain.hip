@@ -18,6 +18,7 @@
 //   W1t[24][128] (rows >= in_dim zero) b1[128] | W2t[128][128] b2[128] | Wo[128][8] (columns >= out_dim zero) bo[8]
 #include "lenv_wavechain.cuh"
 #include "lenv_wavechain_host.h"
+#include "lenv_host.h"
 
 namespace lenv {
 
@@ -953,7 +954,7 @@ __global__ __launch_bounds__(NT) void td3_wavechain_kernel(const T3wArgs a)
     const uint64_t key = a.rng_keys[chain];
     int status = 0;
     // ---- team barrier (G > 1, wc::team_barrier): every member has finished its share of a phase and its arena writes are visible to the
-    // others.  The chain's counter and the launch's give-up word are zeroed by t3w_team_reset_kernel in front of the launch.
+    // others.  The chain's counter and the launch's give-up word are zeroed by wc_team_reset_kernel (wavechain_team_reset.hip) in front of the launch.
     TeamSync tsync{ team_bar, reinterpret_cast<unsigned *>(a.arena + a.a_bar) + 8, ictrl + 5, 0u, G, false, false };
     // (no copies of the give-up flag or counters in kernel-lifetime variables: what lives across the calls of the learn step ends up in
     // scratch memory and costs a round trip at every use; tsync.dead is read where it matters)
@@ -1701,32 +1702,20 @@ static int64_t t3w_env_arena_params(const lenv_td3_cfg *cfg)
     return cfg->rn_layers > 1 ? lenv_rn_num_params(cfg->reward_env_type, cfg->state_dim, cfg->info_dim, cfg->rn_hidden, cfg->rn_layers) : 0;
 }
 
-static void t3w_offsets(const lenv_td3_cfg *cfg, int64_t rb_cap, int RS, T3wArgs &a, int64_t *total)
+// one chain's arena: places the buffers in `a`, returns its floats
+static int64_t t3w_offsets(const lenv_td3_cfg *cfg, int64_t rb_cap, int RS, T3wArgs &a)
 {
     const int shape = lenv_wc_td3_shape(cfg);
     const int SA = 23, B = kT3wShapes[shape].B, NBK = B / 32;
-    int64_t off = 0;
-    auto take = [&](int64_t n) { int64_t r = off; off += (n + 3) & ~(int64_t)3; return r; };
-    a.a_par = take(5 * 3 * (int64_t)t3p::PN); a.a_xc = take((int64_t)B * SA); a.a_xn = take((int64_t)B * SA); a.a_xa = take((int64_t)B * SA);
-    a.a_th = take((int64_t)B * 6); a.a_dump = take((int64_t)T3W_NDUMP * NBK * wc::BLK); a.a_replay = take(rb_cap * RS);
-    a.a_meter = take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
-    a.a_gx = take(2 * (int64_t)B + (int64_t)B * 6);             // team exchange: dq1 | dq2 | dz
-    a.a_bar = take(16);                                          // team barrier counter (one cache line of its own would be 32 floats; the slot is padded below)
-    a.a_w2u = take(3 * (int64_t)wc::IMG);                        // team path: unit-major copies W2u[j][k] of the three online second layers
-    a.a_rn = take(t3w_env_arena_params(cfg));                   // a deeper reward net / the VirtualEnv's nets
-    *total = (off + 63) & ~(int64_t)63;
-}
-
-namespace lenv {
-// the team barrier counters start at 0: a kernel rather than a memset node (see the status word in the fused kernels)
-__global__ void t3w_team_reset_kernel(float *arena, int64_t arena_stride, int64_t a_bar, int64_t chains)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < chains) { unsigned *b = reinterpret_cast<unsigned *>(arena + c * arena_stride + a_bar); b[0] = 0u; b[8] = 0u; }
-#ifdef LENV_DIAG_TEAM_TIMES
-    if (c == 0) *reinterpret_cast<unsigned long long *>(arena + a_bar + 10) = __builtin_amdgcn_s_memrealtime();
-#endif
-}
+    lenv_host::ArenaCursor c;
+    a.a_par = c.take(5 * 3 * (int64_t)t3p::PN); a.a_xc = c.take((int64_t)B * SA); a.a_xn = c.take((int64_t)B * SA); a.a_xa = c.take((int64_t)B * SA);
+    a.a_th = c.take((int64_t)B * 6); a.a_dump = c.take((int64_t)T3W_NDUMP * NBK * wc::BLK); a.a_replay = c.take(rb_cap * RS);
+    a.a_meter = c.take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
+    a.a_gx = c.take(2 * (int64_t)B + (int64_t)B * 6);           // team exchange: dq1 | dq2 | dz
+    a.a_bar = c.take(16);                                        // team barrier counter (one cache line of its own would be 32 floats; the slot is padded below)
+    a.a_w2u = c.take(3 * (int64_t)wc::IMG);                      // team path: unit-major copies W2u[j][k] of the three online second layers
+    a.a_rn = c.take(t3w_env_arena_params(cfg));                 // a deeper reward net / the VirtualEnv's nets
+    return c.total();
 }
 
 static size_t t3w_lds_bytes(int shape, int P_rn)
@@ -1756,17 +1745,11 @@ static void (*t3w_kernel(int shape))(const T3wArgs)
 // automatic, 1 = the plain launch).
 static int t3w_pick_team(const lenv_td3_cfg *cfg, int64_t chains)
 {
-    const int want = cfg->team_size > 0 ? cfg->team_size : 8;
-    if (want == 1 || chains < 1) return 1;
     const int P_rn = cfg->virtual_env ? 0 : (int)lenv_rn_num_params(cfg->reward_env_type, cfg->state_dim, cfg->info_dim, cfg->rn_hidden, cfg->rn_layers);
     const int shape = lenv_wc_td3_shape(cfg);
     if (!shape) return 1;
-    void (*kern)(const T3wArgs) = t3w_kernel(shape);
-    const int64_t padded = 8 * ((chains + 7) / 8);
-    const int NBK = kT3wShapes[shape].B / 32;
-    for (int G : { 8, 6, 4, 3, 2 })
-        if (NBK % G == 0 && G <= want && lenv_team_grid_resident(reinterpret_cast<const void *>(kern), wc::NT, t3w_lds_bytes(shape, P_rn), padded * G)) return G;
-    return 1;
+    return lenv_host::pick_team({ 8, 6, 4, 3, 2 }, cfg->team_size, kT3wShapes[shape].B / 32, chains, reinterpret_cast<const void *>(t3w_kernel(shape)), wc::NT,
+                                t3w_lds_bytes(shape, P_rn));
 }
 
 int lenv_wc_td3_team(const lenv_td3_cfg *cfg, int64_t chains) { return t3w_pick_team(cfg, chains); }
@@ -1774,9 +1757,7 @@ int lenv_wc_td3_team(const lenv_td3_cfg *cfg, int64_t chains) { return t3w_pick_
 int64_t lenv_wc_td3_arena_floats(const lenv_td3_cfg *cfg, int64_t rb_cap, int RS)
 {
     T3wArgs a;
-    int64_t total;
-    t3w_offsets(cfg, rb_cap, RS, a, &total);
-    return total;
+    return t3w_offsets(cfg, rb_cap, RS, a);
 }
 
 int lenv_wc_td3_launch(const lenv_td3_cfg *cfg, const float *theta, const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
@@ -1785,26 +1766,16 @@ int lenv_wc_td3_launch(const lenv_td3_cfg *cfg, const float *theta, const float 
 {
     T3wArgs a;
     a.cfg = *cfg;
-    a.theta = theta; a.eps = eps; a.worker = worker; a.sign = sign; a.agent_init = agent_init; a.rng_keys = rng_keys;
+    lenv_host::fill_population(a, theta, eps, worker, sign, agent_init, rng_keys);
     a.arena = arena; a.arena_stride = arena_stride; a.out = *out; a.rb_cap = rb_cap; a.RS = RS; a.P = P; a.Pa = Pa; a.Pc = Pc; a.P_rn = P_rn;
-    int64_t total;
-    t3w_offsets(cfg, rb_cap, RS, a, &total);
-    if (total > arena_stride) return LENV_ERR_WORKSPACE;
+    if (t3w_offsets(cfg, rb_cap, RS, a) > arena_stride) return LENV_ERR_WORKSPACE;
     const int shape = lenv_wc_td3_shape(cfg);
     if (!shape) return LENV_ERR_UNSUPPORTED;
     const size_t lds_bytes = t3w_lds_bytes(shape, P_rn);
     if (lds_bytes > 160 * 1024) return LENV_ERR_UNSUPPORTED;
-    void (*kern)(const T3wArgs) = t3w_kernel(shape);
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) return LENV_ERR_LAUNCH;
     a.chains = chains;
     a.G = t3w_pick_team(cfg, chains);
-    unsigned grid = (unsigned)chains;
-    if (a.G > 1) {
-        grid = (unsigned)(8 * ((chains + 7) / 8) * a.G);
-        hipLaunchKernelGGL(t3w_team_reset_kernel, dim3((unsigned)((chains + 255) / 256)), dim3(256), 0, stream, arena, arena_stride, a.a_bar, chains);
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(wc::NT), lds_bytes, stream, a);
-    return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+    return lenv_host::launch_team(t3w_kernel(shape), wc::NT, lds_bytes, stream, a);
 }
 
 #ifdef LENV_PHASE_TIMING_SUB
