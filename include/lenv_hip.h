@@ -788,6 +788,31 @@ int lenv_rn_shape_rows(int32_t type, const lenv_mlp_desc *rn /*HOST, types 1-8*/
                        const float *theta, const float *s, const float *s2, const float *info, const float *r, int64_t rows,
                        float *out, void *stream);
 
+/*
+ * One RewardEnv step for a whole NES population in one launch (the non-virtual half of EnvWrapper.step_population): chain c steps its own
+ * instance of a vector-state real env on its action up to `repeat` times -- the same_action_num loop of EnvWrapper._step_real
+ * (envs/env_wrapper.py:48-70): stop after the step that reports done, the TimeLimit at max_steps counts as done -- and shapes every step's
+ * reward with the reward net W_c, W_c[i] = fmaf(sign[c], eps[worker[c]][i], theta[i]) (eps may be NULL: the plain theta; type 0 reads
+ * neither).  The shaped rewards are added in fp64, like the .item() floats Python adds, and rounded once.
+ * env_id: LENV_ENV_CARTPOLE / ACROBOT / MOUNTAINCAR (action int32 [chains], state [chains,4] fp64) or LENV_ENV_PENDULUM / CMC /
+ * CHEETAH_STANDIN (action float [chains,A], state [chains,2 | 2 | 17]); state, elapsed [chains]: the contract of lenv_real_env_step /
+ * lenv_cont_env_step, updated in place.  type, rn, state_dim, info_dim, gamma, theta's layout: as in lenv_rn_shape_rows (1-4 hidden layers,
+ * hidden <= 256, <= 64 net inputs, the shared LayerNorm's weight | bias behind the second Linear); eps rows have theta's length.  The info
+ * vector is the stand-in's own (info_dim 4).  Outputs: obs [chains,state_dim] the last observation, reward [chains] the sum, done [chains]
+ * the last step's flag.  With repeat 1 the outputs are bit for bit those of the env step entry followed by lenv_rn_shape_rows on the
+ * chain's W_c: the same device functions run.
+ * LENV_ERR_INVALID: a NULL action / state / elapsed / obs / reward / done, theta NULL for a type other than 0, rn NULL for types 1-8,
+ * chains < 0, repeat < 1, eps without worker / sign, state_dim that is not the env's, an info type on an env without an info vector (the
+ * reference's ValueError) or with an info_dim that is not the stand-in's.  LENV_ERR_UNSUPPORTED: an unknown type or env_id, a net outside
+ * the shapes above, repeat > 64, chains >= 2^31.  chains == 0 returns LENV_OK after the pointer checks and before the descriptor is looked
+ * at, like lenv_se_step_population.
+ */
+int lenv_rn_step_population(int32_t env_id, int32_t max_steps, int32_t type, const lenv_mlp_desc *rn /*HOST, types 1-8*/,
+                            int32_t state_dim, int32_t info_dim, double gamma,
+                            const float *theta, const float *eps, const int32_t *worker, const float *sign,
+                            int64_t chains, int32_t repeat, const void *action /* int32 [chains] | float [chains,A] */,
+                            double *state, int32_t *elapsed, float *obs, float *reward, float *done, void *stream);
+
 /* HalfCheetah-v3 STAND-IN reset / step for n instances (state [n,17] float64, action [n,6], obs [n,17]); same contract as
  * lenv_real_env_reset / lenv_real_env_step. */
 int lenv_cheetah_standin_reset(const uint64_t *keys, const int64_t *episode, int64_t n, double *state, float *obs,

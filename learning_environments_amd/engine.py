@@ -137,6 +137,51 @@ def se_step_population_vec(descs, theta, eps, worker, sign, state, action, repea
     return ns, r, d
 
 
+# observation words, fp64 state words and action width of the vector-state real envs (csrc/lenv_device.cuh); action width 0 = a discrete index
+REAL_ENV_DIMS = {_lib.ENV[k]: v for k, v in {"CartPole-v0": (4, 4, 0), "Acrobot-v1": (6, 4, 0), "MountainCar-v0": (2, 4, 0), "HalfCheetah-v3": (17, 17, 6),
+                                                "Pendulum-v0": (3, 2, 1), "MountainCarContinuous-v0": (2, 2, 1)}.items()}
+
+
+def rn_step_population(env_id, max_steps, rtype, rn_desc, info_dim, gamma, theta, eps, worker, sign, action, state, elapsed, repeat=1):
+    """One RewardEnv step of every chain in one launch: chain c steps its own instance of the real env `env_id` (state fp64 [chains,SD],
+    elapsed int32 [chains], both updated in place) on its action -- int32 [chains] for the discrete envs, fp32 [chains,A] for the continuous
+    ones -- up to `repeat` times (same_action_num of EnvWrapper._step_real: shaped rewards summed, stop after the step that reports done) and
+    shapes the rewards with theta + sign[c]*eps[worker[c]] (eps None: the plain theta; `theta` None for reward type 0).  Returns
+    (obs [chains,S], reward [chains], done [chains]); device tensors."""
+    dev = require_device()
+    if int(env_id) not in REAL_ENV_DIMS:
+        raise NotImplementedError("lenv_rn_step_population: no vector-state real env with id %d" % int(env_id))
+    S, SD, A = REAL_ENV_DIMS[int(env_id)]
+    _chk(state, torch.float64, "state"); _chk(elapsed, torch.int32, "elapsed")
+    if state.dim() != 2 or state.shape[1] != SD:
+        raise ValueError("state must be [chains,%d]" % SD)
+    chains = state.shape[0]
+    if tuple(elapsed.shape) != (chains,):
+        raise ValueError("elapsed must be [chains]")
+    if A == 0:
+        _chk(action, torch.int32, "action")
+        if tuple(action.shape) != (chains,):
+            raise ValueError("action must be int32 [chains] next to state [chains,%d]" % SD)
+    else:
+        _chk(action, torch.float32, "action")
+        if tuple(action.shape) != (chains, A):
+            raise ValueError("action must be [chains,%d] next to state [chains,%d]" % (A, SD))
+    _chk(theta, torch.float32, "theta"); _chk(eps, torch.float32, "eps"); _chk(worker, torch.int32, "worker"); _chk(sign, torch.float32, "sign")
+    if eps is not None:
+        if theta is None or eps.dim() != 2 or eps.shape[1] != theta.numel():
+            raise ValueError("eps must be [pop,%d], a row per worker next to theta" % (0 if theta is None else theta.numel()))
+        if worker is None or sign is None or tuple(worker.shape) != (chains,) or tuple(sign.shape) != (chains,):
+            raise ValueError("worker and sign must be [chains] next to eps")
+    obs = torch.empty((chains, S), dtype=torch.float32, device=dev)
+    r = torch.empty(chains, dtype=torch.float32, device=dev)
+    d = torch.empty(chains, dtype=torch.float32, device=dev)
+    rc = _lib.lib().lenv_rn_step_population(int(env_id), int(max_steps), int(rtype), C.byref(rn_desc) if rn_desc is not None else None, S,
+                                            int(info_dim), float(gamma), _ptr(theta), _ptr(eps), _ptr(worker), _ptr(sign), chains, int(repeat),
+                                            _ptr(action), _ptr(state), _ptr(elapsed), _ptr(obs), _ptr(r), _ptr(d), _stream())
+    _lib.check(rc, "lenv_rn_step_population")
+    return obs, r, d
+
+
 def qnet_td_forward(qd, online, target, replay, idx, gamma):
     """online/target [chains,P]; replay [chains,cap,row_stride]; idx int32 [chains,B] -> (q_sa, y) [chains,B]."""
     dev = require_device()

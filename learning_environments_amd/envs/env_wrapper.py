@@ -2,16 +2,27 @@
 
 Same methods, argument meaning and return conventions: `step(action, state=None)` returns the 3-tuple
 `(next_state, reward, done)` of CPU fp32 tensors.  New (batched fast path, not in the reference):
-`step_population` evaluates many NES perturbations of a virtual env in one kernel launch.
+`step_population` evaluates many NES perturbations of a virtual env, or of a reward env over a vector-state real env, in one kernel
+launch.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import engine
+from .. import _lib, engine
 from ..utils import from_one_hot_encoding, to_one_hot_encoding
+from .grid_env import GridEnv
+from .reward_env import RewardEnv
 from .spaces import Discrete
 from .virtual_env import VirtualEnv
+
+
+class PopulationState(object):
+    """`chains` instances of a real env on the device, as lenv_real_env_step / lenv_cont_env_step keep them: state fp64 [chains,SD], elapsed
+    int32 [chains] (steps of the running episode, for the TimeLimit) and obs fp32 [chains,S], the observation of `state`."""
+
+    def __init__(self, state, elapsed, obs):
+        self.state, self.elapsed, self.obs = state, elapsed, obs
 
 
 class EnvWrapper(nn.Module):
@@ -53,13 +64,53 @@ class EnvWrapper(nn.Module):
         obs_t = as_f32(obs)
         return (obs_t.unsqueeze(0) if obs_t.dim() == 0 else obs_t), as_f32(total), as_f32(done)
 
+    def _real_env(self):
+        """The device-resident real env behind a non-virtual wrapper; a gridworld has no one-step population path (theirs is the QL kernel)."""
+        real = self.env.real_env if isinstance(self.env, RewardEnv) else self.env
+        if isinstance(real, GridEnv):
+            raise NotImplementedError("step_population is not defined for a gridworld RewardEnv: its population path is the fused Q-learning kernel")
+        return real
+
+    def reset_population(self, chains, seed=0, episode=0):
+        """Fresh episodes of `chains` independent instances of the real env behind a RewardEnv (or of the bare real env): chain c draws its
+        reset state with the key lenv_chain_key(seed, 0, c, 3) -- chain 0 is the instance a DeviceRealEnv seeded with `seed` resets to at
+        that episode.  Returns the PopulationState `step_population` advances."""
+        if self.is_virtual_env():
+            raise NotImplementedError("reset_population is defined for real and reward envs: a virtual env keeps no state of its own")
+        real = self._real_env()
+        dev = engine.require_device()
+        L = _lib.lib()
+        keys = np.array([L.lenv_chain_key(int(seed), 0, c, 3) for c in range(chains)], np.uint64).view(np.int64)
+        keys = torch.from_numpy(keys).to(dev)
+        ep = torch.full((chains,), int(episode), dtype=torch.int64, device=dev)
+        S, SD, _ = engine.REAL_ENV_DIMS[real.env_id]
+        st = PopulationState(torch.zeros((chains, SD), dtype=torch.float64, device=dev), torch.zeros(chains, dtype=torch.int32, device=dev),
+                             torch.zeros((chains, S), dtype=torch.float32, device=dev))
+        reset = L.lenv_cont_env_reset if real.continuous else L.lenv_real_env_reset
+        _lib.check(reset(real.env_id, engine._ptr(keys), engine._ptr(ep), chains, engine._ptr(st.state), engine._ptr(st.obs),
+                         engine._ptr(st.elapsed), engine._stream()), "lenv_real_env_reset")
+        return st
+
     def step_population(self, actions, states, eps=None, worker=None, sign=None, repeat=1):
-        """Batched fast path: chain c steps the SE with weights theta + sign[c]*eps[worker[c]], `repeat` times on the same action
+        """Batched fast path.  Virtual env: chain c steps the SE with weights theta + sign[c]*eps[worker[c]], `repeat` times on the same action
         (what `same_action_num` does in `step`: rewards summed, next state / done of the last step).
         Discrete action space: actions int32 [chains] (or [chains,n]); continuous: fp32 [chains,A] (or [chains,n,A]).
-        states fp32 [chains,S] (or [chains,n,S]), all on the device.  Returns device tensors."""
+        states fp32 [chains,S] (or [chains,n,S]), all on the device.  Returns device tensors.
+        Reward env over a vector-state real env (or the bare real env: reward type 0): chain c steps its own instance of the real env, up to
+        `repeat` times and until it reports done, and shapes the rewards with the reward net theta + sign[c]*eps[worker[c]]; `states` is the
+        PopulationState of `reset_population`, advanced in place; actions int32 [chains] / fp32 [chains,A]; gamma is the value
+        `set_agent_params` stored.  Returns device tensors (obs, reward, done)."""
         if not self.is_virtual_env():
-            raise NotImplementedError("step_population is defined for virtual envs")
+            real = self._real_env()
+            rn = self.env if isinstance(self.env, RewardEnv) else None
+            rtype = rn.reward_env_type if rn is not None else 0
+            gamma = rn.gamma if rn is not None and rn.gamma is not None else 0.0
+            obs, reward, done = engine.rn_step_population(
+                real.env_id, self.max_episode_steps(), rtype, rn.desc() if rn is not None else None, rn.info_dim if rn is not None else 0, gamma,
+                rn.step_params() if rn is not None else None, rn.step_eps(eps) if rn is not None else None, worker, sign, actions, states.state,
+                states.elapsed, repeat=repeat)
+            states.obs = obs
+            return obs, reward, done
         args = (self.env.descs(), self.env.step_params(), self.env.step_eps(eps), worker, sign, states)
         if not self.has_discrete_action_space():
             return engine.se_step_population_vec(*args, actions, repeat=repeat)

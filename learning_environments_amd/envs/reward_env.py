@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, engine
-from ..models.model_utils import FlatParams, build_nn_from_config, linear_params
+from ..models.model_utils import FlatParams, build_nn_from_config, linear_params, mlp_desc, mlp_params
 from .grid_env import GridEnv
 
 
@@ -63,6 +63,40 @@ class RewardEnv(nn.Module):
             self.to(dev)
             self._flat = FlatParams(self, dev)
         return self._flat.flat
+
+    # ---- what lenv_rn_step_population reads (EnvWrapper.step_population on a vector-state real env) ----
+    def desc(self):
+        """lenv_mlp_desc of the reward net; None for the types without an MLP (0: no net is read, 101 / 102: one Linear)."""
+        return mlp_desc(self.reward_net, self.activation_fn) if 1 <= self.reward_env_type <= 8 else None
+
+    def _has_layer_norm(self):
+        return self.desc() is not None and any(isinstance(m, nn.LayerNorm) for m in self.reward_net)
+
+    def step_params(self):
+        """theta itself, or -- a `use_layer_norm` net -- a copy with the LayerNorm weight | bias behind the second Linear (lenv_mlp_desc
+        layout; the module is not part of theta: NES never touches it).  None for type 0."""
+        if self.reward_env_type == 0:
+            return None
+        flat = self.flat_params()
+        if not self._has_layer_norm():
+            return flat
+        return torch.cat([p.detach().reshape(-1).to(flat.device, torch.float32) for p in mlp_params(self.reward_net)])
+
+    def step_eps(self, eps):
+        """eps rows [pop, P_theta] in the layout of step_params(): zero columns where the (never perturbed) LayerNorm block sits."""
+        if eps is None or self.reward_env_type == 0:
+            return None
+        if not self._has_layer_norm():
+            return eps
+        cols, off = [], 0
+        lin = set(id(p) for p in linear_params(self))
+        for p in mlp_params(self.reward_net):
+            if id(p) in lin:
+                cols.append(torch.arange(off, off + p.numel(), device=eps.device))
+            off += p.numel()
+        wide = torch.zeros((eps.shape[0], off), dtype=eps.dtype, device=eps.device)
+        wide[:, torch.cat(cols)] = eps
+        return wide
 
     def _apply(self, fn, *a, **k):
         self._flat = None

@@ -317,6 +317,67 @@ import bench  # noqa: E402  (the byte / FLOP models live next to the contract li
 HBM_PEAK_GBPS, MFMA_F32_PEAK_TFLOPS = bench.HBM_PEAK_GBPS, bench.MFMA_F32_PEAK_TFLOPS
 
 
+def run_rn_step(name, chains=192, hidden=128, repeat=1, runs=7, iters=(40, 2000)):
+    """One RewardEnv step of `chains` chains on the HalfCheetah stand-in (reward type 2, a `hidden`-wide one-hidden-layer PReLU reward net, 3 chains
+    per NES worker with signs 0, +1, -1): lenv_rn_step_population against the composition of the older entries -- per repeat one lenv_cont_env_step
+    launch and `chains` lenv_rn_shape_rows launches on the chain's perturbed theta (perturbed ahead of the clock) -- `runs` timed runs of `iters`
+    = (composed, one launch) steps each, so that either window is a good part of a second, in alternation after a warm-up of each; medians and ranges per step; the two must agree bit for bit before anything is timed."""
+    import numpy as np
+    from learning_environments_amd import _lib, engine
+    dev = engine.require_device()
+    env_id, S, SD, A, max_steps, rtype, gamma = _lib.ENV["HalfCheetah-v3"], 17, 17, 6, 1000, 2, 0.99
+    torch.manual_seed(0)
+    desc = engine.mlp_desc(S, hidden, 1, 1, "prelu")
+    P = engine.mlp_num_params(desc)
+    pop = (chains + 2) // 3
+    theta, eps = (0.3 * torch.randn(P)).to(dev), (0.1 * torch.randn(pop, P)).to(dev)
+    worker = (torch.arange(chains, dtype=torch.int32) // 3).to(dev)
+    sign = torch.tensor([(0.0, 1.0, -1.0)[c % 3] for c in range(chains)], device=dev)
+    W = (sign[:, None] * eps[worker.long()] + theta).contiguous()            # signs 0, +1, -1: the product is exact, so this is the kernel's fmaf
+    action = (torch.rand(chains, A) * 2 - 1).to(dev)
+    L = _lib.lib()
+    keys = torch.from_numpy(np.array([L.lenv_chain_key(0, 0, c, 3) for c in range(chains)], np.uint64).view(np.int64)).to(dev)
+    state0, elapsed0 = torch.zeros((chains, SD), dtype=torch.float64, device=dev), torch.zeros(chains, dtype=torch.int32, device=dev)
+    obs0 = torch.zeros((chains, S), dtype=torch.float32, device=dev)
+    _lib.check(L.lenv_cont_env_reset(env_id, engine._ptr(keys), engine._ptr(torch.zeros(chains, dtype=torch.int64, device=dev)), chains, engine._ptr(state0),
+                                     engine._ptr(obs0), engine._ptr(elapsed0), engine._stream()), "lenv_cont_env_reset")
+
+    def composed():
+        st, el, s, total = state0.clone(), elapsed0.clone(), obs0, None
+        for _ in range(repeat):                      # (the stand-in ends through the TimeLimit only: no chain stops inside the repeat)
+            ob, r, d = torch.empty_like(obs0), torch.empty(chains, device=dev), torch.empty(chains, device=dev)
+            _lib.check(L.lenv_cont_env_step(env_id, max_steps, chains, engine._ptr(action), engine._ptr(st), engine._ptr(el), engine._ptr(ob), engine._ptr(r),
+                                            engine._ptr(d), engine._stream()), "lenv_cont_env_step")
+            shaped = torch.cat([engine.rn_shape_rows(rtype, desc, S, 0, gamma, W[c], s[c:c + 1], ob[c:c + 1], None, r[c:c + 1]) for c in range(chains)])
+            total = shaped.double() if total is None else total + shaped.double()
+            s = ob
+        return ob, total.float(), d, st, el
+
+    def fused():
+        st, el = state0.clone(), elapsed0.clone()
+        return engine.rn_step_population(env_id, max_steps, rtype, desc, 0, gamma, theta, eps, worker, sign, action, st, el, repeat=repeat) + (st, el)
+
+    same = all(torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8)) for a, b in zip(composed(), fused()))
+    assert same, "lenv_rn_step_population and the composition of the older entries differ"
+    forms, times = (("composed", composed, iters[0]), ("one_launch", fused, iters[1])), {"composed": [], "one_launch": []}
+    for it in range(runs + 1):
+        for label, fn, n in forms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                fn()
+            torch.cuda.synchronize()
+            if it:
+                times[label].append((time.perf_counter() - t0) / n)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    out = dict(config=name, chains=chains, repeat=repeat, rn_hidden=hidden, runs_each=runs, steps_per_run=dict(composed=iters[0], one_launch=iters[1]), launches_per_step=dict(composed=repeat * (chains + 1), one_launch=1),
+               us_median={k: 1e6 * v for k, v in med.items()}, us_min={k: 1e6 * min(v) for k, v in times.items()}, us_max={k: 1e6 * max(v) for k, v in times.items()},
+               us_samples={k: [round(1e6 * x, 1) for x in v] for k, v in times.items()}, composed_over_one_launch=med["composed"] / med["one_launch"],
+               bit_identical=bool(same))
+    print(json.dumps(out))
+    return out
+
+
 def _frac(model):
     def f(cfg, st, dt):
         nbytes, flops = model(cfg, st)
@@ -568,6 +629,11 @@ if __name__ == "__main__":
         # from the second
         run_ppo_episode_time("MountainCarContinuous RN (999 steps, same_action_num 5) + PPO 64x2, 1 999 rows x 80 epochs", "MountainCarContinuous-v0", 23)
         run_ppo_episode_time("HalfCheetah-standin RN (1000 steps) + PPO 128x2 tanh, 1 001 rows x 10 epochs", "HalfCheetah-v3", 7)
+    if "rn_step" in which:
+        # the one-step population API on a RewardEnv: 192 chains (64 workers) of the HalfCheetah stand-in, reward type 2, reward net 17-128-1, one
+        # launch against one env-step launch + 192 shaping launches per repeat; a warm-up, then the medians of 7 alternating runs
+        for repeat in (1, 2):
+            run_rn_step("HalfCheetah-standin RN 17-128-1 type 2, 192 chains, one step, repeat %d: composed entries / one launch" % repeat, repeat=repeat)
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
