@@ -813,6 +813,39 @@ int lenv_rn_step_population(int32_t env_id, int32_t max_steps, int32_t type, con
                             int64_t chains, int32_t repeat, const void *action /* int32 [chains] | float [chains,A] */,
                             double *state, int32_t *elapsed, float *obs, float *reward, float *done, void *stream);
 
+/*
+ * BaseAgent.test (agents/base_agent.py:155-227) of a population of trained DDQN / DuelingDDQN agents in one launch, as a call of its own:
+ * agent i runs T = cfg->test_episodes greedy episodes (DDQN.select_test_action / DuelingDDQN.select_test_action, ties towards the lower
+ * index) on the real env cfg->env_id (CartPole-v0, Acrobot-v1, MountainCar-v0).  The operations are those of the fused loops' closing test:
+ * the action same_action_num times or until done, TimeLimit at max_steps env steps, each agent step's reward the fp64 sum of its repeats
+ * rounded once to fp32 and added onto an fp32 episode return -- so on the final_online rows of a fused launch, with that launch's keys and
+ * episode_offset = the test episodes it ran before its closing test, `returns` are that launch's final_returns bit for bit.
+ * params [agents, P]: rows in the layout of lenv_dueling_se_inner_loop's final_online for the same cfg, P = lenv_dueling_num_params(cfg)
+ * (agent_kind 0: the Critic_DQN state dict, which is also the register-resident kernel's final_online; agent_kind 1: feature_stream |
+ * value_stream | advantage_stream; the shared LayerNorm's weight | bias behind the second Linear).  Episode e of agent i resets from the
+ * counter draw (rng_keys[i], test-reset stream, episode_offset[i] + e) -- episode_offset NULL = 0 -- or, when reset_states [agents, T, 4] is
+ * given, from reset_states[i][e] (the fp64 state words of lenv_real_env_reset).
+ * Outputs: returns [agents, T] fp64 (the fp32 episode returns), env_steps [agents, T] env steps taken, agent_steps [agents, T] actions
+ * chosen (what BaseAgent.test appends to episode_length_list, base_agent.py:213).  The row arrays -- all five or none -- receive the
+ * transitions, the third value BaseAgent.test returns: agent step n of episode e of agent i in slot [i][e][n] of
+ * row_state / row_next_state [agents, T, cap, state_dim], row_action (int32) / row_reward / row_done [agents, T, cap],
+ * cap = lenv_agent_test_rows_cap(cfg): the observation acted on, the action, the observation after the last repeat, the fp32 reward, the
+ * done flag with TimeLimit included.  Slots at or beyond agent_steps[i][e] are not written.
+ * Of cfg only env_id, state_dim, num_actions, max_steps, q_hidden, q_layers, q_act, q_prelu, agent_kind, feature_dim, q_layer_norm,
+ * test_episodes and same_action_num are read.  Admitted: the generic kernel's envelope -- q_layers 1..3, q_hidden 1..512, feature_dim 1..128
+ * (agent_kind 1), test_episodes 1..128, same_action_num 0..64, q_act other than PReLU, (env_id, state_dim, num_actions) one of the three
+ * envs; anything else LENV_ERR_UNSUPPORTED.  LENV_ERR_INVALID: agents < 0, a NULL cfg / params / rng_keys / returns / env_steps /
+ * agent_steps, row arrays given in part, agent_kind other than 0 / 1, max_steps < 1.  agents == 0: LENV_OK after these checks.  No workspace.
+ */
+/* HOST: rows one test episode can produce = ceil(max_steps / max(same_action_num, 1)); negative LENV_ERR_* as the launch would return */
+int64_t lenv_agent_test_rows_cap(const lenv_ddqn_cfg *cfg);
+int lenv_agent_test_population(const lenv_ddqn_cfg *cfg /*HOST*/, const float *params /*[agents, P]*/,
+                               const uint64_t *rng_keys /*[agents]*/, const int64_t *episode_offset /*[agents] or NULL = 0*/,
+                               const double *reset_states /*[agents, T, 4] or NULL*/, int64_t agents,
+                               double *returns /*[agents, T]*/, int32_t *env_steps /*[agents, T]*/, int32_t *agent_steps /*[agents, T]*/,
+                               float *row_state /*[agents, T, cap, S]*/, int32_t *row_action /*[agents, T, cap]*/, float *row_next_state,
+                               float *row_reward /*[agents, T, cap]*/, float *row_done, void *stream);
+
 /* HalfCheetah-v3 STAND-IN reset / step for n instances (state [n,17] float64, action [n,6], obs [n,17]); same contract as
  * lenv_real_env_reset / lenv_real_env_step. */
 int lenv_cheetah_standin_reset(const uint64_t *keys, const int64_t *episode, int64_t n, double *state, float *obs,

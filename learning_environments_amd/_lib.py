@@ -235,6 +235,8 @@ SIGNATURES = {
     "lenv_rn_num_params": (_i64, [_i32] * 5),
     "lenv_rn_shape_rows": (C.c_int, [_i32, _P(MlpDesc), _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "lenv_rn_step_population": (C.c_int, [_i32, _i32, _i32, _P(MlpDesc), _i32, _i32, _f64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lenv_agent_test_rows_cap": (_i64, [_P(DdqnCfg)]),
+    "lenv_agent_test_population": (C.c_int, [_P(DdqnCfg), _vp, _vp, _vp, _vp, _i64] + [_vp] * 8 + [_vp]),
     "lenv_td3_rn_workspace_bytes": (C.c_size_t, [_P(Td3Cfg), _i64]),
     "lenv_td3_num_params": (_i64, [_P(Td3Cfg), _P(_i64), _P(_i64)]),
     "lenv_td3_rn_team_size": (C.c_int, [_P(Td3Cfg), _i64]),

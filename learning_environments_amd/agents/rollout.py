@@ -1,0 +1,102 @@
+"""BaseAgent.test as a call of its own (reference agents/base_agent.py:155-227) for DDQN / DuelingDDQN agents that exist as parameter rows.
+
+The reference's agent.test(env) returns (reward_list, episode_length_list, replay_buffer); in the fused launches a test is only the closing part
+of training and yields final_returns alone.  `test_agents` runs the test of a whole population in one launch of lenv_agent_test_population
+(csrc/agent_test_population.hip) and hands every agent's triple back, the visited transitions as `ReplayRows` -- what the histogram / heatmap
+scripts merge and read with get_all()."""
+import numpy as np
+import torch
+
+from .. import engine
+from ..config import ddqn_cfg_from_config
+
+
+class ReplayRows(object):
+    """The transitions of a rollout in visiting order: what the scripts use of the reference's ReplayBuffer (get_all, merge_buffer, get_size),
+    append-only and without a capacity.  All five fields are CPU float32 tensors; actions / rewards / dones are columns [N,1]."""
+    FIELDS = ("states", "actions", "next_states", "rewards", "dones")
+
+    def __init__(self, state_dim, states=None, actions=None, next_states=None, rewards=None, dones=None):
+        self.state_dim = int(state_dim)
+        given = (states, actions, next_states, rewards, dones)
+        if any(g is None for g in given) and not all(g is None for g in given):
+            raise ValueError("ReplayRows takes all five fields or none")
+        widths = (self.state_dim, 1, self.state_dim, 1, 1)
+        self._parts = []
+        if states is not None:
+            part = tuple(torch.as_tensor(np.asarray(g.cpu() if torch.is_tensor(g) else g), dtype=torch.float32).reshape(-1, w) for g, w in zip(given, widths))
+            if len(set(p.shape[0] for p in part)) != 1:
+                raise ValueError("ReplayRows: the five fields must have one row count")
+            self._parts.append(part)
+
+    def get_all(self):
+        """(states [N,S], actions [N,1], next_states [N,S], rewards [N,1], dones [N,1]), episode after episode and step after step."""
+        if not self._parts:
+            return tuple(torch.zeros((0, w), dtype=torch.float32) for w in (self.state_dim, 1, self.state_dim, 1, 1))
+        if len(self._parts) > 1:
+            self._parts = [tuple(torch.cat([p[k] for p in self._parts]) for k in range(5))]
+        return self._parts[0]
+
+    def merge_buffer(self, other):
+        """Append another buffer's rows behind this one's (ReplayBuffer.merge_buffer)."""
+        rows = other.get_all()
+        if rows[0].shape[1] != self.state_dim:
+            raise ValueError("merge_buffer: state_dim %d next to %d" % (rows[0].shape[1], self.state_dim))
+        if rows[0].shape[0]:
+            self._parts.append(tuple(torch.as_tensor(r, dtype=torch.float32).cpu().reshape(-1, w)
+                                     for r, w in zip(rows, (self.state_dim, 1, self.state_dim, 1, 1))))
+
+    def get_size(self):
+        return int(sum(p[0].shape[0] for p in self._parts))
+
+    __len__ = get_size
+
+
+def rows_of_episodes(state, action, next_state, reward, done, counts):
+    """ReplayRows of one agent from padded per-episode arrays [T,cap(,S)] (host) and the rows each episode filled, counts [T]."""
+    S = state.shape[-1]
+    keep = np.arange(state.shape[1])[None, :] < np.asarray(counts)[:, None]          # [T,cap], row-major = episode after episode
+    return ReplayRows(S, state[keep], action[keep].astype(np.float32), next_state[keep], reward[keep], done[keep])
+
+
+def _device_i64(v, n, dev, name):
+    if v is None:
+        return None
+    if torch.is_tensor(v):
+        t = v.to(device=dev, dtype=torch.int64)
+    else:
+        a = np.asarray(v)
+        a = a.view(np.int64) if a.dtype == np.uint64 else a.astype(np.int64)
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    if t.dim() == 0:
+        t = t.repeat(n)
+    if tuple(t.shape) != (n,):
+        raise ValueError("%s must have one entry per agent" % name)
+    return t.contiguous()
+
+
+def test_agents(config, params, rng_keys, episode_offset=None, test_episodes=None, max_steps=None):
+    """agent.test(env=real_env) for every row of `params` (fp32 [agents,P], the layout of the fused loops' final_online for the agent
+    `config` selects: config['agents']['gtn']['agent_name'], default ddqn) on config's real env, in one launch.  rng_keys [agents] (uint64
+    array or int64 tensor): episode e of agent i resets from the draw (rng_keys[i], test-reset stream, episode_offset[i] + e);
+    episode_offset: one integer or one per agent.  test_episodes / max_steps override the config's.
+    Returns, per agent, the reference's triple (reward_list, episode_length_list, replay_buffer): the T episode returns, the T episode
+    lengths counted in agent steps (BaseAgent.test adds 1 per action, base_agent.py:213), and the visited transitions as ReplayRows."""
+    dev = engine.require_device()
+    over = {}
+    if test_episodes is not None:
+        over["test_episodes"] = int(test_episodes)
+    if max_steps is not None:
+        over["max_steps"] = int(max_steps)
+    cfg = ddqn_cfg_from_config(config, **over)
+    params = torch.as_tensor(params, dtype=torch.float32).to(dev).contiguous()
+    n = params.shape[0]
+    out = engine.agent_test_population(cfg, params, _device_i64(rng_keys, n, dev, "rng_keys"), _device_i64(episode_offset, n, dev, "episode_offset"))
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    return [(host["returns"][i].tolist(), host["agent_steps"][i].tolist(),
+             rows_of_episodes(host["row_state"][i], host["row_action"][i], host["row_next_state"][i], host["row_reward"][i], host["row_done"][i],
+                              host["agent_steps"][i]))
+            for i in range(n)]
+
+
+test_agents.__test__ = False      # a library function, not a pytest case

@@ -1,0 +1,299 @@
+// agent_test_population.hip -- BaseAgent.test (agents/base_agent.py:155-227) with DDQN.select_test_action / DuelingDDQN.select_test_action for
+// a whole population of trained agents in one launch: agent i runs cfg->test_episodes greedy episodes on the real env (CartPole-v0,
+// Acrobot-v1, MountainCar-v0) and, when asked, records every transition it visits -- the replay buffer the reference's test() returns.
+//
+// The operations are those of the fused loops' closing test (test_phase of dueling_se_inner_loop.hip): reset, the greedy action with ties
+// towards the lower index repeated same_action_num times or until done, TimeLimit at max_steps env steps, the repeats' rewards summed in fp64
+// and rounded once to fp32 onto an fp32 episode return.  Nothing is restated: the physics, the reset draw and the observation are
+// real_env_step / real_env_reset_draw / real_env_obs of lenv_device.cuh, the parameter layout is duel_param_offsets (the final_online rows of
+// lenv_dueling_se_inner_loop), the shared LayerNorm is ln_rows_forward of lenv_ln.cuh.  Every dot product is the k-ascending fmaf chain from 0,
+// then the bias, then the activation, so the Q values carry the bits of the GEMM-queue forward and of the register-resident DDQN kernel.
+//
+// Grid (agent, block of at most AT_TB episodes), 512 threads.  The episodes of a block advance in lock-step; a finished one idles until the
+// block ends.  A forward item is (output unit j, group of AT_EPT episodes): consecutive lanes own consecutive units, so the activation reads
+// of a wave are LDS broadcasts whatever the row stride, and a weight is loaded once for the group's episodes.  The env state of episode e
+// lives in the registers of thread e.
+// Dynamic LDS (floats), rows = min(T, AT_TB):  two activation buffers [rows][W], W = the widest layer (H, or 2 F for the two head hidden
+// layers of a dueling agent, rounded up to 4) | q_layer_norm with two or more hidden layers: [rows][H | 1] for ln_rows_forward | the agent's
+// parameters where they still fit into 160 KiB, every weight matrix transposed (k-major: conflict-free for lanes on consecutive units);
+// otherwise the weights are read from global memory, a lane streaming its unit's row.  The widest admitted shape (H 512, three hidden layers,
+// LayerNorm) takes 2 * 16 * 512 + 16 * 513 floats = 96.1 KiB.
+#include <hip/hip_runtime.h>
+#include "../../include/lenv_hip.h"
+#include "lenv_gemm.cuh"
+#include "lenv_dueling_params.cuh"
+#include "lenv_ln.cuh"
+#include "lenv_host.h"
+
+namespace lenv {
+
+constexpr int AT_TB = 16;                      // episodes of one workgroup
+constexpr int AT_EPT = 4;                      // episodes of one forward item
+constexpr int AT_XLD = 8;                      // row stride of the observation rows
+constexpr int AT_MAXS = 6, AT_MAXA = 3;        // the widest observation (Acrobot) and the most actions of the three envs
+constexpr int AT_LNBUF = AT_TB * (D_MAXH | 1); // ln_rows_forward: every row of a block in one chunk
+constexpr int AT_MAX_REPEAT = 64;
+constexpr size_t AT_LDS_LIMIT = 160 * 1024 - 1024;   // dynamic bytes next to the static arrays below (under 1 KiB)
+
+struct AtArgs {
+    int env_id, S, A, H, L, F, act, plain, ln, T, max_steps, k_rep, cap;
+    float prelu;
+    int P, W;
+    const float *params; const uint64_t *rng_keys; const int64_t *episode_offset; const double *reset_states;
+    double *returns; int32_t *env_steps, *agent_steps;
+    float *row_state; int32_t *row_action; float *row_next_state, *row_reward, *row_done;
+};
+
+// y[e][j] = (act)(sum_k x[e][k] * W[j][k] + b[j]) for the episodes e < rows of the block, j < n_out.  ST: W is the staged, transposed copy
+// (element (j, k) at k * n_out + j), else the row-major matrix in global memory.  Groups without a live episode are skipped.  The caller
+// synchronises.
+template <bool ST>
+__device__ __forceinline__ void at_layer(const float *W, const float *b, int n_in, int n_out, const float *x, int ldx, float *y, int ldy, int rows,
+                                         bool activate, int act, float prelu, unsigned alive, int tid)
+{
+    const int groups = (rows + AT_EPT - 1) / AT_EPT;
+    const bool xv4 = (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    const bool wv4 = !ST && (n_in & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0;
+    for (int it = tid; it < groups * n_out; it += DNT) {
+        const int g = it / n_out, j = it - g * n_out, e0 = g * AT_EPT;
+        if (((alive >> e0) & ((1u << AT_EPT) - 1)) == 0) continue;
+        const float *xr[AT_EPT];
+        float z[AT_EPT];
+#pragma unroll
+        for (int u = 0; u < AT_EPT; ++u) { const int e = e0 + u < rows ? e0 + u : rows - 1; xr[u] = x + e * ldx; z[u] = 0.0f; }
+        const float *wj = ST ? W + j : W + (int64_t)j * n_in;
+        int k = 0;
+        for (; k + 4 <= n_in; k += 4) {
+            float w[4];
+            if (ST) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) w[q] = wj[(k + q) * n_out];
+            } else if (wv4) {
+                const float4 t = *reinterpret_cast<const float4 *>(wj + k);
+                w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) w[q] = wj[k + q];
+            }
+#pragma unroll
+            for (int u = 0; u < AT_EPT; ++u) {
+                float xv[4];
+                if (xv4) {
+                    const float4 t = *reinterpret_cast<const float4 *>(xr[u] + k);
+                    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) xv[q] = xr[u][k + q];
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) z[u] = fma32(xv[q], w[q], z[u]);
+            }
+        }
+        for (; k < n_in; ++k) {
+            const float w = ST ? wj[k * n_out] : wj[k];
+#pragma unroll
+            for (int u = 0; u < AT_EPT; ++u) z[u] = fma32(xr[u][k], w, z[u]);
+        }
+        const float bj = b[j];
+#pragma unroll
+        for (int u = 0; u < AT_EPT; ++u) {
+            if (e0 + u >= rows) break;
+            const float v = z[u] + bj;
+            y[(e0 + u) * ldy + j] = activate ? act_fwd(act, prelu, v) : v;
+        }
+    }
+}
+
+// the staged copy of one weight matrix [n_out][n_in]: transposed in place of the row-major one
+__device__ __forceinline__ void at_stage_transposed(float *dst, const float *src, int n_out, int n_in, int tid)
+{
+    for (int i = tid; i < n_out * n_in; i += DNT) { const int j = i / n_in, k = i - j * n_in; dst[k * n_out + j] = src[i]; }
+}
+
+template <bool ST>
+__global__ __launch_bounds__(DNT) void agent_test_population_kernel(const AtArgs a)
+{
+    extern __shared__ __align__(16) float lds[];
+    __shared__ __align__(16) float xin[AT_TB * AT_XLD];            // the observation each live episode acts on
+    __shared__ float qadv[AT_TB * 4], vhead[AT_TB];                // Q(s, .) of a plain agent / the advantage head; the value head
+    __shared__ unsigned alive_mask;
+    const int tid = threadIdx.x;
+    const int64_t agent = blockIdx.x;
+    const int S = a.S, A = a.A, H = a.H, L = a.L, F = a.F, T = a.T;
+    const bool plain = a.plain != 0, ln = a.ln != 0;
+    const int ep0 = blockIdx.y * AT_TB, rows = T - ep0 < AT_TB ? T - ep0 : AT_TB, rows_max = T < AT_TB ? T : AT_TB;
+    const DuelOffsets po = duel_param_offsets(S, A, H, F, L, plain, ln);
+
+    float *buf0 = lds, *buf1 = lds + rows_max * a.W;
+    auto buf = [&](int i) { return (i & 1) ? buf1 : buf0; };
+    float *lnbuf = buf1 + rows_max * a.W;
+    float *wst = lnbuf + (ln ? rows_max * (H | 1) : 0);
+    const float *gpar = a.params + agent * a.P;
+    const float *par = ST ? wst : gpar;
+    if (ST) {
+        for (int p = tid; p < a.P; p += DNT) wst[p] = gpar[p];     // biases, LayerNorm, and the matrices' places
+        __syncthreads();
+        int n_in = S;
+        for (int l = 0; l < L; ++l) { at_stage_transposed(wst + po.oWf[l], gpar + po.oWf[l], H, n_in, tid); n_in = H; }
+        at_stage_transposed(wst + po.oWf[L], gpar + po.oWf[L], F, H, tid);
+        if (!plain) {
+            at_stage_transposed(wst + po.oWv1, gpar + po.oWv1, F, F, tid);
+            at_stage_transposed(wst + po.oWa1, gpar + po.oWa1, F, F, tid);
+            at_stage_transposed(wst + po.oWa2, gpar + po.oWa2, A, F, tid);
+        }
+    }
+
+    // ---- env.reset() of every episode of the block ----
+    const bool mine = tid < rows;
+    const int64_t ep = agent * T + ep0 + tid;                      // this thread's episode in the [agents, T] outputs
+    double st[4] = { 0.0, 0.0, 0.0, 0.0 };
+    float ep_rew = 0.0f;
+    int tlen = 0, n_agent = 0;
+    bool live = mine;
+    if (mine) {
+        if (a.reset_states) { for (int i = 0; i < 4; ++i) st[i] = a.reset_states[ep * 4 + i]; }
+        else real_env_reset_draw(a.env_id, a.rng_keys[agent], STREAM_TEST_RESET, (a.episode_offset ? a.episode_offset[agent] : 0) + ep0 + tid, st);
+        float obs[8];
+        real_env_obs(a.env_id, st, obs);
+#pragma unroll
+        for (int i = 0; i < AT_MAXS; ++i) if (i < S) xin[tid * AT_XLD + i] = obs[i];
+    }
+    if (tid == 0) alive_mask = (1u << rows) - 1u;                  // rows <= AT_TB = 16
+    __syncthreads();
+
+    const int ldh = ln ? H : (H + 3) & ~3;                         // ln_rows_forward takes dense rows
+    for (int t = 0; t < a.max_steps; t += a.k_rep) {               // base_agent.py:194 range(0, max_steps, same_action_num)
+        const unsigned alive = alive_mask;
+        // ---- Q(s, .) of the live episodes: Critic_DQN / Critic_DuelingDQN (models/actor_critic.py:84-122) ----
+        const float *in = xin;
+        int n_in = S, ldi = AT_XLD;
+        for (int l = 0; l < L; ++l) {
+            float *out = buf(l);
+            const bool at_ln = ln && l >= 1;
+            at_layer<ST>(par + po.oWf[l], par + po.obf[l], n_in, H, in, ldi, out, ldh, rows, !at_ln, a.act, a.prelu, alive, tid);
+            __syncthreads();
+            if (at_ln) ln_rows_forward<AT_LNBUF>(lnbuf, out, rows, H, par + po.oLN, par + po.oLN + H, nullptr, nullptr, a.act, a.prelu);
+            in = out; n_in = H; ldi = ldh;
+        }
+        if (plain) {
+            at_layer<ST>(par + po.oWf[L], par + po.obf[L], H, A, in, ldi, qadv, 4, rows, false, 0, 0.0f, alive, tid);
+        } else {
+            float *feat = buf(L), *heads = buf(L + 1);   // heads: [rows][v1 | a1]
+            const int ldf = (F + 3) & ~3, ld2 = 2 * ldf;
+            at_layer<ST>(par + po.oWf[L], par + po.obf[L], H, F, in, ldi, feat, ldf, rows, false, 0, 0.0f, alive, tid);
+            __syncthreads();
+            at_layer<ST>(par + po.oWv1, par + po.obv1, F, F, feat, ldf, heads, ld2, rows, true, a.act, a.prelu, alive, tid);
+            at_layer<ST>(par + po.oWa1, par + po.oba1, F, F, feat, ldf, heads + ldf, ld2, rows, true, a.act, a.prelu, alive, tid);
+            __syncthreads();
+            at_layer<ST>(par + po.oWv2, par + po.obv2, F, 1, heads, ld2, vhead, 1, rows, false, 0, 0.0f, alive, tid);
+            at_layer<ST>(par + po.oWa2, par + po.oba2, F, A, heads + ldf, ld2, qadv, 4, rows, false, 0, 0.0f, alive, tid);
+        }
+        __syncthreads();
+        // ---- select_test_action, then EnvWrapper.step on the real env (envs/env_wrapper.py:56-61) ----
+        if (live) {
+            float q[AT_MAXA] = { 0.0f, 0.0f, 0.0f };
+            if (plain) {
+#pragma unroll
+                for (int aa = 0; aa < AT_MAXA; ++aa) if (aa < A) q[aa] = qadv[tid * 4 + aa];
+            }
+            else {                                                 // q = V + (Adv - Adv.mean()) of the row (finish_q, global_mean false)
+                float sum = 0.0f;
+#pragma unroll
+                for (int aa = 0; aa < AT_MAXA; ++aa) if (aa < A) sum = sum + qadv[tid * 4 + aa];
+                const float mean = sum / (float)A;
+#pragma unroll
+                for (int aa = 0; aa < AT_MAXA; ++aa) if (aa < A) q[aa] = vhead[tid] + (qadv[tid * 4 + aa] - mean);
+            }
+            int am = 0; float best = q[0];
+#pragma unroll
+            for (int aa = 1; aa < AT_MAXA; ++aa) if (aa < A && q[aa] > best) { best = q[aa]; am = aa; }
+            double rsum = 0.0;
+            int nstep = 0, dn = 0;
+            for (int r = 0; r < a.k_rep; ++r) {
+                double rew;
+                real_env_step(a.env_id, st, am, rew, dn);
+                rsum = rsum + rew;
+                ++nstep;
+                if (tlen + nstep >= a.max_steps) dn = 1;           // gym.wrappers.TimeLimit
+                if (dn) break;
+            }
+            const float r32 = (float)rsum;
+            float obs[8];
+            real_env_obs(a.env_id, st, obs);
+            if (a.row_state) {
+                const int64_t slot = ep * a.cap + n_agent;
+#pragma unroll
+                for (int i = 0; i < AT_MAXS; ++i) if (i < S) { a.row_state[slot * S + i] = xin[tid * AT_XLD + i]; a.row_next_state[slot * S + i] = obs[i]; }
+                a.row_action[slot] = am; a.row_reward[slot] = r32; a.row_done[slot] = dn ? 1.0f : 0.0f;
+            }
+#pragma unroll
+            for (int i = 0; i < AT_MAXS; ++i) if (i < S) xin[tid * AT_XLD + i] = obs[i];
+            ep_rew = ep_rew + r32;
+            tlen += nstep; ++n_agent;
+            if (dn) { live = false; atomicAnd(&alive_mask, ~(1u << tid)); }
+        }
+        __syncthreads();
+        if (alive_mask == 0) break;                                // uniform; the next write comes behind further barriers
+    }
+    if (mine) { a.returns[ep] = (double)ep_rew; a.env_steps[ep] = tlen; a.agent_steps[ep] = n_agent; }
+}
+
+}  // namespace lenv
+
+using namespace lenv;
+
+// the entry's own checks of cfg (only the fields the kernel reads) into the launch's shape
+static int at_shape(const lenv_ddqn_cfg *cfg, AtArgs &a)
+{
+    if (cfg->agent_kind != 0 && cfg->agent_kind != 1) return LENV_ERR_INVALID;
+    if (cfg->max_steps < 1) return LENV_ERR_INVALID;
+    const bool plain = cfg->agent_kind == 0;
+    const int S = cfg->state_dim, A = cfg->num_actions, H = cfg->q_hidden, L = cfg->q_layers, F = plain ? A : cfg->feature_dim, T = cfg->test_episodes;
+    if (cfg->q_act == LENV_ACT_PRELU) return LENV_ERR_UNSUPPORTED;     // a trained slope in the reference; refused as the generic kernel refuses it
+    if (L < 1 || L > D_MAXL || H < 1 || H > D_MAXH || F < 1 || F > D_MAXW || T < 1 || T > D_MAXW) return LENV_ERR_UNSUPPORTED;
+    if (cfg->same_action_num < 0 || cfg->same_action_num > AT_MAX_REPEAT) return LENV_ERR_UNSUPPORTED;
+    if (!((cfg->env_id == LENV_ENV_CARTPOLE && S == 4 && A == 2) || (cfg->env_id == LENV_ENV_ACROBOT && S == 6 && A == 3) ||
+          (cfg->env_id == LENV_ENV_MOUNTAINCAR && S == 2 && A == 3)))
+        return LENV_ERR_UNSUPPORTED;
+    a.env_id = cfg->env_id; a.S = S; a.A = A; a.H = H; a.L = L; a.F = F; a.act = cfg->q_act; a.prelu = cfg->q_prelu; a.plain = plain ? 1 : 0;
+    a.ln = (cfg->q_layer_norm != 0 && L >= 2) ? 1 : 0;
+    a.T = T; a.max_steps = cfg->max_steps; a.k_rep = cfg->same_action_num > 1 ? cfg->same_action_num : 1;
+    a.cap = (cfg->max_steps + a.k_rep - 1) / a.k_rep;
+    a.P = duel_param_offsets(S, A, H, F, L, plain, a.ln != 0).P;
+    const int hw = (H + 3) & ~3, fw = 2 * ((F + 3) & ~3);
+    a.W = plain || hw > fw ? hw : fw;
+    return LENV_OK;
+}
+
+extern "C" int64_t lenv_agent_test_rows_cap(const lenv_ddqn_cfg *cfg)
+{
+    if (!cfg) return LENV_ERR_INVALID;
+    AtArgs a{};
+    const int rc = at_shape(cfg, a);
+    return rc != LENV_OK ? rc : a.cap;
+}
+
+extern "C" int lenv_agent_test_population(const lenv_ddqn_cfg *cfg, const float *params, const uint64_t *rng_keys, const int64_t *episode_offset,
+                                          const double *reset_states, int64_t agents, double *returns, int32_t *env_steps, int32_t *agent_steps,
+                                          float *row_state, int32_t *row_action, float *row_next_state, float *row_reward, float *row_done,
+                                          void *stream)
+{
+    if (!cfg || !params || !rng_keys || !returns || !env_steps || !agent_steps || agents < 0) return LENV_ERR_INVALID;
+    const int n_rows = (row_state != nullptr) + (row_action != nullptr) + (row_next_state != nullptr) + (row_reward != nullptr) + (row_done != nullptr);
+    if (n_rows != 0 && n_rows != 5) return LENV_ERR_INVALID;
+    AtArgs a{};
+    const int rc = at_shape(cfg, a);
+    if (rc != LENV_OK) return rc;
+    if (agents == 0) return LENV_OK;
+    if (agents > 0x7fffffff) return LENV_ERR_UNSUPPORTED;
+    a.params = params; a.rng_keys = rng_keys; a.episode_offset = episode_offset; a.reset_states = reset_states;
+    a.returns = returns; a.env_steps = env_steps; a.agent_steps = agent_steps;
+    a.row_state = row_state; a.row_action = row_action; a.row_next_state = row_next_state; a.row_reward = row_reward; a.row_done = row_done;
+    const int rows_max = a.T < AT_TB ? a.T : AT_TB;
+    size_t lds_bytes = (2 * (size_t)rows_max * a.W + (a.ln ? (size_t)rows_max * (a.H | 1) : 0)) * sizeof(float);
+    const bool staged = lds_bytes + (size_t)a.P * sizeof(float) <= AT_LDS_LIMIT;         // the parameters next to the activations
+    if (staged) lds_bytes += (size_t)a.P * sizeof(float);
+    const dim3 grid((unsigned)agents, (unsigned)((a.T + AT_TB - 1) / AT_TB));
+    if (staged) return lenv_host::launch(agent_test_population_kernel<true>, grid, dim3(DNT), lds_bytes, stream, a);
+    return lenv_host::launch(agent_test_population_kernel<false>, grid, dim3(DNT), lds_bytes, stream, a);
+}

@@ -16,6 +16,7 @@
 // products by changing strides.  This is the configuration where HBM traffic is real: ~5 MB of weight/Adam streaming
 // per learn step and chain.
 #include "lenv_gemm.cuh"
+#include "lenv_dueling_params.cuh"
 #include "lenv_ln.cuh"
 #include "lenv_icm.cuh"
 #include "lenv_wavechain_host.h"
@@ -23,9 +24,6 @@
 
 namespace lenv {
 
-constexpr int D_MAXL = 3;         // feature-stream hidden layers supported (the *_vary agents draw hidden_layer + 1)
-constexpr int D_MAXW = 128;       // max feature_dim (head width) and test episodes
-constexpr int D_MAXH = 512;       // max hidden_size  (outputs wider than 128 run as several 128-column blocks)
 constexpr int D_MAXB = 640;       // max batch size   (more than 128 rows run as several 128-row blocks)
 constexpr int D_MAXI = 128;       // rows of one product block
 
@@ -76,33 +74,6 @@ struct DuelArgs {
     // instantiations read their arguments where they were.)
     int ep_begin, ep_end; int64_t *resume;
 };
-
-// parameter offsets inside one parameter vector (state-dict order)
-struct DuelOffsets {
-    int oWf[D_MAXL + 1], obf[D_MAXL + 1];     // feature stream: hidden layers 0..L-1, then the output Linear (index L)
-    int oWv1, obv1, oWv2, obv2, oWa1, oba1, oWa2, oba2;
-    int oLN;                                  // q_layer_norm with L >= 2: weight [H] | bias [H] of the ONE shared nn.LayerNorm, behind the second Linear (Module.parameters() order)
-    int P;
-};
-
-__host__ __device__ constexpr DuelOffsets duel_param_offsets(int S, int A, int H, int F, int L, bool plain, bool ln = false)
-{
-    DuelOffsets d{};
-    int o = 0, n_in = S;
-    for (int l = 0; l <= D_MAXL; ++l) d.oWf[l] = d.obf[l] = 0;
-    for (int l = 0; l < L; ++l) {
-        d.oWf[l] = o; o += H * n_in; d.obf[l] = o; o += H; n_in = H;
-        if (ln && l == 1) { d.oLN = o; o += 2 * H; }
-    }
-    d.oWf[L] = o; o += F * H; d.obf[L] = o; o += F;
-    if (plain) { d.oWv1 = d.obv1 = d.oWv2 = d.obv2 = d.oWa1 = d.oba1 = d.oWa2 = d.oba2 = o; }       // no heads
-    else {
-        d.oWv1 = o; o += F * F; d.obv1 = o; o += F; d.oWv2 = o; o += F; d.obv2 = o; o += 1;
-        d.oWa1 = o; o += F * F; d.oba1 = o; o += F; d.oWa2 = o; o += A * F; d.oba2 = o; o += A;
-    }
-    d.P = o;
-    return d;
-}
 
 // Diagnostic build only (-DLENV_PHASE_TIMING): per-phase shader-clock totals of chain 0, never in the shipped library.
 #ifdef LENV_PHASE_TIMING

@@ -182,6 +182,56 @@ def rn_step_population(env_id, max_steps, rtype, rn_desc, info_dim, gamma, theta
     return obs, r, d
 
 
+def agent_test_num_params(cfg):
+    """Row width of `params` in agent_test_population: the agent's flat parameter vector at cfg's shapes (the final_online rows of the fused
+    loops; the shared LayerNorm's weight | bias included).  Computed from the network fields alone, so cfg's training fields may be anything."""
+    S, A, H, L = cfg.state_dim, cfg.num_actions, cfg.q_hidden, cfg.q_layers
+    dims = [(S, H)] + [(H, H)] * (L - 1)
+    if cfg.agent_kind == 1:
+        F = cfg.feature_dim
+        dims += [(H, F), (F, F), (F, 1), (F, F), (F, A)]
+    else:
+        dims += [(H, A)]
+    return sum(fi * fo + fo for fi, fo in dims) + (2 * H if cfg.q_layer_norm and L >= 2 else 0)
+
+
+def agent_test_population(cfg, params, rng_keys, episode_offset=None, reset_states=None, want_rows=True):
+    """BaseAgent.test of a population of trained DDQN / DuelingDDQN agents in one launch (lenv_agent_test_population): agent i, parameters
+    params[i] (fp32 [agents,P] in the layout of the fused loops' final_online), runs T = cfg.test_episodes greedy episodes on the real env.
+    Episode e resets from the counter draw (rng_keys[i], test-reset stream, episode_offset[i] + e) -- episode_offset int64 [agents], None = 0
+    -- or from reset_states[i][e] (fp64 [agents,T,4]).  Returns a dict of device tensors: returns fp64 [agents,T], env_steps / agent_steps
+    int32 [agents,T] and, with want_rows, the transitions row_state / row_next_state fp32 [agents,T,cap,S], row_action int32 /
+    row_reward / row_done fp32 [agents,T,cap]; slots at or beyond agent_steps[i][e] are zero (the kernel does not write them)."""
+    dev = require_device()
+    L = _lib.lib()
+    _chk(params, torch.float32, "params"); _chk(rng_keys, torch.int64, "rng_keys")
+    _chk(episode_offset, torch.int64, "episode_offset"); _chk(reset_states, torch.float64, "reset_states")
+    cap = _count("lenv_agent_test_rows_cap", C.byref(cfg))
+    P, T, S = agent_test_num_params(cfg), cfg.test_episodes, cfg.state_dim
+    if params.dim() != 2 or params.shape[1] != P:
+        raise ValueError("params must be [agents,%d]" % P)
+    n = params.shape[0]
+    if tuple(rng_keys.shape) != (n,):
+        raise ValueError("rng_keys must be [agents]")
+    if episode_offset is not None and tuple(episode_offset.shape) != (n,):
+        raise ValueError("episode_offset must be [agents]")
+    if reset_states is not None and tuple(reset_states.shape) != (n, T, 4):
+        raise ValueError("reset_states must be [agents,%d,4]" % T)
+    out = dict(returns=torch.zeros((n, T), dtype=torch.float64, device=dev), env_steps=torch.zeros((n, T), dtype=torch.int32, device=dev),
+               agent_steps=torch.zeros((n, T), dtype=torch.int32, device=dev))
+    rows = {}
+    if want_rows:
+        rows = dict(row_state=torch.zeros((n, T, cap, S), dtype=torch.float32, device=dev), row_action=torch.zeros((n, T, cap), dtype=torch.int32, device=dev),
+                    row_next_state=torch.zeros((n, T, cap, S), dtype=torch.float32, device=dev), row_reward=torch.zeros((n, T, cap), dtype=torch.float32, device=dev),
+                    row_done=torch.zeros((n, T, cap), dtype=torch.float32, device=dev))
+    rc = L.lenv_agent_test_population(C.byref(cfg), _ptr(params), _ptr(rng_keys), _ptr(episode_offset), _ptr(reset_states), n, _ptr(out["returns"]),
+                                      _ptr(out["env_steps"]), _ptr(out["agent_steps"]), _ptr(rows.get("row_state")), _ptr(rows.get("row_action")),
+                                      _ptr(rows.get("row_next_state")), _ptr(rows.get("row_reward")), _ptr(rows.get("row_done")), _stream())
+    _lib.check(rc, "lenv_agent_test_population")
+    out.update(rows)
+    return out
+
+
 def qnet_td_forward(qd, online, target, replay, idx, gamma):
     """online/target [chains,P]; replay [chains,cap,row_stride]; idx int32 [chains,B] -> (q_sa, y) [chains,B]."""
     dev = require_device()

@@ -378,6 +378,68 @@ def run_rn_step(name, chains=192, hidden=128, repeat=1, runs=7, iters=(40, 2000)
     return out
 
 
+def run_agent_test(name, cfgd, agents=400, test_episodes=10, runs=7, seed=0):
+    """BaseAgent.test of `agents` freshly initialised agents of cfgd's shape, `test_episodes` episodes each (a fresh agent almost never ends a
+    MountainCar / Acrobot episode, so nearly every episode runs to the time limit and both sides do the same steps): lenv_agent_test_population
+    against the only route there was before it, the generic GEMM-queue kernel launched with train_episodes = 0 (its closing test alone; kernel_variant
+    GENERIC | NO_WAVECHAIN keeps the launch on that kernel).  Host clock around a synchronise, a warm-up of each, then `runs` runs in alternation;
+    medians and ranges; the returns must be equal before anything is timed."""
+    from learning_environments_amd import _lib, engine
+    from learning_environments_amd.agents import tasks
+    from learning_environments_amd.agents.nes_common import chain_keys, fresh_agent_init
+    import numpy as np
+    eng = engine.HipNesEngine()
+    dev = eng.device
+    c = configs.fixed_work(cfgd, 0)
+    key = c["agents"]["gtn"]["agent_name"].lower()
+    c["agents"][key]["test_episodes"] = test_episodes
+    c["agents"]["gtn"]["kernel_variant"] = _lib.VARIANT_GENERIC | _lib.VARIANT_NO_WAVECHAIN
+    task = tasks.DdqnSeTask(c, eng)
+    cfg = task.cfg
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    params = fresh_agent_init(task.agent_bounds, agents, g, dev)
+    keys = torch.from_numpy(chain_keys(seed, 0, np.arange(agents), np.zeros(agents, np.int64)).view(np.int64)).to(dev)
+    il = engine.InnerLoop(cfg, agents, want_episode_stats=True)
+    assert il.dueling and il.p_agent == params.shape[1] == engine.agent_test_num_params(cfg)
+    p_se = sum(engine.mlp_num_params(d) for d in engine.se_descs(cfg.state_dim, cfg.num_actions, cfg.se_hidden, cfg.se_layers, cfg.se_act))
+    theta, eps = torch.zeros(p_se, device=dev), torch.zeros((1, p_se), device=dev)
+    worker, sign = torch.zeros(agents, dtype=torch.int32, device=dev), torch.zeros(agents, device=dev)
+
+    def generic():
+        il.run(theta, eps, worker, sign, params, rng_keys=keys)
+        return il.final_returns
+
+    def entry():
+        return engine.agent_test_population(cfg, params, keys, want_rows=False)["returns"]
+
+    def entry_rows():
+        return engine.agent_test_population(cfg, params, keys, want_rows=True)["returns"]
+
+    ref = generic().clone()
+    torch.cuda.synchronize()
+    assert int(il.status.cpu().abs().max()) == 0
+    same = bool(torch.equal(ref, entry())) and bool(torch.equal(ref, entry_rows()))
+    assert same, "lenv_agent_test_population and the generic kernel's closing test differ"
+    forms = (("generic_train_episodes_0", generic), ("agent_test_population", entry), ("agent_test_population_with_rows", entry_rows))
+    times = {label: [] for label, _ in forms}
+    for it in range(runs + 1):
+        for label, fn in forms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if it:
+                times[label].append(time.perf_counter() - t0)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    out = dict(config=name, agents=agents, test_episodes=test_episodes, max_steps=cfg.max_steps, params_per_agent=int(params.shape[1]), runs_each=runs,
+               test_steps=int(il.stats[:, 3].sum()), ms_median={k: 1e3 * v for k, v in med.items()}, ms_min={k: 1e3 * min(v) for k, v in times.items()},
+               ms_max={k: 1e3 * max(v) for k, v in times.items()}, ms_samples={k: [round(1e3 * x, 3) for x in v] for k, v in times.items()},
+               generic_over_entry=med["generic_train_episodes_0"] / med["agent_test_population"], same_returns=same)
+    print(json.dumps(out))
+    return out
+
+
 def _frac(model):
     def f(cfg, st, dt):
         nbytes, flops = model(cfg, st)
@@ -634,6 +696,13 @@ if __name__ == "__main__":
         # launch against one env-step launch + 192 shaping launches per repeat; a warm-up, then the medians of 7 alternating runs
         for repeat in (1, 2):
             run_rn_step("HalfCheetah-standin RN 17-128-1 type 2, 192 chains, one step, repeat %d: composed entries / one launch" % repeat, repeat=repeat)
+    if "agent_test" in which:
+        # BaseAgent.test as a call of its own: 400 fresh agents (the run_vary_hp population) x 10 test episodes, the new entry against the generic
+        # kernel launched with train_episodes = 0; a warm-up, then the medians of 7 alternating runs
+        run_agent_test("MountainCar-v0, DDQN 2-256-256-3, 400 agents x 10 test episodes of 200 steps: generic kernel (train_episodes 0) / agent_test_population",
+                       configs.mountaincar_syn_env_ddqn(16))
+        run_agent_test("Acrobot-v1, DuelingDDQN 6-128-128 f128, 400 agents x 10 test episodes of 500 steps: generic kernel (train_episodes 0) / agent_test_population",
+                       configs.acrobot_syn_env_duelingddqn(16))
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
