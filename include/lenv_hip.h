@@ -756,7 +756,9 @@ int lenv_ppo_rn_inner_loop(const lenv_ppo_cfg *cfg /*HOST*/, const float *theta,
  *   11 learn_calls (PPO.learn calls; also the learn_step / learn_params cursor before the learn_cap clamp)
  *   12..13 bit patterns of the doubles beta1^t, beta2^t of the optimizer
  *   14..21 bit patterns (low 32 bits) of actor_old's action_std[0..8) as the next action has to see it: clamped to >= 0.001 by the
- *          actions taken so far, equal to actor's after a learn call; entries >= action_dim are 0      22..31 reserved (0)
+ *          actions taken so far, equal to actor's after a learn call; entries >= action_dim are 0
+ *   22..23 lenv_ppo_icm_inner_loop_segment: bit patterns of the ICM optimizer's beta1^t, beta2^t (1.0 before the module's first step);
+ *          0 in a record of lenv_ppo_rn_inner_loop_segment                                               24..31 reserved (0)
  * The parameters, the Adam moments, the partly filled on-policy row buffer and the early-out meter live in the arena.
  * Status of a FAILING chain: a thread keeps the code of its latest failure and the launch reports the minimum over the threads; a series of
  * segments folds that minimum at every boundary and starts every thread of the next segment from it, so after different kinds of failure in
@@ -767,6 +769,39 @@ int lenv_ppo_rn_inner_loop_segment(const lenv_ppo_cfg *cfg /*HOST*/, const float
                                    const lenv_ppo_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace,
                                    size_t workspace_bytes, const lenv_ppo_out *out /*HOST*/, int32_t episode_begin, int32_t episode_end,
                                    int64_t *resume /*DEVICE [chains, LENV_PPO_RESUME_WORDS]*/, void *stream);
+
+/* PPO with an Intrinsic Curiosity Module, PPO(icm=True) (agents/PPO.py:46-62,144-145,183-184; the `ppo_icm` agent of the transfer scripts'
+ * mode -1) -- ABI 7, functions only: lenv_ppo_cfg is unchanged and the module's five settings (the config's `icm` section) are scalar
+ * arguments.  The inner loop is lenv_ppo_rn_inner_loop's with, inside every PPO.learn call on its n rows,
+ *   - rewards[i] += eta * mean_f (features(s'_i) - forward(s_i, a_i))^2 for ALL n rows before the return scan, computed with the module as
+ *     the previous call left it (the fresh module in the first call); s' is the observation the agent step ended in;
+ *   - ONE Adam step of the module (lr icm_lr, cfg's adam_beta1 / adam_beta2 / adam_eps, a step counter of its own) on all n rows after the
+ *     last epoch: loss (1 - icm_beta) * MSE(inverse(s, s'), a) + icm_beta * MSE(forward(s, a), features(s')).
+ * The module is the one of lenv_td3_rn_inner_loop_icm (continuous actions: the action vector is the input); icm->icm_init
+ * [chains, lenv_ppo_icm_num_params] = fresh parameters per chain in that layout, icm->icm_final (may be NULL) receives them with the closing
+ * part and, like final_params, as a checkpoint at the end of an unfinished segment.  trace_reward stays the shaped reward at collection time
+ * and learn_params rows stay the agent's P parameters.
+ * Admitted: what lenv_ppo_rn_inner_loop admits, with icm_feature_dim and icm_hidden in 1..128.  Refused before any launch and before the
+ * `chains == 0` return: LENV_ERR_INVALID for icm == NULL or icm->icm_init == NULL, LENV_ERR_UNSUPPORTED for a dimension outside 1..128, and
+ * whatever the ICM-less entry refuses with its code.  One kernel serves both launch entries: lenv_ppo_icm_inner_loop runs the segment
+ * [0, train_episodes) with its records kept in the workspace; lenv_ppo_icm_inner_loop_segment is lenv_ppo_rn_inner_loop_segment's contract
+ * (every split leaves every output, icm_final included, bit-identical to the single launch; record words 22..23 above).  The workspace holds
+ * per chain the ICM-less arena, the next-observation rows and the module's parameters, Adam moments and activations for
+ * lenv_ppo_rows(cfg) rows. */
+/* parameters of the module (the length of an icm_init row), or a negative LENV_ERR_*.  HOST. */
+int64_t lenv_ppo_icm_num_params(const lenv_ppo_cfg *cfg /*HOST*/, int32_t icm_feature_dim, int32_t icm_hidden);
+int64_t lenv_ppo_icm_workspace_bytes(const lenv_ppo_cfg *cfg /*HOST*/, int32_t icm_feature_dim, int32_t icm_hidden, int64_t chains);
+int lenv_ppo_icm_inner_loop(const lenv_ppo_cfg *cfg /*HOST*/, int32_t icm_feature_dim, int32_t icm_hidden, double icm_lr, double icm_beta,
+                            double icm_eta, const lenv_icm_io *icm /*HOST struct of device arrays*/, const float *theta, const float *eps,
+                            const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                            const lenv_ppo_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace, size_t workspace_bytes,
+                            const lenv_ppo_out *out /*HOST*/, void *stream);
+int lenv_ppo_icm_inner_loop_segment(const lenv_ppo_cfg *cfg /*HOST*/, int32_t icm_feature_dim, int32_t icm_hidden, double icm_lr,
+                                    double icm_beta, double icm_eta, const lenv_icm_io *icm /*HOST struct of device arrays*/,
+                                    const float *theta, const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
+                                    const uint64_t *rng_keys, const lenv_ppo_tapes *tapes /*HOST, may be NULL*/, int64_t chains,
+                                    void *workspace, size_t workspace_bytes, const lenv_ppo_out *out /*HOST*/, int32_t episode_begin,
+                                    int32_t episode_end, int64_t *resume /*DEVICE [chains, LENV_PPO_RESUME_WORDS]*/, void *stream);
 
 /*
  * Batched forward of one MLP in the flat layout above: y [rows,out] = net(x [rows,in]) (models/model_utils.py:31-39;

@@ -81,9 +81,11 @@ def ddqn_cfg_from_config(config, rng_mode=_lib.RNG_COUNTER, grad_chunk=0, **over
     return cfg
 
 
-def icm_layer_dims(cfg):
-    """[(fan_in, fan_out), ...] of ICMModel's nn.Linear layers in state-dict order (models/icm_baseline.py:42-78)."""
-    S, F, H = cfg.state_dim, cfg.icm_feature_dim, cfg.icm_hidden
+def icm_layer_dims(cfg, feature_dim=None, hidden_size=None):
+    """[(fan_in, fan_out), ...] of ICMModel's nn.Linear layers in state-dict order (models/icm_baseline.py:42-78).  A PPO cfg has no icm
+    fields: its module's feature_dim / hidden_size (ppo_icm_settings) are arguments."""
+    S = cfg.state_dim
+    F, H = (cfg.icm_feature_dim, cfg.icm_hidden) if feature_dim is None else (int(feature_dim), int(hidden_size))
     discrete = hasattr(cfg, "num_actions")           # a TD3 cfg has action_dim: continuous actions, the vector itself is the input
     A = cfg.num_actions if discrete else cfg.action_dim
     Ai = 1 if (discrete and A == 2) else A
@@ -335,6 +337,13 @@ def ppo_cfg_from_config(config, rng_mode=_lib.RNG_COUNTER, **overrides):
     for k, v in overrides.items():
         setattr(cfg, k, v)
     return cfg
+
+
+def ppo_icm_settings(config):
+    """The `icm` section of a config as engine.PpoIcmInnerLoop takes it (PPO(icm=True), agents/PPO.py:47-53)."""
+    ic = config["agents"]["icm"]
+    return dict(feature_dim=int(ic["feature_dim"]), hidden_size=int(ic["hidden_size"]), lr=float(ic["lr"]), beta=float(ic["beta"]),
+                eta=float(ic["eta"]))
 
 
 def ppo_rows(cfg):

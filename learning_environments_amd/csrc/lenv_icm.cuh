@@ -1,6 +1,7 @@
 // lenv_icm.cuh -- the reference's Intrinsic Curiosity Module (models/icm_baseline.py:8-172) inside the GEMM-tiled inner loops:
 // ICM.train on the gathered minibatch + compute_intrinsic_rewards with the updated model (agents/DDQN.py:74-76,
-// agents/TD3.py:68-70).  oracle/lenv_oracle_icm.inc is the canonical restatement; arithmetic and order are the same.
+// agents/TD3.py:68-70); compute_intrinsic_rewards on all rows of a PPO.learn call and ICM.train after its epochs (agents/PPO.py:144-145,
+// 183-184).  oracle/lenv_oracle_icm.inc is the canonical restatement; arithmetic and order are the same.
 #pragma once
 
 #include "lenv_gemm.cuh"
@@ -56,61 +57,95 @@ struct IcmStep {
     bool continuous;                          // TD3: the action vector is the input and the inverse loss is an MSE
 };
 
-// action_of(b, i): action input i of sample b; add_reward(b, r): rewards[b] += r (called by one thread per sample)
-template <int MAXI, class ActFn, class RewFn>
-__device__ __forceinline__ void icm_train_and_reward(const IcmStep &c, ActFn action_of, RewFn add_reward)
+// the chain's ICM buffers as pointers
+struct IcmPtrs {
+    float *ip, *ig, *X2, *actin, *fh0, *fh1, *fe, *iin, *ih0, *ih1, *iz, *pin, *ph0, *ph1, *qh, *pred, *xc[5], *hc[4];
+};
+__device__ __forceinline__ IcmPtrs icm_ptrs(const IcmStep &c)
+{
+    auto buf = [&](int i) { return c.arena + c.a_icm[i]; };
+    IcmPtrs p;
+    p.ip = buf(IB_P); p.ig = buf(IB_G); p.X2 = buf(IB_X2); p.actin = buf(IB_ACT);
+    p.fh0 = buf(IB_FH0); p.fh1 = buf(IB_FH1); p.fe = buf(IB_FE); p.iin = buf(IB_IIN); p.ih0 = buf(IB_IH0); p.ih1 = buf(IB_IH1); p.iz = buf(IB_IZ);
+    p.pin = buf(IB_PIN); p.ph0 = buf(IB_PH0); p.ph1 = buf(IB_PH1); p.qh = buf(IB_QH); p.pred = buf(IB_PRED);
+    for (int k = 0; k < 5; ++k) p.xc[k] = buf(IB_XC0 + k);
+    for (int k = 0; k < 4; ++k) p.hc[k] = buf(IB_HC0 + k);
+    return p;
+}
+
+// The four pieces every use of the module is made of.  The three routines behind them: icm_rewards (stage, forward, rewards), icm_train
+// (stage, forward, backward + Adam) and icm_train_and_reward (stage, forward, backward + Adam, forward, rewards): a train followed by a
+// reward pass on the same rows stages the same values twice and so equals icm_train_and_reward bit for bit.
+
+// stacked states, action inputs (one logit target for two actions, else one-hot: icm_baseline.py:39-40,134-136) and the action columns of
+// every concatenated buffer.  action_of(b, i): action input i of sample b
+template <class ActFn>
+__device__ __forceinline__ void icm_stage(const IcmStep &c, const IcmPtrs &p, ActFn action_of)
+{
+    const int tid = (int)threadIdx.x;
+    const int B = c.B, S = c.icm.S, F = c.icm.F, Ai = c.icm.Ai, C = c.icm.C;
+    for (int e = tid; e < B * S; e += DNT) { const int b = e / S, i = e - b * S; p.X2[e] = c.s_rows[b * c.lds + i]; p.X2[B * S + e] = c.n_rows[b * c.ldn + i]; }
+    for (int e = tid; e < B * Ai; e += DNT) {
+        const int b = e / Ai, i = e - b * Ai;
+        const float av = action_of(b, i);
+        p.actin[e] = av;
+        p.pin[b * C + F + i] = av;
+        for (int k = 0; k < 5; ++k) p.xc[k][b * C + F + i] = av;
+        for (int k = 0; k < 4; ++k) p.hc[k][b * C + F + i] = av;
+    }
+    __syncthreads();
+}
+
+// ICMModel.forward (icm_baseline.py:80-102) on the staged rows: features_model once on the stacked [s; s'] rows
+template <int MAXI>
+__device__ __forceinline__ void icm_forward(const IcmStep &c, const IcmPtrs &p)
 {
     const int tid = (int)threadIdx.x;
     GemmQueue &gq = c.gq;
-    float *const Ps = c.Ps, *const Qs = c.Qs, *const arena = c.arena;
     const IcmNet &icm = c.icm;
-    volatile float *ctrl = c.ctrl;
-    const int B = c.B, S = icm.S, A = icm.A;
-    const int F = icm.F, Hi = icm.H, Ai = icm.Ai, C = icm.C;
-    auto buf = [&](int i) { return arena + c.a_icm[i]; };
-    float *ip = buf(IB_P), *ig = buf(IB_G), *X2 = buf(IB_X2), *actin = buf(IB_ACT);
-    float *fh0 = buf(IB_FH0), *fh1 = buf(IB_FH1), *fe = buf(IB_FE), *iin = buf(IB_IIN), *ih0 = buf(IB_IH0), *ih1 = buf(IB_IH1), *iz = buf(IB_IZ);
-    float *pin = buf(IB_PIN), *ph0 = buf(IB_PH0), *ph1 = buf(IB_PH1), *qh = buf(IB_QH), *pred = buf(IB_PRED);
-    float *xc[5], *hc[4];
-    for (int k = 0; k < 5; ++k) xc[k] = buf(IB_XC0 + k);
-    for (int k = 0; k < 4; ++k) hc[k] = buf(IB_HC0 + k);
+    const int B = c.B, S = icm.S, F = icm.F, Hi = icm.H, Ai = icm.Ai, C = icm.C;
+    float *const ip = p.ip;
     constexpr int LK = LENV_ACT_LEAKYRELU, RL = LENV_ACT_RELU;
     auto lin = [&](const IcmLin &L, const float *X, int ldx, int rows, float *Y, int ldy, int act) {
         if (act >= 0) gq.gemm(X, ldx, 1, ip + L.oW, L.in, 1, rows, L.out, L.in, epi_bias_act(Y, ldy, ip + L.ob, act, 0.25f));
         else gq.gemm(X, ldx, 1, ip + L.oW, L.in, 1, rows, L.out, L.in, epi_bias(Y, ldy, 0, ip + L.ob));
     };
-    // stacked states, action inputs (one logit target for two actions, else one-hot: icm_baseline.py:39-40,134-136) and
-    // the action columns of every concatenated buffer
-    for (int e = tid; e < B * S; e += DNT) { const int b = e / S, i = e - b * S; X2[e] = c.s_rows[b * c.lds + i]; X2[B * S + e] = c.n_rows[b * c.ldn + i]; }
-    for (int e = tid; e < B * Ai; e += DNT) {
-        const int b = e / Ai, i = e - b * Ai;
-        const float av = action_of(b, i);
-        actin[e] = av;
-        pin[b * C + F + i] = av;
-        for (int k = 0; k < 5; ++k) xc[k][b * C + F + i] = av;
-        for (int k = 0; k < 4; ++k) hc[k][b * C + F + i] = av;
+    lin(icm.feat[0], p.X2, S, 2 * B, p.fh0, Hi, LK); lin(icm.feat[1], p.fh0, Hi, 2 * B, p.fh1, Hi, LK); lin(icm.feat[2], p.fh1, Hi, 2 * B, p.fe, F, -1);
+    gq.run<MAXI>(c.Ps, c.Qs);
+    for (int e = tid; e < B * F; e += DNT) {
+        const int b = e / F, f = e - b * F;
+        const float vs = p.fe[e], vn = p.fe[B * F + e];
+        p.iin[b * 2 * F + f] = vs; p.iin[b * 2 * F + F + f] = vn; p.pin[b * C + f] = vs;
     }
     __syncthreads();
-    auto icm_forward = [&]() {                                  // ICMModel.forward (icm_baseline.py:80-102)
-        lin(icm.feat[0], X2, S, 2 * B, fh0, Hi, LK); lin(icm.feat[1], fh0, Hi, 2 * B, fh1, Hi, LK); lin(icm.feat[2], fh1, Hi, 2 * B, fe, F, -1);
-        gq.run<MAXI>(Ps, Qs);
-        for (int e = tid; e < B * F; e += DNT) {
-            const int b = e / F, f = e - b * F;
-            const float vs = fe[e], vn = fe[B * F + e];
-            iin[b * 2 * F + f] = vs; iin[b * 2 * F + F + f] = vn; pin[b * C + f] = vs;
-        }
-        __syncthreads();
-        lin(icm.inv[0], iin, 2 * F, B, ih0, Hi, RL); lin(icm.inv[1], ih0, Hi, B, ih1, Hi, RL); lin(icm.inv[2], ih1, Hi, B, iz, Ai, -1);
-        lin(icm.pre[0], pin, C, B, ph0, Hi, LK); lin(icm.pre[1], ph0, Hi, B, ph1, Hi, LK); lin(icm.pre[2], ph1, Hi, B, xc[0], C, -1);
-        for (int k = 0; k < 4; ++k) {
-            lin(icm.res[k][0], xc[k], C, B, hc[k], C, LK);
-            const IcmLin &L2 = icm.res[k][1];                   // x_{k+1} = x_k + fc2([fc1([x_k | a]) | a])
-            gq.gemm(hc[k], C, 1, ip + L2.oW, L2.in, 1, B, L2.out, L2.in, epi_bias_add(xc[k + 1], C, ip + L2.ob, xc[k], C));
-        }
-        lin(icm.post[0], xc[4], C, B, qh, Hi, LK); lin(icm.post[1], qh, Hi, B, pred, F, -1);
-        gq.run<MAXI>(Ps, Qs);
-    };
-    icm_forward();
+    lin(icm.inv[0], p.iin, 2 * F, B, p.ih0, Hi, RL); lin(icm.inv[1], p.ih0, Hi, B, p.ih1, Hi, RL); lin(icm.inv[2], p.ih1, Hi, B, p.iz, Ai, -1);
+    lin(icm.pre[0], p.pin, C, B, p.ph0, Hi, LK); lin(icm.pre[1], p.ph0, Hi, B, p.ph1, Hi, LK); lin(icm.pre[2], p.ph1, Hi, B, p.xc[0], C, -1);
+    for (int k = 0; k < 4; ++k) {
+        lin(icm.res[k][0], p.xc[k], C, B, p.hc[k], C, LK);
+        const IcmLin &L2 = icm.res[k][1];                   // x_{k+1} = x_k + fc2([fc1([x_k | a]) | a])
+        gq.gemm(p.hc[k], C, 1, ip + L2.oW, L2.in, 1, B, L2.out, L2.in, epi_bias_add(p.xc[k + 1], C, ip + L2.ob, p.xc[k], C));
+    }
+    lin(icm.post[0], p.xc[4], C, B, p.qh, Hi, LK); lin(icm.post[1], p.qh, Hi, B, p.pred, F, -1);
+    gq.run<MAXI>(c.Ps, c.Qs);
+}
+
+// the loss gradients of the forward pass just run, the backward pass and one step of torch.optim.Adam over all ICM parameters (lr = icm.lr)
+template <int MAXI>
+__device__ __forceinline__ void icm_backward_adam(const IcmStep &c, const IcmPtrs &p)
+{
+    const int tid = (int)threadIdx.x;
+    GemmQueue &gq = c.gq;
+    float *const Ps = c.Ps, *const Qs = c.Qs;
+    const IcmNet &icm = c.icm;
+    volatile float *ctrl = c.ctrl;
+    const int B = c.B, S = icm.S, A = icm.A;
+    const int F = icm.F, Hi = icm.H, Ai = icm.Ai, C = icm.C;
+    auto buf = [&](int i) { return c.arena + c.a_icm[i]; };
+    float *const ip = p.ip, *const ig = p.ig, *const X2 = p.X2, *const actin = p.actin;
+    float *const fh0 = p.fh0, *const fh1 = p.fh1, *const fe = p.fe, *const iin = p.iin, *const ih0 = p.ih0, *const ih1 = p.ih1, *const iz = p.iz;
+    float *const pin = p.pin, *const ph0 = p.ph0, *const ph1 = p.ph1, *const qh = p.qh, *const pred = p.pred;
+    float *const *xc = p.xc, *const *hc = p.hc;
+    constexpr int LK = LENV_ACT_LEAKYRELU, RL = LENV_ACT_RELU;
     // ---- loss gradients: beta * mse(forward, features(s')) and (1 - beta) * BCEWithLogits | CrossEntropy(inverse, action) ----
     float *dpred = buf(IB_DPRED), *dz = buf(IB_DZ), *dqh = buf(IB_DQH), *dx = buf(IB_DX), *dh = buf(IB_DH), *dph1 = buf(IB_DPH1);
     float *dph0 = buf(IB_DPH0), *dfe = buf(IB_DFE), *dih1 = buf(IB_DIH1), *dih0 = buf(IB_DIH0), *diin = buf(IB_DIIN), *dfh1 = buf(IB_DFH1), *dfh0 = buf(IB_DFH0);
@@ -164,7 +199,7 @@ __device__ __forceinline__ void icm_train_and_reward(const IcmStep &c, ActFn act
     bw_w(icm.feat[1], dfh1, Hi, fh0, Hi, 2 * B); bw_x(icm.feat[1], dfh1, Hi, 2 * B, Hi, epi_act_bwd(dfh0, Hi, fh0, Hi, LK, 0.25f));
     bw_w(icm.feat[0], dfh0, Hi, X2, S, 2 * B);
     gq.run<MAXI>(Ps, Qs);
-    // ---- torch.optim.Adam over all ICM parameters (lr = icm.lr), then the intrinsic rewards of the UPDATED model ----
+    // ---- torch.optim.Adam over all ICM parameters (lr = icm.lr) ----
     if (tid == 0) {
         c.pows[0] *= c.adam_beta1; c.pows[1] *= c.adam_beta2;
         ctrl[c.ci] = (float)(-(c.lr / (1.0 - c.pows[0])));
@@ -176,14 +211,52 @@ __device__ __forceinline__ void icm_train_and_reward(const IcmStep &c, ActFn act
         wg_adam(ip, buf(IB_M), buf(IB_V), ig, 0, icm.P, ac, nullptr, 0.0f, 0.0f);
     }
     __syncthreads();
-    icm_forward();
+}
+
+// add_reward(b, eta * mean_f (features(s') - forward)^2) of the forward pass just run (called by one thread per sample)
+template <class RewFn>
+__device__ __forceinline__ void icm_reward_rows(const IcmStep &c, const IcmPtrs &p, RewFn add_reward)
+{
+    const int B = c.B, F = c.icm.F;
     const float eta = (float)c.eta;
-    for (int b = tid; b < B; b += DNT) {                        // rewards += eta * mean_f (features(s') - forward)^2
+    for (int b = (int)threadIdx.x; b < B; b += DNT) {
         float sm = 0.0f;
-        for (int f = 0; f < F; ++f) { const float d = fe[(B + b) * F + f] - pred[b * F + f]; sm = fma32(d, d, sm); }
+        for (int f = 0; f < F; ++f) { const float d = p.fe[(B + b) * F + f] - p.pred[b * F + f]; sm = fma32(d, d, sm); }
         add_reward(b, eta * (sm / (float)F));
     }
     __syncthreads();
+}
+
+// ICM.compute_intrinsic_rewards (icm_baseline.py:160-172) with the module as it is: one forward pass on the B rows, rewards[b] += r
+template <int MAXI, class ActFn, class RewFn>
+__device__ __forceinline__ void icm_rewards(const IcmStep &c, ActFn action_of, RewFn add_reward)
+{
+    const IcmPtrs p = icm_ptrs(c);
+    icm_stage(c, p, action_of);
+    icm_forward<MAXI>(c, p);
+    icm_reward_rows(c, p, add_reward);
+}
+
+// ICM.train (icm_baseline.py:134-158): forward, loss gradients, backward, one Adam step
+template <int MAXI, class ActFn>
+__device__ __forceinline__ void icm_train(const IcmStep &c, ActFn action_of)
+{
+    const IcmPtrs p = icm_ptrs(c);
+    icm_stage(c, p, action_of);
+    icm_forward<MAXI>(c, p);
+    icm_backward_adam<MAXI>(c, p);
+}
+
+// DDQN / TD3: ICM.train on the minibatch, then the intrinsic rewards of the UPDATED model
+template <int MAXI, class ActFn, class RewFn>
+__device__ __forceinline__ void icm_train_and_reward(const IcmStep &c, ActFn action_of, RewFn add_reward)
+{
+    const IcmPtrs p = icm_ptrs(c);
+    icm_stage(c, p, action_of);
+    icm_forward<MAXI>(c, p);
+    icm_backward_adam<MAXI>(c, p);
+    icm_forward<MAXI>(c, p);
+    icm_reward_rows(c, p, add_reward);
 }
 
 }  // namespace lenv

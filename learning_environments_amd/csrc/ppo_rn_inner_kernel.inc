@@ -1,16 +1,23 @@
-// ppo_rn_inner_kernel.inc -- the body of the PPO inner-loop kernel, included twice by ppo_rn_inner_loop.hip (inside namespace lenv):
-//   PPO_RN_KERNEL ppo_rn_inner_kernel,   PPO_RN_SEG false: lenv_ppo_rn_inner_loop, one launch from the first episode to the final test
-//   PPO_RN_KERNEL ppo_rn_segment_kernel, PPO_RN_SEG true:  lenv_ppo_rn_inner_loop_segment, the episodes [a.ep_begin, a.ep_end)
+// ppo_rn_inner_kernel.inc -- the body of the PPO inner-loop kernel, included three times by ppo_rn_inner_loop.hip (inside namespace lenv):
+//   PPO_RN_KERNEL ppo_rn_inner_kernel,    PPO_RN_SEG false: lenv_ppo_rn_inner_loop, one launch from the first episode to the final test
+//   PPO_RN_KERNEL ppo_rn_segment_kernel,  PPO_RN_SEG true:  lenv_ppo_rn_inner_loop_segment, the episodes [a.ep_begin, a.ep_end)
+//   PPO_RN_KERNEL ppo_icm_segment_kernel, PPO_RN_SEG true, PPO_RN_ICM true: lenv_ppo_icm_inner_loop[_segment], PPO(icm=True)
 // SEG: what the loop carries from episode to episode outside the arena -- the counters, the Adam bias-correction powers, actor_old's action_std
 // (LDS), the status -- is read from / written to the chain's resume record (include/lenv_hip.h); the reward net is staged by every segment, the
 // agent only by the first; the closing part runs in the segment in which the chain ends.  Everything SEG adds stands under `if constexpr (SEG)`:
 // ppo_rn_inner_kernel compiles to the instruction stream it had before the segments existed.  Two kernels of their own names rather than one
 // template with a SEG parameter or a shared inlined body: the first would rename the kernels the other entry point launches, the second
 // changes how the compiler reads the kernel arguments and with it the code of both.
+// ICM (PPO.py:46-62,144-145,183-184): the chain's Intrinsic Curiosity Module (lenv_icm.cuh) lives in the arena next to a next-observation row
+// buffer XN; learn() adds the intrinsic rewards of the module AS IT IS to the rows' rewards before the return scan and trains the module once,
+// on all rows, after the last epoch; the module's Adam has its own step counter (resume words 22..23).  Everything ICM adds stands under
+// `if constexpr (ICM)`.
 template <int ENV>
 __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
 {
     constexpr bool SEG = PPO_RN_SEG;
+    constexpr bool ICM = PPO_RN_ICM;
+    static_assert(SEG || !ICM, "the ICM instantiation always has segment capability");
     using EnvT = ContEnv<ENV>;
     extern __shared__ __align__(16) float lds[];
     const lenv_ppo_cfg &cfg = a.cfg;
@@ -54,7 +61,8 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
     double *ret = xt_d + 20;                             // [PP_MAXT]
     volatile float *ctrl = misc;
     volatile int *ictrl = reinterpret_cast<volatile int *>(misc + 32);
-    // the control words in use: ctrl[12..17] (reward net, LayerNorm rows, the returns' mean / std), ictrl[3] = misc[35];
+    // the control words in use: ctrl[12..17] (reward net, LayerNorm rows, the returns' mean / std), ctrl[20..21] (ICM: its Adam's bias
+    // corrections), ictrl[3] = misc[35];
     // misc[MISC_STATUS_FOLD] (an int): the SEG instantiations' fold of the threads' status codes
     constexpr int MISC_STATUS_FOLD = 48;
 
@@ -65,6 +73,8 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
     float *ha[PP_MAXL], *hc[PP_MAXL], *dbuf[2] = { arena + a.a_d[0], arena + a.a_d[1] };
     for (int l = 0; l < PP_MAXL; ++l) { ha[l] = arena + a.a_ha[l]; hc[l] = arena + a.a_hc[l]; }
     double *meter = reinterpret_cast<double *>(arena + a.a_meter);
+    float *XN = arena + a.a_xn;                           // ICM: next observation of every row [N][S] (s' is not the next row's s
+                                                         // at an episode end or with same_action_num > 1)
 
     // ---- stage the perturbed reward network (GTN_worker.py:165-175) and the fresh agent (PPO.py:35-44) ----
     {
@@ -78,6 +88,14 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
     if (fresh) for (int p = tid; p < a.P; p += DNT) {
         const int q = p < A ? p : (p < A + a.Pa ? oA + (p - A) : oC + (p - A - a.Pa));
         params[q] = a.agent_init[chain * a.P + p];
+    }
+    // fresh ICM (continuous actions: the action vector is the model input, MSE inverse loss -- icm_baseline.py:118-119)
+    IcmNet icm;
+    double icm_pows[2] = { 1.0, 1.0 };
+    if constexpr (ICM) {
+        icm_build(icm, S, A, a.icm_F, a.icm_H, /*discrete=*/false);
+        float *ip = arena + a.a_icm[IB_P], *im = arena + a.a_icm[IB_M], *iv = arena + a.a_icm[IB_V];
+        if (fresh) for (int p = tid; p < icm.P; p += DNT) { ip[p] = a.icm_init[chain * a.P_icm + p]; im[p] = 0.0f; iv[p] = 0.0f; }
     }
     if (tid < 64) misc[tid] = 0.0f;
     if (tid < 48) stdv[tid] = 0.0f;
@@ -100,6 +118,7 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
             n_actn = rec[3]; n_testn = rec[4]; n_test_ep = rec[5]; time_step = rec[6]; n_rows = (int)rec[7];
             train_steps = (int)rec[8]; test_steps = (int)rec[9]; episodes_run = (int)rec[10]; learn_calls = (int)rec[11];
             for (int i = 0; i < 2; ++i) pows[i] = __longlong_as_double(rec[12 + i]);
+            if constexpr (ICM) for (int i = 0; i < 2; ++i) icm_pows[i] = __longlong_as_double(rec[22 + i]);
         }
     }
     GemmQueue gq(cmds);
@@ -230,6 +249,13 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
 
     // ================= PPO.learn (PPO.py:136-188) on rows [0, n) =================
     auto learn = [&](int n) {
+        auto icm_step = [&]() {
+            return IcmStep{ gq, Ps, Qs, arena, a.a_icm, ctrl, 20, icm, icm_pows, a.icm_lr, a.icm_beta, a.icm_eta, cfg.adam_beta1,
+                            cfg.adam_beta2, cfg.adam_eps, n, X, S, XN, S, /*continuous=*/true };
+        };
+        auto icm_action = [&](int b, int i) { return ACT[b * A + i]; };
+        // rewards += icm.compute_intrinsic_rewards(states, next_states, actions): the module as the last call left it (PPO.py:144-145)
+        if constexpr (ICM) icm_rewards<PP_MAXI>(icm_step(), icm_action, [&](int b, float r) { REW[b] = REW[b] + r; });
         // discounted returns: one backward scan that restarts where done > 0.5, then (R - mean) / (std + 1e-5) with the unbiased std; the scan
         // and the two fp64 sums run left to right in thread 0 over an LDS copy of the rows' rewards / done flags (the idle staging buffer)
         for (int i = tid; i < n; i += DNT) { Ps[i] = REW[i]; Ps[PP_MAXN + i] = DONE[i]; }
@@ -298,6 +324,7 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
             wg_adam(params, adam_m, adam_v, grad, 0, PP, ac, nullptr, 0.0f, 0.0f);
             __syncthreads();
         }
+        if constexpr (ICM) icm_train<PP_MAXI>(icm_step(), icm_action);      // icm.train(states, next_states, actions) (PPO.py:183-184)
         if (tid < A) stdv[tid] = params[tid];             // actor_old.load_state_dict(actor.state_dict())
         if (a.out.learn_step && learn_calls < a.out.learn_cap) {
             const int64_t k = chain * a.out.learn_cap + learn_calls;
@@ -372,6 +399,7 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
                 if (tid < S) X[n_rows * S + tid] = newrow[tid];
                 if (tid >= 64 && tid < 64 + A) ACT[n_rows * A + tid - 64] = newrow[S + tid - 64];
                 if (tid == 128) { REW[n_rows] = shaped_sum; DONE[n_rows] = done_f; }
+                if constexpr (ICM) { if (tid >= 192 && tid < 192 + S) XN[n_rows * S + tid - 192] = newrow[S + A + tid - 192]; }
                 ++n_rows;
             } else status = -4;
             if (a.out.trace_reward && train_steps < a.out.trace_cap) {
@@ -416,6 +444,9 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
                     a.out.final_params[chain * a.P + p] = params[q];
                 }
             }
+            if constexpr (ICM) {
+                if (a.icm_final) for (int p = tid; p < icm.P; p += DNT) a.icm_final[chain * a.P_icm + p] = arena[a.a_icm[IB_P] + p];
+            }
             __syncthreads();
             if (tid == 0) {
                 if (a.out.stats) {
@@ -424,6 +455,7 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
                 }
                 ppo_write_record(rec, a.ep_end, 0, *st_fold, n_actn, n_testn, n_test_ep, time_step, n_rows, train_steps, test_steps, episodes_run,
                                  learn_calls, pows, stdv);
+                if constexpr (ICM) for (int i = 0; i < 2; ++i) rec[22 + i] = __double_as_longlong(icm_pows[i]);
             }
             return;
         }
@@ -449,12 +481,18 @@ __global__ __launch_bounds__(DNT) void PPO_RN_KERNEL(const PpoArgs a)
             a.out.final_params[chain * a.P + p] = params[q];
         }
     }
+    if constexpr (ICM) {
+        if (a.icm_final) for (int p = tid; p < icm.P; p += DNT) a.icm_final[chain * a.P_icm + p] = arena[a.a_icm[IB_P] + p];
+    }
     if (a.out.status && status != 0) atomicMin(&a.out.status[chain], status);
     if constexpr (SEG) {
         int *st_fold = reinterpret_cast<int *>(misc + MISC_STATUS_FOLD);
         if (status != 0) atomicMin(st_fold, status);
         __syncthreads();
-        if (tid == 0) ppo_write_record(rec, a.ep_end, 1, *st_fold, n_actn, n_testn, n_test_ep, time_step, n_rows, train_steps, test_steps, episodes_run,
-                                       learn_calls, pows, stdv);
+        if (tid == 0) {
+            ppo_write_record(rec, a.ep_end, 1, *st_fold, n_actn, n_testn, n_test_ep, time_step, n_rows, train_steps, test_steps, episodes_run,
+                             learn_calls, pows, stdv);
+            if constexpr (ICM) for (int i = 0; i < 2; ++i) rec[22 + i] = __double_as_longlong(icm_pows[i]);
+        }
     }
 }

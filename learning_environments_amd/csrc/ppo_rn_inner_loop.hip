@@ -15,13 +15,16 @@
 // derivatives (ppo_row_grads) are one thread per row; the returns scan, their mean and variance run left to right in one thread over an LDS copy.
 // Gaussian draws come from tapes (parity mode) or the counter RNG through the deterministic Box-Muller.
 //
-// The kernel's body is ppo_rn_inner_kernel.inc, compiled twice: ppo_rn_inner_kernel (one launch from the first episode to the final test) and
-// ppo_rn_segment_kernel (lenv_ppo_rn_inner_loop_segment: episodes [begin, end) with a resume record per chain).
+// The kernel's body is ppo_rn_inner_kernel.inc, compiled three times: ppo_rn_inner_kernel (one launch from the first episode to the final test),
+// ppo_rn_segment_kernel (lenv_ppo_rn_inner_loop_segment: episodes [begin, end) with a resume record per chain) and ppo_icm_segment_kernel
+// (lenv_ppo_icm_inner_loop / _segment: PPO(icm=True), the segment kernel with the Intrinsic Curiosity Module of lenv_icm.cuh inside learn;
+// CPU restatement: tests/ppo_icm_ref.c).
 //
 // Refused (LENV_ERR_UNSUPPORTED from the queries, before a launch): hidden > 128, more than two hidden layers, rows outside [2, 2048], more than
 // 64 test episodes, an agent PReLU (its slope would be a trained parameter), LayerNorm in the agent nets (lenv_ppo_cfg has no field for it:
 // config.ppo_cfg_from_config refuses) and in a reward net with two or more hidden layers.  CPU restatement: tests/ppo_ref.c.
 #include "lenv_gemm.cuh"
+#include "lenv_icm.cuh"
 #include "lenv_rn.cuh"
 #include "lenv_host.h"
 
@@ -62,6 +65,12 @@ struct PpoArgs {
     // lenv_ppo_rn_inner_loop_segment (ppo_rn_segment_kernel): episodes [ep_begin, ep_end) of every chain, resume records [chains, LENV_PPO_RESUME_WORDS];
     // the other entry point: 0, train_episodes, nullptr.  (Behind everything else: ppo_rn_inner_kernel reads its arguments where they were.)
     int ep_begin, ep_end; int64_t *resume;
+    // lenv_ppo_icm_inner_loop[_segment] (ppo_icm_segment_kernel): the module's shapes and settings, fresh parameters per chain, optional final
+    // parameters, the arena offsets of the next-observation rows and of the IB_* buffers.  (Behind everything else, as above.)
+    int icm_F, icm_H, P_icm;
+    double icm_lr, icm_beta, icm_eta;
+    const float *icm_init; float *icm_final;
+    int64_t a_xn, a_icm[IB_COUNT];
 };
 
 // log-probability of action a under Normal(mean, std) summed over the action dims, left to right (torch.distributions.Normal.log_prob);
@@ -124,6 +133,7 @@ static_assert(14 + PP_STD <= LENV_PPO_RESUME_WORDS, "the record holds the counte
 
 #define PPO_RN_KERNEL ppo_rn_inner_kernel
 #define PPO_RN_SEG false
+#define PPO_RN_ICM false
 #include "ppo_rn_inner_kernel.inc"
 #undef PPO_RN_KERNEL
 #undef PPO_RN_SEG
@@ -131,7 +141,13 @@ static_assert(14 + PP_STD <= LENV_PPO_RESUME_WORDS, "the record holds the counte
 #define PPO_RN_SEG true
 #include "ppo_rn_inner_kernel.inc"
 #undef PPO_RN_KERNEL
+#undef PPO_RN_ICM
+#define PPO_RN_KERNEL ppo_icm_segment_kernel
+#define PPO_RN_ICM true
+#include "ppo_rn_inner_kernel.inc"
+#undef PPO_RN_KERNEL
 #undef PPO_RN_SEG
+#undef PPO_RN_ICM
 
 }  // namespace lenv
 
@@ -149,7 +165,8 @@ static int64_t ppo_rows_of(const lenv_ppo_cfg *cfg)
     return n;
 }
 
-static int ppo_layout(const lenv_ppo_cfg *cfg, PpoArgs &a, size_t *lds_bytes)
+// icm_F > 0: the layout of lenv_ppo_icm_* (the ICM-less arena, then the next-observation rows and the module's buffers for N rows)
+static int ppo_layout(const lenv_ppo_cfg *cfg, PpoArgs &a, size_t *lds_bytes, int icm_F = 0, int icm_H = 0)
 {
     const int H = cfg->hidden, L = cfg->layers, T = cfg->test_episodes, Hrn = cfg->rn_hidden;
     const int S = cfg->state_dim, A = cfg->action_dim;
@@ -185,6 +202,17 @@ static int ppo_layout(const lenv_ppo_cfg *cfg, PpoArgs &a, size_t *lds_bytes)
     a.a_d[0] = c.take(N * H); a.a_d[1] = c.take(N * H);
     a.a_meter = c.take(2 * (int64_t)(cfg->train_episodes > 0 ? cfg->train_episodes : 1));
     a.a_rn = c.take(rn_theta_in_lds(t, cfg->rn_layers) ? 0 : a.P_rn);
+    a.icm_F = icm_F; a.icm_H = icm_H; a.P_icm = 0; a.a_xn = 0;
+    for (int i = 0; i < IB_COUNT; ++i) a.a_icm[i] = 0;
+    if (icm_F > 0) {
+        IcmNet n;
+        icm_build(n, S, A, icm_F, icm_H, /*discrete=*/false);
+        a.P_icm = n.P;
+        a.a_xn = c.take(N * S);
+        int64_t sz[IB_COUNT];
+        icm_buffer_sizes(n, (int)N, sz);
+        for (int i = 0; i < IB_COUNT; ++i) a.a_icm[i] = c.take(sz[i]);
+    }
     a.arena_stride = c.total();
     const size_t lds_floats = GemmShape<PP_MAXI>::PS_FLOATS + GemmShape<PP_MAXI>::QS_FLOATS + GEMM_QUEUE_MAX * sizeof(GemmCmd) / sizeof(float) +
                               ((a.P_rn_lds + 3) & ~3) + 2 * ((Hrn + 3) & ~3) + 2 * PP_MAXW + 64 + 48 + 20 + 20 + 8 + 8 + 64 + 2 + 2 * (20 + 20 + PP_MAXT) + 16;
@@ -287,4 +315,82 @@ extern "C" int lenv_ppo_rn_inner_loop_segment(const lenv_ppo_cfg *cfg, const flo
 {
     return ppo_launch(cfg, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, true, episode_begin,
                       episode_end, resume, stream);
+}
+
+// ---- PPO(icm=True): lenv_ppo_icm_* (ppo_icm_segment_kernel behind both launch entries) ----
+
+static int ppo_icm_layout(const lenv_ppo_cfg *cfg, int32_t F, int32_t H, PpoArgs &a, size_t *lds_bytes)
+{
+    if (F < 1 || F > 128 || H < 1 || H > 128) return LENV_ERR_UNSUPPORTED;
+    return ppo_layout(cfg, a, lds_bytes, F, H);
+}
+
+extern "C" int64_t lenv_ppo_icm_num_params(const lenv_ppo_cfg *cfg, int32_t icm_feature_dim, int32_t icm_hidden)
+{
+    if (!cfg) return LENV_ERR_INVALID;
+    PpoArgs a;
+    size_t lds;
+    const int rc = ppo_icm_layout(cfg, icm_feature_dim, icm_hidden, a, &lds);
+    return rc != LENV_OK ? rc : a.P_icm;
+}
+
+// the chains' arenas, then (256-byte aligned: the stride is a multiple of 64 floats) the resume records of the single-launch entry
+extern "C" int64_t lenv_ppo_icm_workspace_bytes(const lenv_ppo_cfg *cfg, int32_t icm_feature_dim, int32_t icm_hidden, int64_t chains)
+{
+    if (!cfg || chains < 0) return LENV_ERR_INVALID;
+    PpoArgs a;
+    size_t lds;
+    const int rc = ppo_icm_layout(cfg, icm_feature_dim, icm_hidden, a, &lds);
+    if (rc != LENV_OK) return rc;
+    return chains * a.arena_stride * (int64_t)sizeof(float) + chains * LENV_PPO_RESUME_WORDS * (int64_t)sizeof(int64_t) + 256;
+}
+
+// segment false: episodes [0, train_episodes) in one launch, the records in the workspace behind the arenas
+static int ppo_icm_launch(const lenv_ppo_cfg *cfg, int32_t F, int32_t H, double icm_lr, double icm_beta, double icm_eta, const lenv_icm_io *icm,
+                          const float *theta, const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
+                          const uint64_t *rng_keys, const lenv_ppo_tapes *tapes, int64_t chains, void *workspace, size_t workspace_bytes,
+                          const lenv_ppo_out *out, bool segment, int32_t ep_begin, int32_t ep_end, int64_t *resume, void *stream)
+{
+    const lenv_host::Segment seg{segment, ep_begin, ep_end, resume};
+    if (!lenv_host::launch_args_ok(cfg, nullptr, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, out, seg)) return LENV_ERR_INVALID;
+    if (!icm || !icm->icm_init) return LENV_ERR_INVALID;
+    if (!theta && cfg->reward_env_type != 0) return LENV_ERR_INVALID;
+    if (cfg->rng_mode == LENV_RNG_TAPE && (!tapes->act_noise || !tapes->test_noise || !tapes->train_reset || !tapes->test_reset)) return LENV_ERR_INVALID;
+    if (cfg->rng_mode != LENV_RNG_COUNTER && cfg->rng_mode != LENV_RNG_TAPE) return LENV_ERR_INVALID;
+    if (out->trace_reward && out->trace_cap > 0 && (!out->trace_action || !out->trace_state || !out->trace_next_state)) return LENV_ERR_INVALID;
+    PpoArgs a;
+    size_t lds_bytes;
+    const int rc = ppo_icm_layout(cfg, F, H, a, &lds_bytes);
+    if (rc != LENV_OK) return rc;
+    if (chains == 0) return LENV_OK;
+    const size_t arena_bytes = (size_t)chains * a.arena_stride * sizeof(float);
+    if (workspace_bytes < arena_bytes + (segment ? 0 : (size_t)chains * LENV_PPO_RESUME_WORDS * sizeof(int64_t))) return LENV_ERR_WORKSPACE;
+    lenv_host::fill_args(a, cfg, theta, eps, worker, sign, agent_init, rng_keys, tapes, workspace, out);
+    lenv_host::fill_segment(a, cfg, seg);
+    if (!segment) a.resume = reinterpret_cast<int64_t *>(static_cast<char *>(workspace) + arena_bytes);
+    a.icm_lr = icm_lr; a.icm_beta = icm_beta; a.icm_eta = icm_eta; a.icm_init = icm->icm_init; a.icm_final = icm->icm_final;
+    if (a.out.trace_cap <= 0) a.out.trace_reward = nullptr;
+    if (a.out.learn_cap <= 0) a.out.learn_step = nullptr;
+    void (*kern)(const PpoArgs) = cfg->env_id == LENV_ENV_PENDULUM ? ppo_icm_segment_kernel<LENV_ENV_PENDULUM>
+                                  : (cfg->env_id == LENV_ENV_CMC ? ppo_icm_segment_kernel<LENV_ENV_CMC> : ppo_icm_segment_kernel<LENV_ENV_CHEETAH_STANDIN>);
+    return lenv_host::launch(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, stream, a);
+}
+
+extern "C" int lenv_ppo_icm_inner_loop(const lenv_ppo_cfg *cfg, int32_t icm_feature_dim, int32_t icm_hidden, double icm_lr, double icm_beta,
+                                       double icm_eta, const lenv_icm_io *icm, const float *theta, const float *eps, const int32_t *worker,
+                                       const float *sign, const float *agent_init, const uint64_t *rng_keys, const lenv_ppo_tapes *tapes,
+                                       int64_t chains, void *workspace, size_t workspace_bytes, const lenv_ppo_out *out, void *stream)
+{
+    return ppo_icm_launch(cfg, icm_feature_dim, icm_hidden, icm_lr, icm_beta, icm_eta, icm, theta, eps, worker, sign, agent_init, rng_keys, tapes,
+                          chains, workspace, workspace_bytes, out, false, 0, 0, nullptr, stream);
+}
+
+extern "C" int lenv_ppo_icm_inner_loop_segment(const lenv_ppo_cfg *cfg, int32_t icm_feature_dim, int32_t icm_hidden, double icm_lr,
+                                               double icm_beta, double icm_eta, const lenv_icm_io *icm, const float *theta, const float *eps,
+                                               const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                                               const lenv_ppo_tapes *tapes, int64_t chains, void *workspace, size_t workspace_bytes,
+                                               const lenv_ppo_out *out, int32_t episode_begin, int32_t episode_end, int64_t *resume, void *stream)
+{
+    return ppo_icm_launch(cfg, icm_feature_dim, icm_hidden, icm_lr, icm_beta, icm_eta, icm, theta, eps, worker, sign, agent_init, rng_keys, tapes,
+                          chains, workspace, workspace_bytes, out, true, episode_begin, episode_end, resume, stream);
 }

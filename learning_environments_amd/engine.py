@@ -684,7 +684,10 @@ class PpoInnerLoop(_SegmentedInnerLoop):
         if self.learn_cap:
             self.learn_step = torch.zeros((self.chains, self.learn_cap), dtype=torch.int32, device=self.dev)
             self.learn_params = torch.zeros((self.chains, self.learn_cap, self.p_agent), dtype=torch.float32, device=self.dev)
-        self._alloc_outputs(_count("lenv_ppo_rn_workspace_bytes", C.byref(cfg), self.chains), want_episode_stats, want_final_params, trace_cap)
+        self._alloc_outputs(self._workspace_bytes(), want_episode_stats, want_final_params, trace_cap)
+
+    def _workspace_bytes(self):
+        return _count("lenv_ppo_rn_workspace_bytes", C.byref(self.cfg), self.chains)
 
     def _ppo_args(self, theta, eps, worker, sign, agent_init, rng_keys, tapes):
         args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
@@ -694,6 +697,33 @@ class PpoInnerLoop(_SegmentedInnerLoop):
 
     def _launch_args(self, theta, eps, worker, sign, agent_init, rng_keys, tapes, segment=False):
         return self._ppo_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
+
+
+class PpoIcmInnerLoop(PpoInnerLoop):
+    """PPO(icm=True), the transfer scripts' `ppo_icm` agent, through lenv_ppo_icm_inner_loop: PpoInnerLoop with a fresh Intrinsic
+    Curiosity Module per chain.  icm = dict(feature_dim, hidden_size, lr, beta, eta), the config's `icm` section; icm_init
+    [chains, p_icm] (fill it, or draw_icm_init) are the modules' start parameters, icm_final receives them after the run."""
+    entry = ("lenv_ppo_icm_inner_loop",) * 2
+    segment_entry = "lenv_ppo_icm_inner_loop_segment"
+    prefix = ("icm_feature_dim", "icm_hidden", "icm_lr", "icm_beta", "icm_eta", "icm")
+
+    def __init__(self, cfg, chains, icm, **kw):
+        self.icm_settings = dict(feature_dim=int(icm["feature_dim"]), hidden_size=int(icm["hidden_size"]), lr=float(icm["lr"]),
+                                 beta=float(icm["beta"]), eta=float(icm["eta"]))
+        self.icm = True
+        self.p_icm = _count("lenv_ppo_icm_num_params", C.byref(cfg), self.icm_settings["feature_dim"], self.icm_settings["hidden_size"])
+        super().__init__(cfg, chains, **kw)
+        self.icm_init = torch.zeros((self.chains, self.p_icm), dtype=torch.float32, device=self.dev)
+        self.icm_final = torch.zeros((self.chains, self.p_icm), dtype=torch.float32, device=self.dev)
+        self.icm_io = _lib.IcmIo(_ptr(self.icm_init), _ptr(self.icm_final))
+
+    def _workspace_bytes(self):
+        return _count("lenv_ppo_icm_workspace_bytes", C.byref(self.cfg), self.icm_settings["feature_dim"], self.icm_settings["hidden_size"],
+                      self.chains)
+
+    def _prefix_args(self):
+        s = self.icm_settings
+        return (s["feature_dim"], s["hidden_size"], s["lr"], s["beta"], s["eta"], self._icm_arg())
 
 
 def rn_shape_population(cfg, theta, eps, worker, sign, next_state, reward, chains=1):

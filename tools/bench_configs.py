@@ -260,17 +260,23 @@ def run_dueling_episode_time(name, cfgd, shape, chains=8, episodes=300, lr=1e-3)
     return out
 
 
-def _ppo_loop(cfgd, chains, models=1, seed=0, **over):
+def _ppo_loop(cfgd, chains, models=1, seed=0, icm=None, **over):
     """A PpoInnerLoop at cfgd's PPO shape with seeded inputs: (inner loop, run arguments, keyword arguments).  models > 1: chain c reads reward net
-    c // (chains / models) through its eps row (theta 0, sign 1), as experiments/transfer_algo.py launches the models of a mode."""
+    c // (chains / models) through its eps row (theta 0, sign 1), as experiments/transfer_algo.py launches the models of a mode.  icm (a dict of
+    the config's `icm` section): a PpoIcmInnerLoop with seeded fresh modules instead."""
     import numpy as np
     from learning_environments_amd import engine
     from learning_environments_amd.agents.nes_common import linear_init_bounds
-    from learning_environments_amd.config import ppo_cfg_from_config, ppo_layer_dims
+    from learning_environments_amd.config import icm_layer_dims, ppo_cfg_from_config, ppo_layer_dims
     cfg = ppo_cfg_from_config(cfgd, **over)
-    il = engine.PpoInnerLoop(cfg, chains, want_episode_stats=True, want_final_params=True)
     rng = np.random.RandomState(seed)
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    if icm is None:
+        il = engine.PpoInnerLoop(cfg, chains, want_episode_stats=True, want_final_params=True)
+    else:
+        il = engine.PpoIcmInnerLoop(cfg, chains, icm, want_episode_stats=True, want_final_params=True)
+        ib = linear_init_bounds(icm_layer_dims(cfg, icm["feature_dim"], icm["hidden_size"]))
+        il.icm_init.copy_(dev((np.random.RandomState(seed + 1).uniform(-1.0, 1.0, (chains, il.p_icm)) * ib[None]).astype(np.float32)))
     p_theta = max(1, il.p_theta)
     nets = (rng.randn(models, p_theta) * 0.1).astype(np.float32)
     bounds = np.concatenate([np.zeros(cfg.action_dim, np.float32), linear_init_bounds(ppo_layer_dims(cfg))])
@@ -285,17 +291,72 @@ def _ppo_loop(cfgd, chains, models=1, seed=0, **over):
     return il, pos, dict(rng_keys=keys)
 
 
-def run_ppo_episode_time(name, env_name, episodes, models=10, agents=10, seed=0):
+def run_ppo_icm_cost(name, cfgd, chains, icm, runs=7):
+    """The ICM's cost on one shape: the same seeded launch through lenv_ppo_rn_inner_loop and through lenv_ppo_icm_inner_loop, a warm-up of each, then
+    `runs` alternating launches of each timed with the host clock around a synchronise; medians, and the difference per learn call of a chain."""
+    loops = {"without_icm": _ppo_loop(cfgd, chains), "with_icm": _ppo_loop(cfgd, chains, icm=icm)}
+    times = {k: [] for k in loops}
+    for r in range(runs + 1):
+        for k, (il, pos, kw) in loops.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            il.run(*pos, **kw)
+            torch.cuda.synchronize()
+            if r:
+                times[k].append(time.perf_counter() - t0)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    calls = {k: float(l[0].stats[:, 2].cpu().numpy().mean()) for k, l in loops.items()}
+    il = loops["with_icm"][0]
+    out = dict(config=name, chains=chains, runs_each=runs, rows_per_learn=il.rows, ppo_epochs=il.cfg.ppo_epochs, icm=icm, s_median=med,
+               s_spread={k: max(v) - min(v) for k, v in times.items()}, s_samples={k: [round(t, 5) for t in v] for k, v in times.items()},
+               learn_calls_per_chain=calls, ms_icm_per_learn_call=1e3 * (med["with_icm"] - med["without_icm"]) / max(1.0, calls["with_icm"]),
+               ratio_with_to_without=med["with_icm"] / med["without_icm"], workspace_MiB={k: l[0].ws_bytes / 2.0 ** 20 for k, l in loops.items()},
+               status_ok=all(int(l[0].status.min()) == 0 for l in loops.values()))
+    print(json.dumps(out))
+    return out
+
+
+def run_ppo_entry_builds(name, cfgd, chains, other_lib, runs=7):
+    """lenv_ppo_rn_inner_loop of this build against the same entry of another build of the library (the parent commit's: its path is the
+    caller's), one seeded launch, a warm-up of each, then `runs` alternating launches; medians and whether the outputs agree bit for bit."""
+    import ctypes as C
+    from learning_environments_amd import _lib
+    il, pos, kw = _ppo_loop(cfgd, chains)
+    args = il._launch_args(*pos, kw["rng_keys"], None)
+    other = C.CDLL(os.path.abspath(other_lib))
+    fns = {"this_build": _lib.lib().lenv_ppo_rn_inner_loop, "other_build": other.lenv_ppo_rn_inner_loop}
+    fns["other_build"].restype, fns["other_build"].argtypes = _lib.SIGNATURES["lenv_ppo_rn_inner_loop"]
+    times, snaps = {k: [] for k in fns}, {}
+    for r in range(runs + 1):
+        for k, fn in fns.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _lib.check(fn(C.byref(il.cfg), *args), k)
+            torch.cuda.synchronize()
+            if r:
+                times[k].append(time.perf_counter() - t0)
+            snaps[k] = [getattr(il, n).cpu().numpy().tobytes() for n in ("score", "stats", "status", "episode_test_mean", "episode_len", "final_params")]
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    out = dict(config=name, runs_each=runs, s_median=med, s_spread={k: max(v) - min(v) for k, v in times.items()},
+               s_samples={k: [round(t, 5) for t in v] for k, v in times.items()}, ratio_this_to_other=med["this_build"] / med["other_build"],
+               bit_identical=snaps["this_build"] == snaps["other_build"], status_ok=bool(int(il.status.min()) == 0))
+    print(json.dumps(out))
+    return out
+
+
+def run_ppo_episode_time(name, env_name, episodes, models=10, agents=10, seed=0, icm=None):
     """Seconds per episode of the PPO transfer scripts' chains: models x agents chains at experiments/transfer_algo.py's PPO_SETTINGS of the env on a
     RewardEnv of the real env at full episode length, `episodes` segment launches of ONE episode each, every one timed on its own (the first is
     the warm-up and is left out); segments in which some chain ran PPO.learn and segments in which none did are reported apart (a segment lasts
-    as long as its slowest chain)."""
+    as long as its slowest chain).  icm: the chains of mode -1 (ppo_icm agents on the real env, the module of that dict) instead."""
     from learning_environments_amd.experiments import transfer_algo as ta
     cfgd = ta.base_config(env_name)
     cfgd["agents"]["ppo"] = dict(ta.PPO_SETTINGS[env_name])
     cfgd["envs"][env_name]["solved_reward"] = ta.SOLVED_REWARD[env_name]
+    if icm is not None:
+        cfgd["envs"][env_name]["reward_env_type"] = 0
     chains = models * agents
-    il, pos, kw = _ppo_loop(cfgd, chains, models=models, seed=seed, train_episodes=episodes)
+    il, pos, kw = _ppo_loop(cfgd, chains, models=models if icm is None else 1, seed=seed, icm=icm, train_episodes=episodes)
     calls = [0]
     times = _timed_segments(il, pos, kw, episodes, after=lambda: calls.append(int(il.stats[:, 2].sum())))
     learned = [b > a for a, b in zip(calls[:-1], calls[1:])]
@@ -691,6 +752,26 @@ if __name__ == "__main__":
         # from the second
         run_ppo_episode_time("MountainCarContinuous RN (999 steps, same_action_num 5) + PPO 64x2, 1 999 rows x 80 epochs", "MountainCarContinuous-v0", 23)
         run_ppo_episode_time("HalfCheetah-standin RN (1000 steps) + PPO 128x2 tanh, 1 001 rows x 10 epochs", "HalfCheetah-v3", 7)
+    if "ppo_icm" in which:
+        from learning_environments_amd.experiments import transfer_algo as ta
+        # (a) the README's PPO row shape (64 x 2 relu, Pendulum RewardEnv, 10 episodes x 200 steps = one learn call of 1 001 rows x 10 epochs per chain)
+        # at 48 and 192 chains, with the transfer scripts' module (feature_dim 32, hidden 128) against the ICM-less entry of the same build
+        icm = dict(ta.ICM_SETTINGS["MountainCarContinuous-v0"])
+        for pop in (16, 64):
+            c = configs.fixed_work(configs.pendulum_reward_env_ppo(pop, train_episodes=10, ppo_epochs=10), 10)
+            run_ppo_icm_cost("Pendulum RN + PPO 64x2, %d chains, 10 episodes x 200 steps, 1 learn call x 10 epochs x 1001 rows: ICM 32/128 against none"
+                             % (3 * pop), c, 3 * pop, icm)
+        # (b) the two scripts' mode -1 chains (10 x 10 ppo_icm agents on the real env) at full episode length, with and without a learn call
+        run_ppo_episode_time("MountainCarContinuous (999 steps, same_action_num 5) + PPO 64x2 + ICM 32/128, 1 999 rows x 80 epochs",
+                             "MountainCarContinuous-v0", 23, icm=dict(ta.ICM_SETTINGS["MountainCarContinuous-v0"]))
+        run_ppo_episode_time("HalfCheetah-standin (1000 steps) + PPO 128x2 tanh + ICM 32/128, 1 001 rows x 10 epochs", "HalfCheetah-v3", 7,
+                             icm=dict(ta.ICM_SETTINGS["HalfCheetah-v3"]))
+    if "ppo_entry_builds" in which:
+        # (c) the ICM-less single-launch entry on this build against another build of the library (usage: ppo_entry_builds <path of the other .so>):
+        # the shape of ppo_segments
+        c = configs.fixed_work(configs.pendulum_reward_env_ppo(16, train_episodes=60), 60)
+        run_ppo_entry_builds("lenv_ppo_rn_inner_loop, Pendulum RN + PPO 64x2, 48 chains, 60 episodes x 200 steps: this build / the other build", c, 48,
+                             which[which.index("ppo_entry_builds") + 1])
     if "rn_step" in which:
         # the one-step population API on a RewardEnv: 192 chains (64 workers) of the HalfCheetah stand-in, reward type 2, reward net 17-128-1, one
         # launch against one env-step launch + 192 shaping launches per repeat; a warm-up, then the medians of 7 alternating runs
