@@ -881,6 +881,47 @@ int lenv_agent_test_population(const lenv_ddqn_cfg *cfg /*HOST*/, const float *p
                                float *row_state /*[agents, T, cap, S]*/, int32_t *row_action /*[agents, T, cap]*/, float *row_next_state,
                                float *row_reward /*[agents, T, cap]*/, float *row_done, void *stream);
 
+/*
+ * BaseAgent.test of a population of trained TD3 / PPO agents in one launch, as a call of its own: the continuous-control half of
+ * lenv_agent_test_population.  kind = LENV_ACTOR_TD3 (cfg is a lenv_td3_cfg; agents "td3" and "td3_vary" with vary_hp off) or LENV_ACTOR_PPO
+ * (cfg is a lenv_ppo_cfg); any other kind is LENV_ERR_UNSUPPORTED -- TD3_discrete_vary (a Gumbel-softmax actor with an annealed temperature)
+ * and the gridworld agents have none.  Agent i runs T = cfg->test_episodes episodes on the real env cfg->env_id (the HalfCheetah-v3 stand-in,
+ * Pendulum-v0, MountainCarContinuous-v0) with the operations of the fused loops' closing test:
+ *   TD3 (TD3.select_test_action): a = clamp(max_action * tanh(actor(s)) + (z * (float)action_std) * max_action, +-max_action),
+ *       z = normal(rng_keys[i], TD3 test-noise stream, ((episode_offset[i] + e) * max_steps + agent_step) * A + k);
+ *   PPO (actor_old.forward): a = tanh(net(s)) + z * max(action_std, 0.001f), action_std = the first A words of the row (a final_params row
+ *       carries the trained, unclamped parameter: actor_old's copy differs from it by this clamp alone),
+ *       z = normal(rng_keys[i], PPO test-noise stream, ((episode_offset[i] + e) * cap + agent_step) * A + k);
+ * the action same_action_num times or until done, TimeLimit at max_steps env steps, each agent step's reward the fp64 sum of its repeats
+ * rounded once to fp32 and added onto an fp32 episode return -- so on the final_params rows of a fused counter-mode launch, with that launch's
+ * keys and episode_offset = the test episodes it ran before its closing test, `returns` are that launch's final_returns bit for bit.
+ * params [agents, P]: rows in the layout of the fused loops' final_params for the same cfg.  TD3: actor | critic_1 | critic_2,
+ * P = lenv_td3_num_params, only the actor is read.  PPO: action_std [A] | actor.net | critic.net, P = lenv_ppo_num_params.  One shape per
+ * launch: a caller groups the agents of a *_vary population by drawn shape.
+ * Episode e of agent i resets from the counter draw (rng_keys[i], test-reset stream, episode_offset[i] + e) -- episode_offset NULL = 0 -- or,
+ * when reset_states [agents, T, SD] is given, from reset_states[i][e] (the fp64 state words of lenv_cont_env_reset: SD = 17 / 2 / 2).  noise
+ * [agents, T, cap, A] (may be NULL): z of agent step n of episode e is noise[i][e][n][k] and the keys' noise streams are not drawn.
+ * Outputs as lenv_agent_test_population: returns [agents, T] fp64 (the fp32 episode returns), env_steps / agent_steps [agents, T]; the row
+ * arrays -- all five or none -- row_state / row_next_state [agents, T, cap, state_dim], row_action [agents, T, cap, action_dim] fp32,
+ * row_reward / row_done [agents, T, cap], cap = lenv_actor_test_rows_cap(kind, cfg).  Slots at or beyond agent_steps[i][e] are not written.
+ * Of cfg only env_id, state_dim, action_dim, max_steps, test_episodes, same_action_num, hidden, layers, act and -- TD3 -- use_layer_norm,
+ * action_std, max_action are read.  Admitted: what the fused entry of the same kind admits for its actor and its test -- TD3: layers 1..3,
+ * hidden 1..512, test_episodes * state_dim <= 512; PPO: layers 1..2, hidden 1..128, test_episodes 1..64; same_action_num 0..64, act other
+ * than PReLU, (env_id, state_dim, action_dim) one of the three envs; anything else LENV_ERR_UNSUPPORTED.  LENV_ERR_INVALID: agents < 0, a NULL
+ * cfg / params / rng_keys / returns / env_steps / agent_steps, row arrays given in part, max_steps < 1.  agents == 0: LENV_OK after these
+ * checks.  No workspace.
+ */
+enum { LENV_ACTOR_TD3 = 0, LENV_ACTOR_PPO = 1 };
+/* HOST: rows one test episode can produce = ceil(max_steps / max(same_action_num, 1)); negative LENV_ERR_* as the launch would return */
+int64_t lenv_actor_test_rows_cap(int kind, const void *cfg /*HOST: lenv_td3_cfg / lenv_ppo_cfg*/);
+int lenv_actor_test_population(int kind, const void *cfg /*HOST*/, const float *params /*[agents, P]*/,
+                               const uint64_t *rng_keys /*[agents]*/, const int64_t *episode_offset /*[agents] or NULL = 0*/,
+                               const double *reset_states /*[agents, T, SD] or NULL*/, const float *noise /*[agents, T, cap, A] or NULL*/,
+                               int64_t agents, double *returns /*[agents, T]*/, int32_t *env_steps /*[agents, T]*/,
+                               int32_t *agent_steps /*[agents, T]*/, float *row_state /*[agents, T, cap, S]*/,
+                               float *row_action /*[agents, T, cap, A]*/, float *row_next_state, float *row_reward /*[agents, T, cap]*/,
+                               float *row_done, void *stream);
+
 /* HalfCheetah-v3 STAND-IN reset / step for n instances (state [n,17] float64, action [n,6], obs [n,17]); same contract as
  * lenv_real_env_reset / lenv_real_env_step. */
 int lenv_cheetah_standin_reset(const uint64_t *keys, const int64_t *episode, int64_t n, double *state, float *obs,

@@ -10,6 +10,7 @@ CSRC = os.path.join(_HERE, "csrc")
 ACT = {"identity": 0, "relu": 1, "leakyrelu": 2, "tanh": 3, "prelu": 4}
 ENV = {"CartPole-v0": 0, "Acrobot-v1": 1, "HalfCheetah-v3": 2, "MountainCar-v0": 3, "Pendulum-v0": 4, "MountainCarContinuous-v0": 5}
 RNG_COUNTER, RNG_TAPE = 0, 1
+ACTOR_TD3, ACTOR_PPO = 0, 1                      # LENV_ACTOR_*: the `kind` of lenv_actor_test_population (its cfg is a Td3Cfg / PpoCfg)
 VARIANT_NO_WAVECHAIN, VARIANT_GENERIC, VARIANT_TEAM_NARROW, VARIANT_NO_DIRECT = 1, 2, 4, 8     # lenv_ddqn_cfg / lenv_td3_cfg kernel_variant bits (A/B timing, kernel-vs-kernel parity tests)
 TD3_RESUME_WORDS = 32                            # LENV_TD3_RESUME_WORDS: int64 words of a chain's record between two segment launches
 DUELING_RESUME_WORDS = 32                        # LENV_DUELING_RESUME_WORDS: the same for lenv_dueling_se_inner_loop_segment
@@ -237,6 +238,9 @@ SIGNATURES = {
     "lenv_rn_step_population": (C.c_int, [_i32, _i32, _i32, _P(MlpDesc), _i32, _i32, _f64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lenv_agent_test_rows_cap": (_i64, [_P(DdqnCfg)]),
     "lenv_agent_test_population": (C.c_int, [_P(DdqnCfg), _vp, _vp, _vp, _vp, _i64] + [_vp] * 8 + [_vp]),
+    # kind (ACTOR_TD3 / ACTOR_PPO), cfg (a Td3Cfg / PpoCfg by reference), ...
+    "lenv_actor_test_rows_cap": (_i64, [C.c_int, _vp]),
+    "lenv_actor_test_population": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64] + [_vp] * 8 + [_vp]),
     "lenv_td3_rn_workspace_bytes": (C.c_size_t, [_P(Td3Cfg), _i64]),
     "lenv_td3_num_params": (_i64, [_P(Td3Cfg), _P(_i64), _P(_i64)]),
     "lenv_td3_rn_team_size": (C.c_int, [_P(Td3Cfg), _i64]),

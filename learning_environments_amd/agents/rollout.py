@@ -1,4 +1,5 @@
-"""BaseAgent.test as a call of its own (reference agents/base_agent.py:155-227) for DDQN / DuelingDDQN agents that exist as parameter rows.
+"""BaseAgent.test as a call of its own (reference agents/base_agent.py:155-227) for DDQN / DuelingDDQN agents (`test_agents`) and TD3 / PPO
+agents (`test_actor_agents`, lenv_actor_test_population, csrc/actor_test_population.hip) that exist as parameter rows.
 
 The reference's agent.test(env) returns (reward_list, episode_length_list, replay_buffer); in the fused launches a test is only the closing part
 of training and yields final_returns alone.  `test_agents` runs the test of a whole population in one launch of lenv_agent_test_population
@@ -8,20 +9,21 @@ import numpy as np
 import torch
 
 from .. import engine
-from ..config import ddqn_cfg_from_config
+from ..config import ddqn_cfg_from_config, ppo_cfg_from_config, td3_cfg_from_config
 
 
 class ReplayRows(object):
     """The transitions of a rollout in visiting order: what the scripts use of the reference's ReplayBuffer (get_all, merge_buffer, get_size),
-    append-only and without a capacity.  All five fields are CPU float32 tensors; actions / rewards / dones are columns [N,1]."""
+    append-only and without a capacity.  All five fields are CPU float32 tensors; rewards / dones are columns [N,1], actions [N,action_dim]
+    (1, a discrete index, unless stated: the continuous envs' action vectors are up to six wide)."""
     FIELDS = ("states", "actions", "next_states", "rewards", "dones")
 
-    def __init__(self, state_dim, states=None, actions=None, next_states=None, rewards=None, dones=None):
-        self.state_dim = int(state_dim)
+    def __init__(self, state_dim, states=None, actions=None, next_states=None, rewards=None, dones=None, action_dim=1):
+        self.state_dim, self.action_dim = int(state_dim), int(action_dim)
         given = (states, actions, next_states, rewards, dones)
         if any(g is None for g in given) and not all(g is None for g in given):
             raise ValueError("ReplayRows takes all five fields or none")
-        widths = (self.state_dim, 1, self.state_dim, 1, 1)
+        widths = self._widths()
         self._parts = []
         if states is not None:
             part = tuple(torch.as_tensor(np.asarray(g.cpu() if torch.is_tensor(g) else g), dtype=torch.float32).reshape(-1, w) for g, w in zip(given, widths))
@@ -29,10 +31,13 @@ class ReplayRows(object):
                 raise ValueError("ReplayRows: the five fields must have one row count")
             self._parts.append(part)
 
+    def _widths(self):
+        return (self.state_dim, self.action_dim, self.state_dim, 1, 1)
+
     def get_all(self):
-        """(states [N,S], actions [N,1], next_states [N,S], rewards [N,1], dones [N,1]), episode after episode and step after step."""
+        """(states [N,S], actions [N,action_dim], next_states [N,S], rewards [N,1], dones [N,1]), episode after episode and step after step."""
         if not self._parts:
-            return tuple(torch.zeros((0, w), dtype=torch.float32) for w in (self.state_dim, 1, self.state_dim, 1, 1))
+            return tuple(torch.zeros((0, w), dtype=torch.float32) for w in self._widths())
         if len(self._parts) > 1:
             self._parts = [tuple(torch.cat([p[k] for p in self._parts]) for k in range(5))]
         return self._parts[0]
@@ -42,9 +47,10 @@ class ReplayRows(object):
         rows = other.get_all()
         if rows[0].shape[1] != self.state_dim:
             raise ValueError("merge_buffer: state_dim %d next to %d" % (rows[0].shape[1], self.state_dim))
+        if rows[1].shape[1] != self.action_dim:
+            raise ValueError("merge_buffer: action_dim %d next to %d" % (rows[1].shape[1], self.action_dim))
         if rows[0].shape[0]:
-            self._parts.append(tuple(torch.as_tensor(r, dtype=torch.float32).cpu().reshape(-1, w)
-                                     for r, w in zip(rows, (self.state_dim, 1, self.state_dim, 1, 1))))
+            self._parts.append(tuple(torch.as_tensor(r, dtype=torch.float32).cpu().reshape(-1, w) for r, w in zip(rows, self._widths())))
 
     def get_size(self):
         return int(sum(p[0].shape[0] for p in self._parts))
@@ -56,7 +62,8 @@ def rows_of_episodes(state, action, next_state, reward, done, counts):
     """ReplayRows of one agent from padded per-episode arrays [T,cap(,S)] (host) and the rows each episode filled, counts [T]."""
     S = state.shape[-1]
     keep = np.arange(state.shape[1])[None, :] < np.asarray(counts)[:, None]          # [T,cap], row-major = episode after episode
-    return ReplayRows(S, state[keep], action[keep].astype(np.float32), next_state[keep], reward[keep], done[keep])
+    A = action.shape[-1] if action.ndim == 3 else 1                                   # [T,cap,A]: action vectors of a continuous env
+    return ReplayRows(S, state[keep], action[keep].astype(np.float32), next_state[keep], reward[keep], done[keep], action_dim=A)
 
 
 def _device_i64(v, n, dev, name):
@@ -100,3 +107,41 @@ def test_agents(config, params, rng_keys, episode_offset=None, test_episodes=Non
 
 
 test_agents.__test__ = False      # a library function, not a pytest case
+
+
+def test_actor_agents(config, params, rng_keys, episode_offset=None, test_episodes=None, max_steps=None):
+    """test_agents for the continuous-control agents: agent.test(env=real_env) for every row of `params` (fp32 [agents,P], the layout of the
+    fused loops' final_params) on config's real env (the HalfCheetah stand-in, Pendulum-v0, MountainCarContinuous-v0), in one launch of
+    lenv_actor_test_population.  The agent is config['agents']['gtn']['agent_name']: td3, td3_vary with vary_hp off (the agent IS TD3 then),
+    or ppo; anything else -- td3_discrete_vary (a Gumbel-softmax actor), td3_vary with vary_hp on (per-agent shapes: group the agents by
+    drawn shape and call engine.actor_test_population per group), the Q-net agents (test_agents) and the gridworld agents -- raises
+    NotImplementedError naming it.  The test actions carry the noise of the fused loops' closing test, drawn from the counter RNG:
+    (rng_keys[i], the agent's test-noise stream, episode_offset[i] + e, agent step); the resets as in test_agents.
+    Returns, per agent, the reference's triple (reward_list, episode_length_list, replay_buffer); the ReplayRows carry action vectors
+    (action_dim = the env's)."""
+    name = config["agents"]["gtn"]["agent_name"].lower() if "gtn" in config["agents"] else "td3"
+    if name == "td3_vary" and not config["agents"]["td3_vary"]["vary_hp"]:
+        name = "td3"
+    if name == "td3_vary":
+        raise NotImplementedError("test_actor_agents: agent '%s' with vary_hp on draws a shape per agent; group the agents by shape and call "
+                                  "engine.actor_test_population per group" % config["agents"]["gtn"]["agent_name"])
+    if name not in ("td3", "ppo"):
+        raise NotImplementedError("test_actor_agents: agent '%s' (TD3 and PPO actors of one shape only)" % config["agents"].get("gtn", {}).get("agent_name", name))
+    dev = engine.require_device()
+    over = {}
+    if test_episodes is not None:
+        over["test_episodes"] = int(test_episodes)
+    if max_steps is not None:
+        over["max_steps"] = int(max_steps)
+    cfg = (td3_cfg_from_config if name == "td3" else ppo_cfg_from_config)(config, **over)
+    params = torch.as_tensor(params, dtype=torch.float32).to(dev).contiguous()
+    n = params.shape[0]
+    out = engine.actor_test_population(name, cfg, params, _device_i64(rng_keys, n, dev, "rng_keys"), _device_i64(episode_offset, n, dev, "episode_offset"))
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    return [(host["returns"][i].tolist(), host["agent_steps"][i].tolist(),
+             rows_of_episodes(host["row_state"][i], host["row_action"][i], host["row_next_state"][i], host["row_reward"][i], host["row_done"][i],
+                              host["agent_steps"][i]))
+            for i in range(n)]
+
+
+test_actor_agents.__test__ = False

@@ -23,12 +23,12 @@
 #include "lenv_gemm.cuh"
 #include "lenv_dueling_params.cuh"
 #include "lenv_ln.cuh"
+#include "lenv_at_layer.cuh"
 #include "lenv_host.h"
 
 namespace lenv {
 
 constexpr int AT_TB = 16;                      // episodes of one workgroup
-constexpr int AT_EPT = 4;                      // episodes of one forward item
 constexpr int AT_XLD = 8;                      // row stride of the observation rows
 constexpr int AT_MAXS = 6, AT_MAXA = 3;        // the widest observation (Acrobot) and the most actions of the three envs
 constexpr int AT_LNBUF = AT_TB * (D_MAXH | 1); // ln_rows_forward: every row of a block in one chunk
@@ -43,72 +43,6 @@ struct AtArgs {
     double *returns; int32_t *env_steps, *agent_steps;
     float *row_state; int32_t *row_action; float *row_next_state, *row_reward, *row_done;
 };
-
-// y[e][j] = (act)(sum_k x[e][k] * W[j][k] + b[j]) for the episodes e < rows of the block, j < n_out.  ST: W is the staged, transposed copy
-// (element (j, k) at k * n_out + j), else the row-major matrix in global memory.  Groups without a live episode are skipped.  The caller
-// synchronises.
-template <bool ST>
-__device__ __forceinline__ void at_layer(const float *W, const float *b, int n_in, int n_out, const float *x, int ldx, float *y, int ldy, int rows,
-                                         bool activate, int act, float prelu, unsigned alive, int tid)
-{
-    const int groups = (rows + AT_EPT - 1) / AT_EPT;
-    const bool xv4 = (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    const bool wv4 = !ST && (n_in & 3) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0;
-    for (int it = tid; it < groups * n_out; it += DNT) {
-        const int g = it / n_out, j = it - g * n_out, e0 = g * AT_EPT;
-        if (((alive >> e0) & ((1u << AT_EPT) - 1)) == 0) continue;
-        const float *xr[AT_EPT];
-        float z[AT_EPT];
-#pragma unroll
-        for (int u = 0; u < AT_EPT; ++u) { const int e = e0 + u < rows ? e0 + u : rows - 1; xr[u] = x + e * ldx; z[u] = 0.0f; }
-        const float *wj = ST ? W + j : W + (int64_t)j * n_in;
-        int k = 0;
-        for (; k + 4 <= n_in; k += 4) {
-            float w[4];
-            if (ST) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) w[q] = wj[(k + q) * n_out];
-            } else if (wv4) {
-                const float4 t = *reinterpret_cast<const float4 *>(wj + k);
-                w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) w[q] = wj[k + q];
-            }
-#pragma unroll
-            for (int u = 0; u < AT_EPT; ++u) {
-                float xv[4];
-                if (xv4) {
-                    const float4 t = *reinterpret_cast<const float4 *>(xr[u] + k);
-                    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) xv[q] = xr[u][k + q];
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) z[u] = fma32(xv[q], w[q], z[u]);
-            }
-        }
-        for (; k < n_in; ++k) {
-            const float w = ST ? wj[k * n_out] : wj[k];
-#pragma unroll
-            for (int u = 0; u < AT_EPT; ++u) z[u] = fma32(xr[u][k], w, z[u]);
-        }
-        const float bj = b[j];
-#pragma unroll
-        for (int u = 0; u < AT_EPT; ++u) {
-            if (e0 + u >= rows) break;
-            const float v = z[u] + bj;
-            y[(e0 + u) * ldy + j] = activate ? act_fwd(act, prelu, v) : v;
-        }
-    }
-}
-
-// the staged copy of one weight matrix [n_out][n_in]: transposed in place of the row-major one
-__device__ __forceinline__ void at_stage_transposed(float *dst, const float *src, int n_out, int n_in, int tid)
-{
-    for (int i = tid; i < n_out * n_in; i += DNT) { const int j = i / n_in, k = i - j * n_in; dst[k * n_out + j] = src[i]; }
-}
 
 template <bool ST>
 __global__ __launch_bounds__(DNT) void agent_test_population_kernel(const AtArgs a)

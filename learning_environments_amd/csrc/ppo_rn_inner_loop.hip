@@ -27,27 +27,13 @@
 #include "lenv_icm.cuh"
 #include "lenv_rn.cuh"
 #include "lenv_host.h"
+#include "lenv_actor_params.cuh"      // PP_MAXL, PP_MAXW, PP_MAXT, PpoMlp / ppo_mlp
 
 namespace lenv {
 
-constexpr int PP_MAXL = 2;       // hidden layers of actor.net / critic.net
-constexpr int PP_MAXW = 128;     // hidden_size
 constexpr int PP_MAXN = 2048;    // rows of one learn call (the MountainCarContinuous transfer settings need 1999, the HalfCheetah ones 1001)
 constexpr int PP_MAXI = 256;     // rows of one product block
-constexpr int PP_MAXT = 64;      // test episodes
 constexpr int PP_STD = 8;        // arena floats reserved for action_std in front of actor.net (A <= 6; keeps the nets 16-byte aligned)
-
-struct PpoMlp { int in, H, L, out; int oW[PP_MAXL + 1], ob[PP_MAXL + 1]; int P; };
-
-__host__ __device__ inline void ppo_mlp(PpoMlp &m, int in, int H, int L, int out)
-{
-    m.in = in; m.H = H; m.L = L; m.out = out;
-    int o = 0, n_in = in;
-    for (int l = 0; l <= PP_MAXL; ++l) m.oW[l] = m.ob[l] = 0;
-    for (int l = 0; l < L; ++l) { m.oW[l] = o; o += H * n_in; m.ob[l] = o; o += H; n_in = H; }
-    m.oW[L] = o; o += out * H; m.ob[L] = o; o += out;
-    m.P = o;
-}
 
 struct PpoArgs {
     lenv_ppo_cfg cfg;

@@ -20,31 +20,14 @@
 #include "lenv_icm.cuh"
 #include "lenv_wavechain_host.h"
 #include "lenv_host.h"
+#include "lenv_actor_params.cuh"      // T3_MAXL, T3_MAXW, MlpOff / mlp_off
 
 namespace lenv {
 
-constexpr int T3_MAXL = 3;     // hidden layers of actor / critic (TD3_vary draws hidden_layer + 1)
-constexpr int T3_MAXW = 512;   // max hidden_size (outputs wider than 128 run as several 128-column blocks)
 constexpr int T3_MAXB = 768;   // max batch size  (more than 256 rows run as several row blocks; 768 = 3 x the shipped 256)
 constexpr int T3_MAXI = 256;   // rows of one product block
 constexpr int T3_DIRECT_H = 64, T3_DIRECT_B = 256;   // the DIRECT instantiations: one hidden layer of at most 64 units, batch <= 256 (see the kernel)
 // observation / action dims come from the env (ContEnv<ENV> in lenv_device.cuh): the stand-in 17 / 6, Pendulum-v0 3 / 1
-
-struct MlpOff { int in, H, L, out; int oW[T3_MAXL + 1], ob[T3_MAXL + 1]; int P; int ln, oLN; };      // ln: the net's shared LayerNorm (weight | bias at oLN, behind the second Linear)
-
-__host__ __device__ inline void mlp_off(MlpOff &m, int in, int H, int L, int out, bool layer_norm = false)
-{
-    m.in = in; m.H = H; m.L = L; m.out = out;
-    m.ln = layer_norm && L >= 2 ? 1 : 0; m.oLN = 0;        // use_layer_norm (model_utils.py:22-37): nothing to normalise with one hidden layer
-    int o = 0, n_in = in;
-    for (int l = 0; l <= T3_MAXL; ++l) m.oW[l] = m.ob[l] = 0;
-    for (int l = 0; l < L; ++l) {
-        m.oW[l] = o; o += H * n_in; m.ob[l] = o; o += H; n_in = H;
-        if (m.ln && l == 1) { m.oLN = o; o += 2 * H; }
-    }
-    m.oW[L] = o; o += out * H; m.ob[L] = o; o += out;
-    m.P = o;
-}
 
 struct Td3Args {
     lenv_td3_cfg cfg;

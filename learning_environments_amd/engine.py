@@ -232,6 +232,75 @@ def agent_test_population(cfg, params, rng_keys, episode_offset=None, reset_stat
     return out
 
 
+def _actor_kind(kind):
+    k = {"td3": _lib.ACTOR_TD3, "ppo": _lib.ACTOR_PPO}.get(kind.lower(), None) if isinstance(kind, str) else int(kind)
+    if k not in (_lib.ACTOR_TD3, _lib.ACTOR_PPO):
+        raise NotImplementedError("actor_test_population: kind %r (TD3 and PPO actors only)" % (kind,))
+    return k
+
+
+def actor_test_num_params(kind, cfg):
+    """Row width of `params` in actor_test_population: the flat parameter vector of the fused loops' final_params at cfg's shapes -- TD3:
+    actor | critic_1 | critic_2 with each net's shared LayerNorm (lenv_td3_num_params), PPO: action_std | actor.net | critic.net
+    (lenv_ppo_num_params).  Computed from the network fields alone, so cfg's training fields may be anything."""
+    k = _actor_kind(kind)
+    S, A, H, L = cfg.state_dim, cfg.action_dim, cfg.hidden, cfg.layers
+
+    def net(n_in, n_out, ln):
+        return (n_in * H + H) + (L - 1) * (H * H + H) + (2 * H if ln and L >= 2 else 0) + (n_out * H + n_out)
+    if k == _lib.ACTOR_TD3:
+        ln = bool(cfg.use_layer_norm)
+        return net(S, A, ln) + 2 * net(S + A, 1, ln)
+    return A + net(S, A, False) + net(S, 1, False)
+
+
+def actor_test_population(kind, cfg, params, rng_keys, episode_offset=None, reset_states=None, noise=None, want_rows=True):
+    """BaseAgent.test of a population of trained TD3 / PPO agents in one launch (lenv_actor_test_population): kind "td3" (cfg a Td3Cfg) or
+    "ppo" (a PpoCfg), or _lib.ACTOR_*.  Agent i, parameters params[i] (fp32 [agents,P] in the layout of the fused loops' final_params,
+    P = actor_test_num_params(kind, cfg)), runs T = cfg.test_episodes episodes with the test noise of the fused loops' closing test on the
+    real env.  Episode e resets from the counter draw (rng_keys[i], test-reset stream, episode_offset[i] + e) -- episode_offset int64
+    [agents], None = 0 -- or from reset_states[i][e] (fp64 [agents,T,SD], the env's own state words); noise (fp32 [agents,T,cap,A]) replaces
+    the standard-normal draws of the keys' noise streams.  Returns a dict of device tensors: returns fp64 [agents,T], env_steps /
+    agent_steps int32 [agents,T] and, with want_rows, the transitions row_state / row_next_state fp32 [agents,T,cap,S], row_action fp32
+    [agents,T,cap,A], row_reward / row_done fp32 [agents,T,cap]; slots at or beyond agent_steps[i][e] are zero (the kernel does not write
+    them)."""
+    dev = require_device()
+    L = _lib.lib()
+    k = _actor_kind(kind)
+    if not isinstance(cfg, Td3Cfg if k == _lib.ACTOR_TD3 else PpoCfg):
+        raise TypeError("actor_test_population: kind %r takes a %s" % (kind, "Td3Cfg" if k == _lib.ACTOR_TD3 else "PpoCfg"))
+    _chk(params, torch.float32, "params"); _chk(rng_keys, torch.int64, "rng_keys"); _chk(noise, torch.float32, "noise")
+    _chk(episode_offset, torch.int64, "episode_offset"); _chk(reset_states, torch.float64, "reset_states")
+    cap = _count("lenv_actor_test_rows_cap", k, C.byref(cfg))
+    P, T, S, A = actor_test_num_params(k, cfg), cfg.test_episodes, cfg.state_dim, cfg.action_dim
+    SD = REAL_ENV_DIMS[int(cfg.env_id)][1]
+    if params.dim() != 2 or params.shape[1] != P:
+        raise ValueError("params must be [agents,%d]" % P)
+    n = params.shape[0]
+    if tuple(rng_keys.shape) != (n,):
+        raise ValueError("rng_keys must be [agents]")
+    if episode_offset is not None and tuple(episode_offset.shape) != (n,):
+        raise ValueError("episode_offset must be [agents]")
+    if reset_states is not None and tuple(reset_states.shape) != (n, T, SD):
+        raise ValueError("reset_states must be [agents,%d,%d]" % (T, SD))
+    if noise is not None and tuple(noise.shape) != (n, T, cap, A):
+        raise ValueError("noise must be [agents,%d,%d,%d]" % (T, cap, A))
+    out = dict(returns=torch.zeros((n, T), dtype=torch.float64, device=dev), env_steps=torch.zeros((n, T), dtype=torch.int32, device=dev),
+               agent_steps=torch.zeros((n, T), dtype=torch.int32, device=dev))
+    rows = {}
+    if want_rows:
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        rows = dict(row_state=f32(n, T, cap, S), row_action=f32(n, T, cap, A), row_next_state=f32(n, T, cap, S), row_reward=f32(n, T, cap),
+                    row_done=f32(n, T, cap))
+    rc = L.lenv_actor_test_population(k, C.byref(cfg), _ptr(params), _ptr(rng_keys), _ptr(episode_offset), _ptr(reset_states), _ptr(noise), n,
+                                      _ptr(out["returns"]), _ptr(out["env_steps"]), _ptr(out["agent_steps"]), _ptr(rows.get("row_state")),
+                                      _ptr(rows.get("row_action")), _ptr(rows.get("row_next_state")), _ptr(rows.get("row_reward")),
+                                      _ptr(rows.get("row_done")), _stream())
+    _lib.check(rc, "lenv_actor_test_population")
+    out.update(rows)
+    return out
+
+
 def qnet_td_forward(qd, online, target, replay, idx, gamma):
     """online/target [chains,P]; replay [chains,cap,row_stride]; idx int32 [chains,B] -> (q_sa, y) [chains,B]."""
     dev = require_device()

@@ -501,6 +501,84 @@ def run_agent_test(name, cfgd, agents=400, test_episodes=10, runs=7, seed=0):
     return out
 
 
+def run_actor_test(name, cfgd, kind, agents=400, test_episodes=10, runs=7, seed=0):
+    """BaseAgent.test of `agents` freshly initialised TD3 / PPO agents of cfgd's shape, `test_episodes` episodes each: lenv_actor_test_population
+    against the only route there was before it, the fused entry launched with train_episodes = 0 (its closing test alone) -- as the launch
+    picks its kernel and, for TD3, also with kernel_variant GENERIC | NO_WAVECHAIN (the GEMM-queue kernel).  Host clock around a synchronise, a
+    warm-up of each, then `runs` runs in alternation; medians and ranges; the returns must be equal before anything is timed."""
+    from learning_environments_amd import _lib, engine
+    from learning_environments_amd.agents import tasks
+    from learning_environments_amd.agents.nes_common import chain_keys, fresh_agent_init, set_layer_norm_init
+    import numpy as np
+    eng = engine.HipNesEngine()
+    dev = eng.device
+    c = configs.fixed_work(cfgd, 0)
+    c["agents"][kind]["test_episodes"] = test_episodes
+    task = (tasks.Td3RnTask if kind == "td3" else tasks.PpoRnTask)(c, eng)
+    cfg = task.cfg
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    params = fresh_agent_init(task.agent_bounds, agents, g, dev)
+    if kind == "td3":
+        set_layer_norm_init(params, task.ln_slice)
+    else:
+        params[:, :cfg.action_dim] = float(cfg.action_std)
+    keys = torch.from_numpy(chain_keys(seed, 0, np.arange(agents), np.zeros(agents, np.int64)).view(np.int64)).to(dev)
+    loops = {}
+    if kind == "td3":
+        loops["fused_train_episodes_0"] = engine.Td3InnerLoop(cfg, agents, want_episode_stats=True)
+        queue_cfg = _lib.Td3Cfg.from_buffer_copy(cfg)
+        queue_cfg.kernel_variant = _lib.VARIANT_GENERIC | _lib.VARIANT_NO_WAVECHAIN
+        loops["fused_gemm_queue_train_episodes_0"] = engine.Td3InnerLoop(queue_cfg, agents, want_episode_stats=True)
+        if cfg.virtual_env:
+            p_theta = sum(engine.mlp_num_params(d) for d in engine.se_descs(cfg.state_dim, cfg.action_dim, cfg.rn_hidden, cfg.rn_layers, cfg.rn_act))
+        else:
+            p_theta = engine.rn_num_params(cfg.reward_env_type, cfg.state_dim, cfg.info_dim, cfg.rn_hidden, cfg.rn_layers)
+    else:
+        loops["fused_train_episodes_0"] = engine.PpoInnerLoop(cfg, agents, want_episode_stats=True)
+        p_theta = loops["fused_train_episodes_0"].p_theta
+    first = loops["fused_train_episodes_0"]
+    assert first.p_agent == params.shape[1] == engine.actor_test_num_params(kind, cfg)
+    theta, eps = torch.zeros(max(p_theta, 1), device=dev)[:p_theta].contiguous(), torch.zeros((1, p_theta), device=dev)
+    worker, sign = torch.zeros(agents, dtype=torch.int32, device=dev), torch.zeros(agents, device=dev)
+
+    def fused(il):
+        def f():
+            il.run(theta, eps, worker, sign, params, rng_keys=keys)
+            return il.final_returns
+        return f
+
+    def entry():
+        return engine.actor_test_population(kind, cfg, params, keys, want_rows=False)["returns"]
+
+    def entry_rows():
+        return engine.actor_test_population(kind, cfg, params, keys, want_rows=True)["returns"]
+
+    forms = tuple((label, fused(il)) for label, il in loops.items()) + (("actor_test_population", entry), ("actor_test_population_with_rows", entry_rows))
+    ref = forms[0][1]().clone()
+    torch.cuda.synchronize()
+    assert int(first.status.cpu().abs().max()) == 0
+    same = all(bool(torch.equal(ref, fn())) for _, fn in forms[1:])
+    assert same, "lenv_actor_test_population and the fused kernels' closing test differ"
+    times = {label: [] for label, _ in forms}
+    for it in range(runs + 1):
+        for label, fn in forms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if it:
+                times[label].append(time.perf_counter() - t0)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    out = dict(config=name, kind=kind, agents=agents, test_episodes=test_episodes, max_steps=cfg.max_steps, params_per_agent=int(params.shape[1]),
+               runs_each=runs, test_steps=int(first.stats[:, 3].sum()), ms_median={k: 1e3 * v for k, v in med.items()},
+               ms_min={k: 1e3 * min(v) for k, v in times.items()}, ms_max={k: 1e3 * max(v) for k, v in times.items()},
+               ms_samples={k: [round(1e3 * x, 3) for x in v] for k, v in times.items()},
+               fused_over_entry={k: med[k] / med["actor_test_population"] for k in loops}, same_returns=same)
+    print(json.dumps(out))
+    return out
+
+
 def _frac(model):
     def f(cfg, st, dt):
         nbytes, flops = model(cfg, st)
@@ -784,6 +862,13 @@ if __name__ == "__main__":
                        configs.mountaincar_syn_env_ddqn(16))
         run_agent_test("Acrobot-v1, DuelingDDQN 6-128-128 f128, 400 agents x 10 test episodes of 500 steps: generic kernel (train_episodes 0) / agent_test_population",
                        configs.acrobot_syn_env_duelingddqn(16))
+    if "actor_test" in which:
+        # BaseAgent.test of TD3 / PPO agents as a call of its own: 400 fresh agents x 10 test episodes, the new entry against the fused entry
+        # launched with train_episodes = 0; a warm-up, then the medians of 7 alternating runs
+        run_actor_test("Pendulum-v0, PPO 64x2 relu, 400 agents x 10 test episodes of 200 steps: fused entry (train_episodes 0) / actor_test_population",
+                       configs.pendulum_reward_env_ppo(16, test_episodes=10), "ppo")
+        run_actor_test("HalfCheetah-standin, TD3 17-128-128-6 relu (default_config_halfcheetah.yaml), 400 agents x 10 test episodes of 1000 steps: "
+                       "fused entry (train_episodes 0) / GEMM-queue kernel / actor_test_population", configs.halfcheetah_syn_env_td3(16), "td3")
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
