@@ -922,6 +922,70 @@ int lenv_actor_test_population(int kind, const void *cfg /*HOST*/, const float *
                                float *row_action /*[agents, T, cap, A]*/, float *row_next_state, float *row_reward /*[agents, T, cap]*/,
                                float *row_done, void *stream);
 
+/*
+ * BaseAgent.test of a population of trained TD3_discrete_vary agents (Gumbel-softmax actors) in one launch, as a call of its own: the
+ * discrete-action sibling of lenv_actor_test_population.  Agent i runs T = cfg->test_episodes episodes on the real env cfg->env_id
+ * (CartPole-v0, Acrobot-v1, MountainCar-v0) with the operations of the closing test of lenv_td3d_inner_loop / lenv_td3d_rn_inner_loop
+ * (TD3_discrete_vary.select_test_action, agents/TD3_discrete_vary.py:169-171; base_agent.py:155-227 with discretize_action):
+ *   a = gumbel_softmax(actor(s) * max_action + g, temp, gumbel_hard) + z * (float)action_std      the action VECTOR the row keeps,
+ *   the env gets the first maximum of a; n = ((episode_offset[i] + e) * max_steps + step) * A + k,
+ *   g = gumbel(rng_keys[i], Gumbel test stream, n), z = normal(rng_keys[i], TD3 test-noise stream, n),
+ *   temp = np.linspace(gumbel_temp, gumbel_temp / 20, 2000)[min(max(learn_calls[i] - 1, 0), 1999)] in fp32: the fused loop reads the
+ *   temperature before it counts a learn call, so after L calls it holds the value of index L - 1 (with none: index 0).  learn_calls
+ *   [agents] (NULL = 0) is column 2 of a fused launch's stats.
+ * Each step's reward is rounded to fp32 onto an fp32 episode return; the episode ends at the env's done or after max_steps steps
+ * (TimeLimit) -- so on the final_params rows of a fused counter-mode launch, with that launch's keys, learn_calls = its learn steps and
+ * episode_offset = the test episodes it ran before its closing test, `returns` are that launch's final_returns bit for bit.
+ * params [agents, P]: actor | critic_1 | critic_2, P = lenv_td3d_num_params(cfg); only the actor is read.  One shape per launch.
+ * Episode e of agent i resets from the counter draw (rng_keys[i], test-reset stream, episode_offset[i] + e) -- episode_offset NULL = 0 -- or,
+ * when reset_states [agents, T, 4] is given, from reset_states[i][e] (the fp64 state words of lenv_real_env_reset).  gumbel / noise
+ * [agents, T, cap, A] (each may be NULL, each may be given without the other): g / z of step n of episode e is tape[i][e][n][k] and that
+ * stream is not drawn.
+ * Outputs as lenv_actor_test_population: returns [agents, T] fp64 (the fp32 episode returns), env_steps = agent_steps [agents, T] (one env
+ * step per action); the row arrays -- all five or none -- row_state / row_next_state [agents, T, cap, state_dim], row_action
+ * [agents, T, cap, action_dim] fp32, row_reward / row_done [agents, T, cap] (done with TimeLimit included), cap =
+ * lenv_td3d_test_rows_cap(cfg) = max_steps.  Slots at or beyond agent_steps[i][e] are not written.
+ * Of cfg only env_id, state_dim, action_dim, max_steps, test_episodes, hidden, layers, act, use_layer_norm, gumbel_hard, gumbel_temp,
+ * action_std and max_action are read.  Admitted: what lenv_td3d_inner_loop admits for its actor and its test -- layers 1..3, hidden 1..512,
+ * test_episodes 1..64, gumbel_temp > 0, act other than PReLU, (env_id, state_dim, action_dim) one of the three envs; anything else
+ * LENV_ERR_UNSUPPORTED.  LENV_ERR_INVALID: agents < 0, a NULL cfg / params / rng_keys / returns / env_steps / agent_steps, row arrays given
+ * in part, max_steps < 1.  agents == 0: LENV_OK after these checks.  No workspace.
+ */
+/* HOST: rows one test episode can produce = max_steps; negative LENV_ERR_* as the launch would return */
+int64_t lenv_td3d_test_rows_cap(const lenv_td3d_cfg *cfg);
+int lenv_td3d_test_population(const lenv_td3d_cfg *cfg /*HOST*/, const float *params /*[agents, P]*/,
+                              const uint64_t *rng_keys /*[agents]*/, const int64_t *episode_offset /*[agents] or NULL = 0*/,
+                              const int64_t *learn_calls /*[agents] or NULL = 0*/, const double *reset_states /*[agents, T, 4] or NULL*/,
+                              const float *gumbel /*[agents, T, cap, A] or NULL*/, const float *noise /*[agents, T, cap, A] or NULL*/,
+                              int64_t agents, double *returns /*[agents, T]*/, int32_t *env_steps /*[agents, T]*/,
+                              int32_t *agent_steps /*[agents, T]*/, float *row_state /*[agents, T, cap, S]*/,
+                              float *row_action /*[agents, T, cap, A]*/, float *row_next_state, float *row_reward /*[agents, T, cap]*/,
+                              float *row_done, void *stream);
+
+/*
+ * BaseAgent.test of a population of trained tabular agents (QL, SARSA and their count-based variants: one select_test_action) in one
+ * launch, as a call of its own.  Agent i, Q-table q_table[i] (fp64 [n_states * n_actions], the q_table output of lenv_ql_rn_inner_loop /
+ * lenv_ql_se_inner_loop), runs T = cfg->test_episodes greedy episodes on the grid MDP given as the transition tables
+ * next_state / reward / done [n_states, n_actions] (shared by all agents) with the operations of the fused loops' closing test: start at
+ * start_state, the first maximum of the fp32-cast Q row, the action same_action_num times or until done, TimeLimit at max_steps env steps
+ * (envs/env_factory.py:65-89 wraps every gridworld), each agent step's reward the fp64 sum of its repeats rounded once to fp32 and added
+ * onto an fp32 episode return -- so on the q_table rows of a fused launch `returns` are that launch's final_returns bit for bit.
+ * Outputs as lenv_agent_test_population: returns [agents, T] fp64, env_steps / agent_steps [agents, T]; the row arrays -- all five or none --
+ * row_state / row_action / row_next_state (int32 state and action indices), row_reward / row_done (fp32) [agents, T, cap], cap =
+ * lenv_ql_test_rows_cap(cfg); row_done has TimeLimit included.  Slots at or beyond agent_steps[i][e] are not written.
+ * Of cfg only n_states, n_actions, start_state, max_steps, test_episodes and same_action_num are read.  Admitted: n_actions 1..8,
+ * test_episodes 1..128, same_action_num 0..64, start_state inside 0..n_states-1; anything else LENV_ERR_UNSUPPORTED.  LENV_ERR_INVALID:
+ * agents < 0, a NULL cfg / q_table / table / returns / env_steps / agent_steps, row arrays given in part, max_steps < 1.  agents == 0:
+ * LENV_OK after these checks.  One thread per (agent, episode); no workspace.
+ */
+/* HOST: rows one test episode can produce = ceil(max_steps / max(same_action_num, 1)); negative LENV_ERR_* as the launch would return */
+int64_t lenv_ql_test_rows_cap(const lenv_ql_cfg *cfg);
+int lenv_ql_test_population(const lenv_ql_cfg *cfg /*HOST*/, const double *q_table /*[agents, n_states * n_actions]*/,
+                            const int32_t *next_state, const double *reward, const uint8_t *done /*[n_states, n_actions], shared*/,
+                            int64_t agents, double *returns /*[agents, T]*/, int32_t *env_steps /*[agents, T]*/,
+                            int32_t *agent_steps /*[agents, T]*/, int32_t *row_state /*[agents, T, cap]*/, int32_t *row_action,
+                            int32_t *row_next_state, float *row_reward, float *row_done, void *stream);
+
 /* HalfCheetah-v3 STAND-IN reset / step for n instances (state [n,17] float64, action [n,6], obs [n,17]); same contract as
  * lenv_real_env_reset / lenv_real_env_step. */
 int lenv_cheetah_standin_reset(const uint64_t *keys, const int64_t *episode, int64_t n, double *state, float *obs,

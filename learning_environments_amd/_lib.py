@@ -241,6 +241,12 @@ SIGNATURES = {
     # kind (ACTOR_TD3 / ACTOR_PPO), cfg (a Td3Cfg / PpoCfg by reference), ...
     "lenv_actor_test_rows_cap": (_i64, [C.c_int, _vp]),
     "lenv_actor_test_population": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64] + [_vp] * 8 + [_vp]),
+    # cfg, params, rng_keys, episode_offset, learn_calls, reset_states, gumbel, noise, agents, 3 outputs, 5 row arrays, stream
+    "lenv_td3d_test_rows_cap": (_i64, [_P(Td3dCfg)]),
+    "lenv_td3d_test_population": (C.c_int, [_P(Td3dCfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64] + [_vp] * 8 + [_vp]),
+    # cfg, q_table, next_state, reward, done, agents, 3 outputs, 5 row arrays, stream
+    "lenv_ql_test_rows_cap": (_i64, [_P(QlCfg)]),
+    "lenv_ql_test_population": (C.c_int, [_P(QlCfg), _vp, _vp, _vp, _vp, _i64] + [_vp] * 8 + [_vp]),
     "lenv_td3_rn_workspace_bytes": (C.c_size_t, [_P(Td3Cfg), _i64]),
     "lenv_td3_num_params": (_i64, [_P(Td3Cfg), _P(_i64), _P(_i64)]),
     "lenv_td3_rn_team_size": (C.c_int, [_P(Td3Cfg), _i64]),

@@ -1,5 +1,7 @@
-"""BaseAgent.test as a call of its own (reference agents/base_agent.py:155-227) for DDQN / DuelingDDQN agents (`test_agents`) and TD3 / PPO
-agents (`test_actor_agents`, lenv_actor_test_population, csrc/actor_test_population.hip) that exist as parameter rows.
+"""BaseAgent.test as a call of its own (reference agents/base_agent.py:155-227) for DDQN / DuelingDDQN agents (`test_agents`), TD3 / PPO
+agents (`test_actor_agents`, lenv_actor_test_population, csrc/actor_test_population.hip), TD3_discrete_vary agents
+(`test_discrete_actor_agents`, lenv_td3d_test_population, csrc/discrete_actor_test_population.hip) that exist as parameter rows, and the
+tabular agents (`test_tabular_agents`, lenv_ql_test_population, csrc/ql_test_population.hip) that exist as Q-tables.
 
 The reference's agent.test(env) returns (reward_list, episode_length_list, replay_buffer); in the fused launches a test is only the closing part
 of training and yields final_returns alone.  `test_agents` runs the test of a whole population in one launch of lenv_agent_test_population
@@ -9,7 +11,7 @@ import numpy as np
 import torch
 
 from .. import engine
-from ..config import ddqn_cfg_from_config, ppo_cfg_from_config, td3_cfg_from_config
+from ..config import TABULAR_AGENTS, ddqn_cfg_from_config, ppo_cfg_from_config, ql_cfg_from_config, td3_cfg_from_config, td3d_cfg_from_config
 
 
 class ReplayRows(object):
@@ -55,15 +57,25 @@ class ReplayRows(object):
     def get_size(self):
         return int(sum(p[0].shape[0] for p in self._parts))
 
+    def make_one_hot_buffer(self):
+        """ReplayBuffer.make_one_hot_buffer (utils.py:71-72): despite its name, the action VECTORS become their argmax (first maximum), an
+        index column; action_dim is 1 afterwards."""
+        s, a, s2, r, d = self.get_all()
+        self._parts = [(s, torch.argmax(a, dim=1, keepdim=True).to(torch.float32), s2, r, d)] if self._parts else []
+        self.action_dim = 1
+
     __len__ = get_size
 
 
 def rows_of_episodes(state, action, next_state, reward, done, counts):
     """ReplayRows of one agent from padded per-episode arrays [T,cap(,S)] (host) and the rows each episode filled, counts [T]."""
+    if state.ndim == 2:                                                               # [T,cap]: the state indices of a gridworld
+        state, next_state = state[..., None], next_state[..., None]
     S = state.shape[-1]
     keep = np.arange(state.shape[1])[None, :] < np.asarray(counts)[:, None]          # [T,cap], row-major = episode after episode
     A = action.shape[-1] if action.ndim == 3 else 1                                   # [T,cap,A]: action vectors of a continuous env
-    return ReplayRows(S, state[keep], action[keep].astype(np.float32), next_state[keep], reward[keep], done[keep], action_dim=A)
+    return ReplayRows(S, state[keep].astype(np.float32), action[keep].astype(np.float32), next_state[keep].astype(np.float32), reward[keep], done[keep],
+                      action_dim=A)
 
 
 def _device_i64(v, n, dev, name):
@@ -113,8 +125,9 @@ def test_actor_agents(config, params, rng_keys, episode_offset=None, test_episod
     """test_agents for the continuous-control agents: agent.test(env=real_env) for every row of `params` (fp32 [agents,P], the layout of the
     fused loops' final_params) on config's real env (the HalfCheetah stand-in, Pendulum-v0, MountainCarContinuous-v0), in one launch of
     lenv_actor_test_population.  The agent is config['agents']['gtn']['agent_name']: td3, td3_vary with vary_hp off (the agent IS TD3 then),
-    or ppo; anything else -- td3_discrete_vary (a Gumbel-softmax actor), td3_vary with vary_hp on (per-agent shapes: group the agents by
-    drawn shape and call engine.actor_test_population per group), the Q-net agents (test_agents) and the gridworld agents -- raises
+    or ppo; anything else -- td3_discrete_vary (a Gumbel-softmax actor: test_discrete_actor_agents), td3_vary with vary_hp on (per-agent shapes: group the agents by
+    drawn shape and call engine.actor_test_population per group), the Q-net agents (test_agents) and the gridworld agents
+    (test_tabular_agents) -- raises
     NotImplementedError naming it.  The test actions carry the noise of the fused loops' closing test, drawn from the counter RNG:
     (rng_keys[i], the agent's test-noise stream, episode_offset[i] + e, agent step); the resets as in test_agents.
     Returns, per agent, the reference's triple (reward_list, episode_length_list, replay_buffer); the ReplayRows carry action vectors
@@ -145,3 +158,69 @@ def test_actor_agents(config, params, rng_keys, episode_offset=None, test_episod
 
 
 test_actor_agents.__test__ = False
+
+
+def _triples(host):
+    return [(host["returns"][i].tolist(), host["agent_steps"][i].tolist(),
+             rows_of_episodes(host["row_state"][i], host["row_action"][i], host["row_next_state"][i], host["row_reward"][i], host["row_done"][i],
+                              host["agent_steps"][i]))
+            for i in range(host["returns"].shape[0])]
+
+
+def test_discrete_actor_agents(config, params, rng_keys, learn_calls=None, episode_offset=None, test_episodes=None, max_steps=None):
+    """test_actor_agents for TD3_discrete_vary with vary_hp off: agent.test(env=real_env) for every row of `params` (fp32 [agents,P], the
+    layout of the fused loops' final_params) on config's real env (CartPole-v0, Acrobot-v1, MountainCar-v0), in one launch of
+    lenv_td3d_test_population.  learn_calls (one integer or one per agent, None = 0): the learn calls the agent has made -- column 2 of a
+    fused launch's stats -- which set the annealed Gumbel-softmax temperature.  The test actions carry the Gumbel and Gaussian draws of the
+    fused loops' closing test: (rng_keys[i], the stream, episode_offset[i] + e, step); the resets as in test_agents.  With vary_hp on every
+    agent has its own shape: NotImplementedError naming it (group the agents by shape and call engine.td3d_test_population per group).
+    Returns, per agent, the reference's triple (reward_list, episode_length_list, replay_buffer); the ReplayRows carry the action VECTORS
+    (action_dim = the env's action count; make_one_hot_buffer turns them into indices)."""
+    name = config["agents"]["gtn"]["agent_name"].lower() if "gtn" in config["agents"] else "td3_discrete_vary"
+    if name != "td3_discrete_vary":
+        raise NotImplementedError("test_discrete_actor_agents: agent '%s' (TD3_discrete_vary only)" % config["agents"]["gtn"]["agent_name"])
+    if config["agents"]["td3_discrete_vary"]["vary_hp"]:
+        raise NotImplementedError("test_discrete_actor_agents: agent '%s' with vary_hp on draws a shape per agent; group the agents by shape and "
+                                  "call engine.td3d_test_population per group" % config["agents"].get("gtn", {}).get("agent_name", name))
+    dev = engine.require_device()
+    over = {}
+    if test_episodes is not None:
+        over["test_episodes"] = int(test_episodes)
+    if max_steps is not None:
+        over["max_steps"] = int(max_steps)
+    cfg = td3d_cfg_from_config(config, **over)
+    params = torch.as_tensor(params, dtype=torch.float32).to(dev).contiguous()
+    n = params.shape[0]
+    out = engine.td3d_test_population(cfg, params, _device_i64(rng_keys, n, dev, "rng_keys"), _device_i64(episode_offset, n, dev, "episode_offset"),
+                                      _device_i64(learn_calls, n, dev, "learn_calls"))
+    return _triples({k: v.cpu().numpy() for k, v in out.items()})
+
+
+test_discrete_actor_agents.__test__ = False
+
+
+def test_tabular_agents(config, q_tables, tables=None, test_episodes=None, max_steps=None):
+    """agent.test(env=real_env) for the tabular agents (config['agents']['gtn']['agent_name']: QL / QL_cb / SARSA / SARSA_cb -- they share
+    select_test_action), every row of q_tables (fp64 [agents, n_states * n_actions], the q_table of the fused tabular launches) on the
+    gridworld `tables` (GridEnv.tables: n_states, n_actions, start_state, next_state / reward / done; None: the gridworld config names), in
+    one launch of lenv_ql_test_population.  Returns, per agent, the reference's triple (reward_list, episode_length_list, replay_buffer) with
+    ReplayRows(state_dim=1): states, actions and next states are indices."""
+    name = config["agents"]["gtn"]["agent_name"].lower() if "gtn" in config["agents"] else "ql"
+    if name not in TABULAR_AGENTS:
+        raise NotImplementedError("test_tabular_agents: agent '%s' (the tabular agents: %s)" % (config["agents"]["gtn"]["agent_name"], ", ".join(TABULAR_AGENTS)))
+    if tables is None:
+        from ..envs.env_factory import EnvFactory
+        tables = EnvFactory(config=config).generate_real_env().env.tables
+    over = {}
+    if test_episodes is not None:
+        over["test_episodes"] = int(test_episodes)
+    if max_steps is not None:
+        over["max_steps"] = int(max_steps)
+    cfg = ql_cfg_from_config(config, tables, **over)
+    dev = engine.require_device()
+    q = torch.as_tensor(q_tables, dtype=torch.float64).to(dev).contiguous()
+    out = engine.ql_test_population(cfg, q.reshape(q.shape[0], -1), tables)
+    return _triples({k: v.cpu().numpy() for k, v in out.items()})
+
+
+test_tabular_agents.__test__ = False

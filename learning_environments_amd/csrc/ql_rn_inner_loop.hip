@@ -13,6 +13,7 @@
 // strictly sequential scalar walk (<= train_episodes*max_steps steps) executed by lane 0 on the LDS-resident fp64 Q-table.
 // Integer/fp64 work is exact by construction; phi uses the canonical sequential-fmaf order of oracle/lenv_oracle.h.
 #include "lenv_device.cuh"
+#include "lenv_ql_policy.cuh"
 #include "lenv_host.h"
 
 namespace lenv {
@@ -29,14 +30,6 @@ struct QlArgs {
     int64_t P;
     int draw_cap;          // exploration draws precomputed per episode (a speed-up: draws past it are computed inline); clamped to what fits the LDS
 };
-
-__device__ __forceinline__ int ql_argmax_f32(const double *row, int n)
-{
-    int best = 0;
-    float bv = (float)row[0];
-    for (int i = 1; i < n; ++i) { const float v = (float)row[i]; if (v > bv) { bv = v; best = i; } }
-    return best;
-}
 
 // phi(s) = reward_net(one_hot(s)) for all states with W = theta + sign*eps[worker] (reward_env.py:74-76,
 // GTN_worker.py:165-175), then RewardEnv._calc_reward for every (s,a) (reward_env.py:81-110) in fp32, left to right.

@@ -301,6 +301,101 @@ def actor_test_population(kind, cfg, params, rng_keys, episode_offset=None, rese
     return out
 
 
+def td3d_test_num_params(cfg):
+    """Row width of `params` in td3d_test_population: actor | critic_1 | critic_2 with each net's shared LayerNorm (lenv_td3d_num_params).
+    Computed from the network fields alone, so cfg's training fields may be anything."""
+    S, A, H, L = cfg.state_dim, cfg.action_dim, cfg.hidden, cfg.layers
+
+    def net(n_in, n_out):
+        return (n_in * H + H) + (L - 1) * (H * H + H) + (2 * H if cfg.use_layer_norm and L >= 2 else 0) + (n_out * H + n_out)
+    return net(S, A) + 2 * net(S + A, 1)
+
+
+def td3d_test_population(cfg, params, rng_keys, episode_offset=None, learn_calls=None, reset_states=None, gumbel=None, noise=None, want_rows=True):
+    """BaseAgent.test of a population of trained TD3_discrete_vary agents in one launch (lenv_td3d_test_population): agent i, parameters
+    params[i] (fp32 [agents,P] in the layout of the fused loops' final_params, P = td3d_test_num_params(cfg)), runs T = cfg.test_episodes
+    episodes on the real env with the Gumbel-softmax head and the test noise of the fused loops' closing test, at the temperature the
+    fused loop holds after learn_calls[i] learn calls (int64 [agents], None = 0: column 2 of a fused launch's stats).  Episode e resets from
+    the counter draw (rng_keys[i], test-reset stream, episode_offset[i] + e) -- episode_offset int64 [agents], None = 0 -- or from
+    reset_states[i][e] (fp64 [agents,T,4]); gumbel / noise (fp32 [agents,T,cap,A], each on its own) replace the draws of the keys' Gumbel /
+    noise streams.  Returns a dict of device tensors: returns fp64 [agents,T], env_steps / agent_steps int32 [agents,T] and, with
+    want_rows, the transitions row_state / row_next_state fp32 [agents,T,cap,S], row_action fp32 [agents,T,cap,A] (the action VECTORS; the
+    env got their argmax), row_reward / row_done fp32 [agents,T,cap]; slots at or beyond agent_steps[i][e] are zero (the kernel does not
+    write them)."""
+    dev = require_device()
+    L = _lib.lib()
+    if not isinstance(cfg, Td3dCfg):
+        raise TypeError("td3d_test_population takes a Td3dCfg")
+    _chk(params, torch.float32, "params"); _chk(rng_keys, torch.int64, "rng_keys"); _chk(gumbel, torch.float32, "gumbel"); _chk(noise, torch.float32, "noise")
+    _chk(episode_offset, torch.int64, "episode_offset"); _chk(learn_calls, torch.int64, "learn_calls"); _chk(reset_states, torch.float64, "reset_states")
+    cap = _count("lenv_td3d_test_rows_cap", C.byref(cfg))
+    P, T, S, A = td3d_test_num_params(cfg), cfg.test_episodes, cfg.state_dim, cfg.action_dim
+    if params.dim() != 2 or params.shape[1] != P:
+        raise ValueError("params must be [agents,%d]" % P)
+    n = params.shape[0]
+    if tuple(rng_keys.shape) != (n,):
+        raise ValueError("rng_keys must be [agents]")
+    for name, v in (("episode_offset", episode_offset), ("learn_calls", learn_calls)):
+        if v is not None and tuple(v.shape) != (n,):
+            raise ValueError("%s must be [agents]" % name)
+    if reset_states is not None and tuple(reset_states.shape) != (n, T, 4):
+        raise ValueError("reset_states must be [agents,%d,4]" % T)
+    for name, v in (("gumbel", gumbel), ("noise", noise)):
+        if v is not None and tuple(v.shape) != (n, T, cap, A):
+            raise ValueError("%s must be [agents,%d,%d,%d]" % (name, T, cap, A))
+    out = dict(returns=torch.zeros((n, T), dtype=torch.float64, device=dev), env_steps=torch.zeros((n, T), dtype=torch.int32, device=dev),
+               agent_steps=torch.zeros((n, T), dtype=torch.int32, device=dev))
+    rows = {}
+    if want_rows:
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        rows = dict(row_state=f32(n, T, cap, S), row_action=f32(n, T, cap, A), row_next_state=f32(n, T, cap, S), row_reward=f32(n, T, cap),
+                    row_done=f32(n, T, cap))
+    rc = L.lenv_td3d_test_population(C.byref(cfg), _ptr(params), _ptr(rng_keys), _ptr(episode_offset), _ptr(learn_calls), _ptr(reset_states),
+                                     _ptr(gumbel), _ptr(noise), n, _ptr(out["returns"]), _ptr(out["env_steps"]), _ptr(out["agent_steps"]),
+                                     _ptr(rows.get("row_state")), _ptr(rows.get("row_action")), _ptr(rows.get("row_next_state")),
+                                     _ptr(rows.get("row_reward")), _ptr(rows.get("row_done")), _stream())
+    _lib.check(rc, "lenv_td3d_test_population")
+    out.update(rows)
+    return out
+
+
+def ql_test_population(cfg, q_table, tables, want_rows=True):
+    """BaseAgent.test of a population of trained tabular agents (QL / SARSA and their count-based variants) in one launch
+    (lenv_ql_test_population): agent i, Q-table q_table[i] (fp64 [agents, n_states * n_actions], the q_table of the fused tabular launches),
+    runs T = cfg.test_episodes greedy episodes on the grid MDP `tables` (a dict next_state / reward / done [n_states, n_actions] of numpy
+    arrays, as the fused loops take it, or of device tensors int32 / float64 / uint8).  Returns a dict of device tensors: returns fp64
+    [agents,T], env_steps / agent_steps int32 [agents,T] and, with want_rows, row_state / row_action / row_next_state int32, row_reward /
+    row_done fp32 [agents,T,cap]; slots at or beyond agent_steps[i][e] are zero (the kernel does not write them)."""
+    dev = require_device()
+    L = _lib.lib()
+    _chk(q_table, torch.float64, "q_table")
+    cap = _count("lenv_ql_test_rows_cap", C.byref(cfg))
+    N, A, T = cfg.n_states, cfg.n_actions, cfg.test_episodes
+    if q_table.dim() != 2 or q_table.shape[1] != N * A:
+        raise ValueError("q_table must be [agents,%d]" % (N * A))
+    tabs = []
+    for name, dt, np_dt in (("next_state", torch.int32, "int32"), ("reward", torch.float64, "float64"), ("done", torch.uint8, "uint8")):
+        t = tables[name]
+        t = t.to(device=dev, dtype=dt) if torch.is_tensor(t) else torch.from_numpy(t.astype(np_dt)).to(dev)
+        if t.numel() != N * A:
+            raise ValueError("tables[%r] must be [%d,%d]" % (name, N, A))
+        tabs.append(t.contiguous())
+    n = q_table.shape[0]
+    out = dict(returns=torch.zeros((n, T), dtype=torch.float64, device=dev), env_steps=torch.zeros((n, T), dtype=torch.int32, device=dev),
+               agent_steps=torch.zeros((n, T), dtype=torch.int32, device=dev))
+    rows = {}
+    if want_rows:
+        z = lambda dt: torch.zeros((n, T, cap), dtype=dt, device=dev)
+        rows = dict(row_state=z(torch.int32), row_action=z(torch.int32), row_next_state=z(torch.int32), row_reward=z(torch.float32),
+                    row_done=z(torch.float32))
+    rc = L.lenv_ql_test_population(C.byref(cfg), _ptr(q_table), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), n, _ptr(out["returns"]),
+                                   _ptr(out["env_steps"]), _ptr(out["agent_steps"]), _ptr(rows.get("row_state")), _ptr(rows.get("row_action")),
+                                   _ptr(rows.get("row_next_state")), _ptr(rows.get("row_reward")), _ptr(rows.get("row_done")), _stream())
+    _lib.check(rc, "lenv_ql_test_population")
+    out.update(rows)
+    return out
+
+
 def qnet_td_forward(qd, online, target, replay, idx, gamma):
     """online/target [chains,P]; replay [chains,cap,row_stride]; idx int32 [chains,B] -> (q_sa, y) [chains,B]."""
     dev = require_device()

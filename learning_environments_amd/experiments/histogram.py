@@ -8,7 +8,8 @@ which on the real env when they are tested, and what does the synthetic env answ
 
 The scripts' loop -- agent.train(env=virtual_env), agent.test(env=real_env), merge both replay buffers -- runs here as two launches for all
 agents: the fused inner loop with test_mode 1 (train without a test env) and a step trace, then agents/rollout.test_agents on the trained
-parameter rows.  The first user of BaseAgent.test's third return value."""
+parameter rows -- for the scripts' third agent, td3_discrete_vary, rollout.test_discrete_actor_agents, whose buffers hold action vectors and
+go through make_one_hot_buffer before they are merged, as in the scripts.  The first user of BaseAgent.test's third return value."""
 import copy
 
 import numpy as np
@@ -16,11 +17,11 @@ import torch
 
 from ..agents import tasks
 from ..agents.nes_common import chain_keys, fresh_agent_init
-from ..agents.rollout import ReplayRows, test_agents
+from ..agents.rollout import ReplayRows, test_agents, test_discrete_actor_agents
 from ..engine import HipNesEngine
 from . import syn_env_evaluate
 
-AGENTS = ("ddqn", "duelingddqn")      # td3_discrete_vary, the scripts' third choice, draws noise in its test actions: not built
+AGENTS = ("ddqn", "duelingddqn", "td3_discrete_vary")
 
 
 def load_envs_and_config(dir, file_name):
@@ -70,15 +71,21 @@ def collect(virtual_env, real_env, config, agent_name, agents_num=10, seed=0):
     n = int(agents_num)
     task = tasks.select_task(cfg_dict, engine, virtual_env, test_mode=1)
     cfg = task.cfg
-    k_rep = max(1, cfg.same_action_num)
+    discrete_actor = key == "td3_discrete_vary"
+    if discrete_actor and task.vary:
+        raise NotImplementedError("histogram.collect: agent '%s' with vary_hp on draws a shape per agent" % agent_name)
+    k_rep = 1 if discrete_actor else max(1, cfg.same_action_num)
     trace_cap = max(1, cfg.train_episodes * ((cfg.max_steps + k_rep - 1) // k_rep))         # every agent step of the longest possible run
-    inner = engine.make_inner(cfg, n, want_episode_stats=True, want_final_online=True, trace_cap=trace_cap)
+    if discrete_actor:
+        inner = engine.make_inner_td3d(cfg, n, want_episode_stats=True, want_final_params=True, trace_cap=trace_cap)
+    else:
+        inner = engine.make_inner(cfg, n, want_episode_stats=True, want_final_online=True, trace_cap=trace_cap)
     keys = chain_keys(int(seed), 0, np.arange(n), np.zeros(n, np.int64))
     keys_t = torch.from_numpy(keys.view(np.int64)).to(dev)
     theta = virtual_env.env.flat_params()
     g = torch.Generator(device=dev)
     g.manual_seed(int(seed))
-    agent_init = fresh_agent_init(task.agent_bounds, n, g, dev)
+    agent_init = None if discrete_actor else fresh_agent_init(task.agent_bounds, n, g, dev)     # TD3_discrete_vary: drawn from the keys in scores()
     task.scores(inner, theta, torch.zeros((1, theta.numel()), dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
                 torch.zeros(n, dtype=torch.float32, device=dev), keys_t, agent_init)
     engine.check_status(inner)
@@ -88,18 +95,36 @@ def collect(virtual_env, real_env, config, agent_name, agents_num=10, seed=0):
     tr = {k: v.cpu().numpy() for k, v in inner.trace.items()}
     S = cfg.state_dim
     train_all, test_all = ReplayRows(S), ReplayRows(S)
+    episode_len = inner.episode_len.cpu().numpy() if discrete_actor else None
+    episodes_run = inner.stats[:, 0].cpu().numpy()
     for i in range(n):
         m = int(train_steps[i])
-        train_all.merge_buffer(ReplayRows(S, tr["state"][i, :m], (tr["action"][i, :m] & 0xffff).astype(np.float32), tr["next_state"][i, :m],
-                                          tr["reward_done"][i, :m, 0], tr["reward_done"][i, :m, 1]))
+        if discrete_actor:
+            # the trace holds the action vector, the state pair and the reward; an episode's last step is the done one unless the episode
+            # ran into max_steps on the VirtualEnv, which knows no TimeLimit (base_agent.py:104-131)
+            lens = episode_len[i, :int(episodes_run[i])]
+            ends = np.cumsum(lens) - 1
+            done = np.zeros(m, np.float32)
+            done[ends[lens < cfg.max_steps]] = 1.0
+            rows = ReplayRows(S, tr["state"][i, :m], tr["action"][i, :m], tr["next_state"][i, :m], tr["reward"][i, :m], done, action_dim=cfg.action_dim)
+            rows.make_one_hot_buffer()
+            train_all.merge_buffer(rows)
+        else:
+            train_all.merge_buffer(ReplayRows(S, tr["state"][i, :m], (tr["action"][i, :m] & 0xffff).astype(np.float32), tr["next_state"][i, :m],
+                                              tr["reward_done"][i, :m, 0], tr["reward_done"][i, :m, 1]))
 
     # agent.test(env=real_env): test_mode 1 ran no test before the launch's closing one, so these are its episodes
-    triples = test_agents(cfg_dict, inner.final_online, keys_t)
+    if discrete_actor:
+        triples = test_discrete_actor_agents(cfg_dict, inner.final_params, keys_t, learn_calls=inner.stats[:, 2])
+    else:
+        triples = test_agents(cfg_dict, inner.final_online, keys_t)
     finals = inner.final_returns.cpu().numpy()
     rewards = []
     for i, (reward_list, _, rows) in enumerate(triples):
         assert reward_list == finals[i].tolist(), "agent %d: test returns %s next to the launch's final_returns %s" % (i, reward_list, finals[i].tolist())
         rewards.append(float(np.mean(reward_list)))
+        if discrete_actor:
+            rows.make_one_hot_buffer()
         test_all.merge_buffer(rows)
     virtual_env.set_agent_params(same_action_num=k_rep, gamma=float(cfg.gamma))
     collect.last = dict(inner=inner, keys=keys_t, triples=triples, cfg=cfg, config=cfg_dict)

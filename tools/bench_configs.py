@@ -579,6 +579,113 @@ def run_actor_test(name, cfgd, kind, agents=400, test_episodes=10, runs=7, seed=
     return out
 
 
+def _time_forms(forms, runs):
+    """a warm-up of each form, then `runs` runs in alternation, host clock around a synchronise: (medians, all samples) in seconds"""
+    times = {label: [] for label, _ in forms}
+    for it in range(runs + 1):
+        for label, fn in forms:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if it:
+                times[label].append(time.perf_counter() - t0)
+    return {k: sorted(v)[len(v) // 2] for k, v in times.items()}, times
+
+
+def run_discrete_actor_test(name, cfgd, agents=400, test_episodes=10, runs=7, seed=0):
+    """BaseAgent.test of `agents` freshly initialised TD3_discrete_vary agents of cfgd's shape, `test_episodes` episodes each:
+    lenv_td3d_test_population against the only route there was before it, lenv_td3d_inner_loop launched with train_episodes = 0 (its closing
+    test alone, at the start temperature, behind a full training arena per chain).  Host clock around a synchronise, a warm-up of each, then
+    `runs` runs in alternation; medians and ranges; the returns must be equal before anything is timed."""
+    from learning_environments_amd import engine
+    from learning_environments_amd.agents import tasks
+    from learning_environments_amd.agents.nes_common import chain_keys
+    import numpy as np
+    eng = engine.HipNesEngine()
+    dev = eng.device
+    c = configs.fixed_work(cfgd, 0)
+    c["agents"]["td3_discrete_vary"]["test_episodes"] = test_episodes
+    task = tasks.Td3DiscreteTask(c, eng)
+    cfg = task.cfg
+    keys = torch.from_numpy(chain_keys(seed, 0, np.arange(agents), np.zeros(agents, np.int64)).view(np.int64)).to(dev)
+    il = engine.Td3DiscreteInnerLoop(cfg, agents, want_episode_stats=True, want_final_params=True)
+    params = il.draw_agent_init(keys).clone()
+    assert il.p_agent == params.shape[1] == engine.td3d_test_num_params(cfg)
+    theta, eps = torch.zeros(il.p_theta, device=dev), torch.zeros((1, il.p_theta), device=dev)
+    worker, sign = torch.zeros(agents, dtype=torch.int32, device=dev), torch.zeros(agents, device=dev)
+
+    def fused():
+        il.run(theta, eps, worker, sign, params, rng_keys=keys)
+        return il.final_returns
+
+    def entry():
+        return engine.td3d_test_population(cfg, params, keys, want_rows=False)["returns"]
+
+    def entry_rows():
+        return engine.td3d_test_population(cfg, params, keys, want_rows=True)["returns"]
+
+    forms = (("fused_train_episodes_0", fused), ("td3d_test_population", entry), ("td3d_test_population_with_rows", entry_rows))
+    ref = fused().clone()
+    torch.cuda.synchronize()
+    assert int(il.status.cpu().abs().max()) == 0
+    same = all(bool(torch.equal(ref, fn())) for _, fn in forms[1:])
+    assert same, "lenv_td3d_test_population and the fused kernel's closing test differ"
+    med, times = _time_forms(forms, runs)
+    out = dict(config=name, agents=agents, test_episodes=test_episodes, max_steps=cfg.max_steps, params_per_agent=int(params.shape[1]),
+               workspace_mib_fused=il.ws_bytes / 2 ** 20, runs_each=runs, test_steps=int(il.stats[:, 3].sum()), ms_median={k: 1e3 * v for k, v in med.items()},
+               ms_min={k: 1e3 * min(v) for k, v in times.items()}, ms_max={k: 1e3 * max(v) for k, v in times.items()},
+               ms_samples={k: [round(1e3 * x, 3) for x in v] for k, v in times.items()},
+               fused_over_entry=med["fused_train_episodes_0"] / med["td3d_test_population"], same_returns=same)
+    print(json.dumps(out))
+    return out
+
+
+def run_ql_test(name, agents=400, test_episodes=10, runs=7, seed=0):
+    """BaseAgent.test of `agents` Cliff Q-tables: lenv_ql_test_population against lenv_ql_rn_inner_loop launched with train_episodes = 0 (all-zero
+    tables: the fused loop cannot be handed a trained one) and, for the entry alone, on random tables.  Not a throughput item -- a greedy walk
+    on a deterministic grid is serial and short -- so both sides are a launch and a few hundred dependent loads."""
+    from learning_environments_amd import engine
+    from learning_environments_amd.agents.nes_common import chain_keys
+    from learning_environments_amd.config import ql_cfg_from_config
+    from learning_environments_amd.envs.gridworld import transition_tables
+    import numpy as np
+    dev = engine.require_device()
+    c = configs.fixed_work(configs.cliff_reward_env_ql(16), 0)
+    c["agents"]["ql"]["test_episodes"] = test_episodes
+    tables = transition_tables("Cliff")
+    cfg = ql_cfg_from_config(c, tables)
+    il = engine.QlInnerLoop(cfg, agents, tables)
+    keys = torch.from_numpy(chain_keys(seed, 0, np.arange(agents), np.zeros(agents, np.int64)).view(np.int64)).to(dev)
+    theta, eps = torch.zeros(il.p_theta, device=dev), torch.zeros((1, il.p_theta), device=dev)
+    worker, sign = torch.zeros(agents, dtype=torch.int32, device=dev), torch.zeros(agents, device=dev)
+    dtab = dict(next_state=il.next_state, reward=il.reward, done=il.done)
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    q_random = torch.randn((agents, cfg.n_states * cfg.n_actions), generator=g, device=dev, dtype=torch.float64)
+
+    def fused():
+        il.run(theta, eps, worker, sign, rng_keys=keys)
+        return il.final_returns
+
+    forms = (("fused_train_episodes_0", fused),
+             ("ql_test_population", lambda: engine.ql_test_population(cfg, il.q_table, dtab, want_rows=False)["returns"]),
+             ("ql_test_population_with_rows", lambda: engine.ql_test_population(cfg, il.q_table, dtab, want_rows=True)["returns"]),
+             ("ql_test_population_random_tables", lambda: engine.ql_test_population(cfg, q_random, dtab, want_rows=False)["returns"]))
+    ref = fused().clone()
+    torch.cuda.synchronize()
+    assert int(il.status.cpu().abs().max()) == 0
+    same = all(bool(torch.equal(ref, fn())) for _, fn in forms[1:3])
+    assert same, "lenv_ql_test_population and the fused kernel's closing test differ"
+    med, times = _time_forms(forms, runs)
+    out = dict(config=name, agents=agents, test_episodes=test_episodes, max_steps=cfg.max_steps, runs_each=runs, test_steps=int(il.stats[:, 3].sum()),
+               ms_median={k: 1e3 * v for k, v in med.items()}, ms_min={k: 1e3 * min(v) for k, v in times.items()},
+               ms_max={k: 1e3 * max(v) for k, v in times.items()}, ms_samples={k: [round(1e3 * x, 3) for x in v] for k, v in times.items()},
+               fused_over_entry=med["fused_train_episodes_0"] / med["ql_test_population"], same_returns=same)
+    print(json.dumps(out))
+    return out
+
+
 def _frac(model):
     def f(cfg, st, dt):
         nbytes, flops = model(cfg, st)
@@ -869,6 +976,16 @@ if __name__ == "__main__":
                        configs.pendulum_reward_env_ppo(16, test_episodes=10), "ppo")
         run_actor_test("HalfCheetah-standin, TD3 17-128-128-6 relu (default_config_halfcheetah.yaml), 400 agents x 10 test episodes of 1000 steps: "
                        "fused entry (train_episodes 0) / GEMM-queue kernel / actor_test_population", configs.halfcheetah_syn_env_td3(16), "td3")
+    if "discrete_actor_test" in which:
+        # BaseAgent.test of TD3_discrete_vary agents as a call of its own: 400 fresh agents x 10 test episodes at the histogram scripts' shape
+        # (td3_discrete_vary_layer_norm_2: 4-128-128-2 tanh with LayerNorm, soft head, temperature 1), the new entry against lenv_td3d_inner_loop
+        # launched with train_episodes = 0; a warm-up, then the medians of 7 alternating runs
+        run_discrete_actor_test("CartPole-v0, TD3_discrete_vary 4-128-128-2 tanh LayerNorm, 400 agents x 10 test episodes of up to 200 steps: "
+                                "fused entry (train_episodes 0) / td3d_test_population",
+                                configs.cartpole_syn_env_td3_discrete(16, hidden_size=128, hidden_layer=2, batch_size=128, use_layer_norm=True, gumbel_softmax_temp=1.0,
+                                                                      gumbel_softmax_hard=False, action_std=0.1, policy_delay=2, init_episodes=10))
+    if "ql_test" in which:
+        run_ql_test("Cliff, 400 Q-tables x 10 test episodes of up to 50 steps: lenv_ql_rn_inner_loop (train_episodes 0) / ql_test_population")
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
