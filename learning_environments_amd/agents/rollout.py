@@ -94,6 +94,20 @@ def _device_i64(v, n, dev, name):
     return t.contiguous()
 
 
+def _test_overrides(test_episodes, max_steps):
+    """the cfg_from_config overrides of the test_* functions: what is None keeps the config's value"""
+    return {k: int(v) for k, v in (("test_episodes", test_episodes), ("max_steps", max_steps)) if v is not None}
+
+
+def _triples(out):
+    """the reference's (reward_list, episode_length_list, replay_buffer) per agent from a *_test_population result"""
+    host = {k: v.cpu().numpy() for k, v in out.items()}
+    return [(host["returns"][i].tolist(), host["agent_steps"][i].tolist(),
+             rows_of_episodes(host["row_state"][i], host["row_action"][i], host["row_next_state"][i], host["row_reward"][i], host["row_done"][i],
+                              host["agent_steps"][i]))
+            for i in range(host["returns"].shape[0])]
+
+
 def test_agents(config, params, rng_keys, episode_offset=None, test_episodes=None, max_steps=None):
     """agent.test(env=real_env) for every row of `params` (fp32 [agents,P], the layout of the fused loops' final_online for the agent
     `config` selects: config['agents']['gtn']['agent_name'], default ddqn) on config's real env, in one launch.  rng_keys [agents] (uint64
@@ -102,20 +116,12 @@ def test_agents(config, params, rng_keys, episode_offset=None, test_episodes=Non
     Returns, per agent, the reference's triple (reward_list, episode_length_list, replay_buffer): the T episode returns, the T episode
     lengths counted in agent steps (BaseAgent.test adds 1 per action, base_agent.py:213), and the visited transitions as ReplayRows."""
     dev = engine.require_device()
-    over = {}
-    if test_episodes is not None:
-        over["test_episodes"] = int(test_episodes)
-    if max_steps is not None:
-        over["max_steps"] = int(max_steps)
+    over = _test_overrides(test_episodes, max_steps)
     cfg = ddqn_cfg_from_config(config, **over)
     params = torch.as_tensor(params, dtype=torch.float32).to(dev).contiguous()
     n = params.shape[0]
     out = engine.agent_test_population(cfg, params, _device_i64(rng_keys, n, dev, "rng_keys"), _device_i64(episode_offset, n, dev, "episode_offset"))
-    host = {k: v.cpu().numpy() for k, v in out.items()}
-    return [(host["returns"][i].tolist(), host["agent_steps"][i].tolist(),
-             rows_of_episodes(host["row_state"][i], host["row_action"][i], host["row_next_state"][i], host["row_reward"][i], host["row_done"][i],
-                              host["agent_steps"][i]))
-            for i in range(n)]
+    return _triples(out)
 
 
 test_agents.__test__ = False      # a library function, not a pytest case
@@ -141,30 +147,15 @@ def test_actor_agents(config, params, rng_keys, episode_offset=None, test_episod
     if name not in ("td3", "ppo"):
         raise NotImplementedError("test_actor_agents: agent '%s' (TD3 and PPO actors of one shape only)" % config["agents"].get("gtn", {}).get("agent_name", name))
     dev = engine.require_device()
-    over = {}
-    if test_episodes is not None:
-        over["test_episodes"] = int(test_episodes)
-    if max_steps is not None:
-        over["max_steps"] = int(max_steps)
+    over = _test_overrides(test_episodes, max_steps)
     cfg = (td3_cfg_from_config if name == "td3" else ppo_cfg_from_config)(config, **over)
     params = torch.as_tensor(params, dtype=torch.float32).to(dev).contiguous()
     n = params.shape[0]
     out = engine.actor_test_population(name, cfg, params, _device_i64(rng_keys, n, dev, "rng_keys"), _device_i64(episode_offset, n, dev, "episode_offset"))
-    host = {k: v.cpu().numpy() for k, v in out.items()}
-    return [(host["returns"][i].tolist(), host["agent_steps"][i].tolist(),
-             rows_of_episodes(host["row_state"][i], host["row_action"][i], host["row_next_state"][i], host["row_reward"][i], host["row_done"][i],
-                              host["agent_steps"][i]))
-            for i in range(n)]
+    return _triples(out)
 
 
 test_actor_agents.__test__ = False
-
-
-def _triples(host):
-    return [(host["returns"][i].tolist(), host["agent_steps"][i].tolist(),
-             rows_of_episodes(host["row_state"][i], host["row_action"][i], host["row_next_state"][i], host["row_reward"][i], host["row_done"][i],
-                              host["agent_steps"][i]))
-            for i in range(host["returns"].shape[0])]
 
 
 def test_discrete_actor_agents(config, params, rng_keys, learn_calls=None, episode_offset=None, test_episodes=None, max_steps=None):
@@ -183,17 +174,13 @@ def test_discrete_actor_agents(config, params, rng_keys, learn_calls=None, episo
         raise NotImplementedError("test_discrete_actor_agents: agent '%s' with vary_hp on draws a shape per agent; group the agents by shape and "
                                   "call engine.td3d_test_population per group" % config["agents"].get("gtn", {}).get("agent_name", name))
     dev = engine.require_device()
-    over = {}
-    if test_episodes is not None:
-        over["test_episodes"] = int(test_episodes)
-    if max_steps is not None:
-        over["max_steps"] = int(max_steps)
+    over = _test_overrides(test_episodes, max_steps)
     cfg = td3d_cfg_from_config(config, **over)
     params = torch.as_tensor(params, dtype=torch.float32).to(dev).contiguous()
     n = params.shape[0]
     out = engine.td3d_test_population(cfg, params, _device_i64(rng_keys, n, dev, "rng_keys"), _device_i64(episode_offset, n, dev, "episode_offset"),
                                       _device_i64(learn_calls, n, dev, "learn_calls"))
-    return _triples({k: v.cpu().numpy() for k, v in out.items()})
+    return _triples(out)
 
 
 test_discrete_actor_agents.__test__ = False
@@ -211,16 +198,12 @@ def test_tabular_agents(config, q_tables, tables=None, test_episodes=None, max_s
     if tables is None:
         from ..envs.env_factory import EnvFactory
         tables = EnvFactory(config=config).generate_real_env().env.tables
-    over = {}
-    if test_episodes is not None:
-        over["test_episodes"] = int(test_episodes)
-    if max_steps is not None:
-        over["max_steps"] = int(max_steps)
+    over = _test_overrides(test_episodes, max_steps)
     cfg = ql_cfg_from_config(config, tables, **over)
     dev = engine.require_device()
     q = torch.as_tensor(q_tables, dtype=torch.float64).to(dev).contiguous()
     out = engine.ql_test_population(cfg, q.reshape(q.shape[0], -1), tables)
-    return _triples({k: v.cpu().numpy() for k, v in out.items()})
+    return _triples(out)
 
 
 test_tabular_agents.__test__ = False

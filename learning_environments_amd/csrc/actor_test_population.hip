@@ -18,16 +18,14 @@
 //        z = det_normal(key, STREAM_PPO_TEST_NOISE, ((episode_offset + e) * cap + agent_step) * A + k)
 // With a noise tape z = noise[agent][e][agent_step][k] and the streams are not drawn.
 //
-// Grid (agent, block of at most AC_TB episodes), 512 threads.  The episodes of a block advance in lock-step; a finished one idles until the
-// block ends.  A forward item is (output unit j, group of AT_EPT episodes): consecutive lanes own consecutive units, so the activation reads
-// of a wave are LDS broadcasts whatever the row stride, and a weight is loaded once for the group's episodes.  The fp64 env state is
-// [rows][SD] in LDS and thread (episode, word) steps it (the stand-in has 17 words: 272 threads per repeat instead of 16); thread e < rows
-// owns episode e's bookkeeping (reward sum, step counts, the done flag).
-// Dynamic LDS (floats), rows = min(T, AC_TB): two activation buffers [rows][W], W = H rounded up to 4 | a TD3 actor's shared LayerNorm with
-// two or more hidden layers: [rows][H | 1] for ln_rows_forward | the actor's parameters where all of it stays below AC_LDS_LIMIT, every
-// weight matrix transposed (k-major: conflict-free for lanes on consecutive units); otherwise the weights are read from global memory, a lane
-// streaming its unit's row.  The widest admitted shape (H 512, three hidden layers, LayerNorm) takes 2 * 16 * 512 + 16 * 513 floats = 96.1 KiB
-// and is never staged.  __launch_bounds__(DNT, 4): four waves per SIMD, i.e. at most 128 VGPRs (a scratch frame of up to 100 B per lane).
+// Grid (agent, block of at most TP_TB episodes), 512 threads.  The episodes of a block advance in lock-step; a finished one idles until the
+// block ends.  The fp64 env state is [rows][SD] in LDS and thread (episode, word) steps it (the stand-in has 17 words: 272 threads per
+// repeat instead of 16); thread e < rows owns episode e's bookkeeping (reward sum, step counts, the done flag).
+// The block's episodes and their alive mask, the dynamic-LDS layout, the staging and the hidden layers are the shared pieces of
+// lenv_at_layer.cuh (tp_block, tp_stage_mlp, tp_trunk) and lenv_tp_layout.h (tp_lds_layout); the launch plan is tp_launch_plan of lenv_host.h.  Here W = H rounded
+// up to 4, the LayerNorm is a TD3 actor's, and the actor is staged where all of it stays below AC_LDS_LIMIT.  The widest admitted shape (H
+// 512, three hidden layers, LayerNorm) takes 2 * 16 * 512 + 16 * 513 floats = 96.1 KiB and is never staged.
+// __launch_bounds__(DNT, 4): four waves per SIMD, i.e. at most 128 VGPRs (a scratch frame of up to 100 B per lane).
 #include <hip/hip_runtime.h>
 #include "../../include/lenv_hip.h"
 #include "lenv_gemm.cuh"
@@ -38,12 +36,10 @@
 
 namespace lenv {
 
-constexpr int AC_TB = 16;                      // episodes of one workgroup
 constexpr int AC_XLD = 20;                     // row stride of the observation rows (the stand-in's 17, rounded up to 4)
 constexpr int AC_ALD = 8;                      // row stride of the action rows (the stand-in's 6)
 constexpr int AC_MAXSD = 17;                   // fp64 words of the widest env state
-constexpr int AC_LNBUF = AC_TB * (T3_MAXW | 1);     // ln_rows_forward: every row of a block in one chunk
-constexpr int AC_MAX_REPEAT = 64;
+constexpr int AC_LNBUF = TP_TB * (T3_MAXW | 1);     // ln_rows_forward: every row of a block in one chunk
 // The actor is staged where the workgroup's LDS stays within half a CU's 160 KiB: two workgroups then share a CU (the kernel is held to 128
 // VGPRs for the same reason), which for a population larger than the 256 CUs is worth more than the staged weights (measured: 400 agents
 // 17-128-128-6, 25.7 ms read from global memory two to a CU against 37.9 ms staged one to a CU; one to a CU the staged form is 7 % faster).
@@ -64,33 +60,26 @@ __global__ __launch_bounds__(DNT, 4) void actor_test_population_kernel(const AcA
 {
     using EnvT = ContEnv<ENV>;
     constexpr int S = EnvT::S, A = EnvT::A, SD = EnvT::SD;
-    static_assert(S <= AC_XLD && A <= AC_ALD && SD <= AC_MAXSD && AC_TB * SD <= DNT, "one thread per (episode, state word)");
+    static_assert(S <= AC_XLD && A <= AC_ALD && SD <= AC_MAXSD && TP_TB * SD <= DNT, "one thread per (episode, state word)");
     extern __shared__ __align__(16) float lds[];
-    __shared__ __align__(16) float xin[AC_TB * AC_XLD];            // the observation each live episode acts on
-    __shared__ __align__(16) float araw[AC_TB * AC_ALD];           // the actor's last Linear + bias
-    __shared__ __align__(16) float actv[AC_TB * AC_ALD];           // the actions
-    __shared__ double xd[AC_TB * SD];                              // the envs' own fp64 state
-    __shared__ int tflag[AC_TB];                                   // episode still running (read by the threads that step its words)
+    __shared__ __align__(16) float xin[TP_TB * AC_XLD];            // the observation each live episode acts on
+    __shared__ __align__(16) float araw[TP_TB * AC_ALD];           // the actor's last Linear + bias
+    __shared__ __align__(16) float actv[TP_TB * AC_ALD];           // the actions
+    __shared__ double xd[TP_TB * SD];                              // the envs' own fp64 state
+    __shared__ int tflag[TP_TB];                                   // episode still running (read by the threads that step its words)
     __shared__ unsigned alive_mask;
     const int tid = threadIdx.x;
     const int64_t agent = blockIdx.x;
     const int H = a.H, L = a.L, T = a.T;
     const bool ln = a.ln != 0, ppo = a.kind == LENV_ACTOR_PPO;
-    const int ep0 = blockIdx.y * AC_TB, rows = T - ep0 < AC_TB ? T - ep0 : AC_TB, rows_max = T < AC_TB ? T : AC_TB;
+    const TpBlock blk = tp_block(T);
+    const int ep0 = blk.ep0, rows = blk.rows;
 
-    float *buf0 = lds, *buf1 = lds + rows_max * a.W;
-    auto buf = [&](int i) { return (i & 1) ? buf1 : buf0; };
-    float *lnbuf = buf1 + rows_max * a.W;
-    float *wst = lnbuf + (ln ? rows_max * (H | 1) : 0);
+    const TpLds lay = tp_lds_layout(blk.rows_max, a.W, ln, H);
+    float *buf0 = lds, *buf1 = lds + lay.act, *lnbuf = buf1 + lay.act, *wst = lnbuf + lay.ln;
     const float *grow = a.params + agent * a.P, *gpar = grow + a.oAct;
     const float *par = ST ? wst : gpar;
-    if (ST) {
-        for (int p = tid; p < a.Pa; p += DNT) wst[p] = gpar[p];     // biases, LayerNorm, and the matrices' places
-        __syncthreads();
-        int n_in = S;
-        for (int l = 0; l < L; ++l) { at_stage_transposed(wst + a.oW[l], gpar + a.oW[l], H, n_in, tid); n_in = H; }
-        at_stage_transposed(wst + a.oW[L], gpar + a.oW[L], A, H, tid);
-    }
+    if (ST) tp_stage_mlp(wst, gpar, a.Pa, a.oW, L, S, H, A, tid);
 
     // ---- env.reset() of every episode of the block ----
     const uint64_t key = a.rng_keys[agent];
@@ -104,27 +93,17 @@ __global__ __launch_bounds__(DNT, 4) void actor_test_population_kernel(const AcA
     float ep_rew = 0.0f;
     int my_el = 0, n_agent = 0;
     bool my_alive = mine;
-    if (tid < AC_TB) tflag[tid] = mine ? 1 : 0;
-    if (tid == 0) alive_mask = (1u << rows) - 1u;                  // rows <= AC_TB = 16
+    if (tid < TP_TB) tflag[tid] = mine ? 1 : 0;
+    tp_alive_init(&alive_mask, rows, tid);
     __syncthreads();
 
-    const int ldh = ln ? H : (H + 3) & ~3;                         // ln_rows_forward takes dense rows
     for (int ai = 0; ai < a.cap; ++ai) {                           // base_agent.py:194 range(0, max_steps, same_action_num)
         const unsigned alive = alive_mask;
         for (int e = tid; e < rows * S; e += DNT) { const int te = e / S, i = e - te * S; xin[te * AC_XLD + i] = EnvT::obs(i, xd + te * SD); }
         __syncthreads();
         // ---- the actor on the live episodes: Actor_TD3 / Actor_PPO.net (models/actor_critic.py:11-19,38-49) ----
-        const float *in = xin;
-        int n_in = S, ldi = AC_XLD;
-        for (int l = 0; l < L; ++l) {
-            float *out = buf(l);
-            const bool at_ln = ln && l >= 1;
-            at_layer<ST>(par + a.oW[l], par + a.ob[l], n_in, H, in, ldi, out, ldh, rows, !at_ln, a.act, 0.0f, alive, tid);
-            __syncthreads();
-            if (at_ln) ln_rows_forward<AC_LNBUF>(lnbuf, out, rows, H, par + a.oLN, par + a.oLN + H, nullptr, nullptr, a.act, 0.0f);
-            in = out; n_in = H; ldi = ldh;
-        }
-        at_layer<ST>(par + a.oW[L], par + a.ob[L], H, A, in, ldi, araw, AC_ALD, rows, false, 0, 0.0f, alive, tid);
+        const TpAct h = tp_trunk<ST, AC_LNBUF>(par, a.oW, a.ob, a.oLN, L, H, ln, xin, S, AC_XLD, buf0, buf1, lnbuf, rows, a.act, 0.0f, alive, tid);
+        at_layer<ST>(par + a.oW[L], par + a.ob[L], H, A, h.x, h.ld, araw, AC_ALD, rows, false, 0, 0.0f, alive, tid);
         __syncthreads();
         // ---- select_test_action (TD3.py:126-129) / actor_old.forward (actor_critic.py:45-49) ----
         for (int e = tid; e < rows * A; e += DNT) {
@@ -183,10 +162,9 @@ __global__ __launch_bounds__(DNT, 4) void actor_test_population_kernel(const AcA
                 a.row_reward[slot] = r32; a.row_done[slot] = my_alive ? 0.0f : 1.0f;
             }
             ++n_agent;
-            if (!my_alive) atomicAnd(&alive_mask, ~(1u << tid));
+            if (!my_alive) tp_retire(&alive_mask, tid);
         }
-        __syncthreads();
-        if (alive_mask == 0) break;                                // uniform; the next write comes behind further barriers
+        if (tp_all_retired(&alive_mask)) break;
     }
     if (mine) { a.returns[ep] = (double)ep_rew; a.env_steps[ep] = my_el; a.agent_steps[ep] = n_agent; }
 }
@@ -195,51 +173,45 @@ __global__ __launch_bounds__(DNT, 4) void actor_test_population_kernel(const AcA
 
 using namespace lenv;
 
-static bool ac_env_ok(int env_id, int S, int A)
-{
-    return (env_id == LENV_ENV_CHEETAH_STANDIN && S == 17 && A == 6) || (env_id == LENV_ENV_PENDULUM && S == 3 && A == 1) ||
-           (env_id == LENV_ENV_CMC && S == 2 && A == 1);
-}
-
 // the entry's own checks of cfg (only the fields the kernel reads) into the launch's shape
 static int ac_shape(int kind, const void *cfg_, AcArgs &a, int &env_id)
 {
     int S, A, H, L, T, act, san, max_steps;
+    bool use_ln = false;                                           // TD3 alone
+    a.ma = 1.0f; a.astd = 0.0f;
     if (kind == LENV_ACTOR_TD3) {
         const lenv_td3_cfg *c = static_cast<const lenv_td3_cfg *>(cfg_);
         env_id = c->env_id; S = c->state_dim; A = c->action_dim; H = c->hidden; L = c->layers; T = c->test_episodes; act = c->act;
         san = c->same_action_num; max_steps = c->max_steps;
+        use_ln = c->use_layer_norm != 0; a.ma = (float)c->max_action; a.astd = (float)c->action_std;
     } else if (kind == LENV_ACTOR_PPO) {
         const lenv_ppo_cfg *c = static_cast<const lenv_ppo_cfg *>(cfg_);
         env_id = c->env_id; S = c->state_dim; A = c->action_dim; H = c->hidden; L = c->layers; T = c->test_episodes; act = c->act;
         san = c->same_action_num; max_steps = c->max_steps;
     } else return LENV_ERR_UNSUPPORTED;                            // TD3_discrete_vary (Gumbel-softmax actor), the gridworld agents: no kind
     if (max_steps < 1) return LENV_ERR_INVALID;
-    if (!ac_env_ok(env_id, S, A)) return LENV_ERR_UNSUPPORTED;
+    if (!lenv_host::tp_cont_env_ok(env_id, S, A)) return LENV_ERR_UNSUPPORTED;
     if (act == LENV_ACT_PRELU || act < 0 || act > LENV_ACT_PRELU) return LENV_ERR_UNSUPPORTED;   // a trained slope in the reference; refused as the fused entries refuse it
-    if (san < 0 || san > AC_MAX_REPEAT) return LENV_ERR_UNSUPPORTED;
+    if (san < 0 || san > TP_MAX_REPEAT) return LENV_ERR_UNSUPPORTED;
     // the envelope of the fused entry of the same kind (td3_layout / ppo_layout), as far as the actor and the test go
     if (kind == LENV_ACTOR_TD3) { if (L < 1 || L > T3_MAXL || H < 1 || H > T3_MAXW || T < 1 || T * S > DNT) return LENV_ERR_UNSUPPORTED; }
     else if (L < 1 || L > PP_MAXL || H < 1 || H > PP_MAXW || T < 1 || T > PP_MAXT) return LENV_ERR_UNSUPPORTED;
-    a.kind = kind; a.H = H; a.L = L; a.act = act; a.T = T; a.max_steps = max_steps; a.k_rep = san > 1 ? san : 1;
-    a.cap = (max_steps + a.k_rep - 1) / a.k_rep;
+    a.kind = kind; a.H = H; a.L = L; a.act = act; a.T = T; a.max_steps = max_steps;
+    lenv_host::tp_repeat(a, max_steps, san);
     a.W = (H + 3) & ~3;
     for (int l = 0; l <= T3_MAXL; ++l) a.oW[l] = a.ob[l] = 0;
     if (kind == LENV_ACTOR_TD3) {
-        const lenv_td3_cfg *c = static_cast<const lenv_td3_cfg *>(cfg_);
         MlpOff ma, mc;
-        mlp_off(ma, S, H, L, A, c->use_layer_norm != 0);
-        mlp_off(mc, S + A, H, L, 1, c->use_layer_norm != 0);
+        mlp_off(ma, S, H, L, A, use_ln);
+        mlp_off(mc, S + A, H, L, 1, use_ln);
         for (int l = 0; l <= L; ++l) { a.oW[l] = ma.oW[l]; a.ob[l] = ma.ob[l]; }
         a.ln = ma.ln; a.oLN = ma.oLN; a.Pa = ma.P; a.oAct = 0; a.P = ma.P + 2 * mc.P;       // actor | critic_1 | critic_2
-        a.ma = (float)c->max_action; a.astd = (float)c->action_std;
     } else {
         PpoMlp ma, mc;
         ppo_mlp(ma, S, H, L, A);
         ppo_mlp(mc, S, H, L, 1);
         for (int l = 0; l <= L; ++l) { a.oW[l] = ma.oW[l]; a.ob[l] = ma.ob[l]; }
         a.ln = 0; a.oLN = 0; a.Pa = ma.P; a.oAct = A; a.P = A + ma.P + mc.P;                // action_std | actor.net | critic.net
-        a.ma = 1.0f; a.astd = 0.0f;
     }
     return LENV_OK;
 }
@@ -266,22 +238,16 @@ extern "C" int lenv_actor_test_population(int kind, const void *cfg, const float
                                           int32_t *agent_steps, float *row_state, float *row_action, float *row_next_state, float *row_reward,
                                           float *row_done, void *stream)
 {
-    if (!cfg || !params || !rng_keys || !returns || !env_steps || !agent_steps || agents < 0) return LENV_ERR_INVALID;
-    const int n_rows = (row_state != nullptr) + (row_action != nullptr) + (row_next_state != nullptr) + (row_reward != nullptr) + (row_done != nullptr);
-    if (n_rows != 0 && n_rows != 5) return LENV_ERR_INVALID;
+    int rc = lenv_host::tp_check_args({ cfg, params, rng_keys, returns, env_steps, agent_steps }, agents, row_state, row_action, row_next_state, row_reward, row_done);
+    if (rc != LENV_OK) return rc;
     AcArgs a{};
     int env_id = 0;
-    const int rc = ac_shape(kind, cfg, a, env_id);
-    if (rc != LENV_OK) return rc;
-    if (agents == 0) return LENV_OK;
-    if (agents > 0x7fffffff) return LENV_ERR_UNSUPPORTED;
+    rc = ac_shape(kind, cfg, a, env_id);
+    if (rc != LENV_OK || agents == 0) return rc;
+    if ((rc = lenv_host::tp_agents_rc(agents, 0x7fffffff)) != LENV_OK) return rc;
     a.params = params; a.rng_keys = rng_keys; a.episode_offset = episode_offset; a.reset_states = reset_states; a.noise = noise;
     a.returns = returns; a.env_steps = env_steps; a.agent_steps = agent_steps;
     a.row_state = row_state; a.row_action = row_action; a.row_next_state = row_next_state; a.row_reward = row_reward; a.row_done = row_done;
-    const int rows_max = a.T < AC_TB ? a.T : AC_TB;
-    size_t lds_bytes = (2 * (size_t)rows_max * a.W + (a.ln ? (size_t)rows_max * (a.H | 1) : 0)) * sizeof(float);
-    const bool staged = lds_bytes + (size_t)a.Pa * sizeof(float) <= AC_LDS_LIMIT;          // the actor next to the activations
-    if (staged) lds_bytes += (size_t)a.Pa * sizeof(float);
-    const dim3 grid((unsigned)agents, (unsigned)((a.T + AC_TB - 1) / AC_TB));
-    return staged ? ac_launch<true>(env_id, grid, lds_bytes, stream, a) : ac_launch<false>(env_id, grid, lds_bytes, stream, a);
+    const lenv_host::TpPlan p = lenv_host::tp_launch_plan(agents, a.T, a.W, a.ln != 0, a.H, a.Pa, AC_LDS_LIMIT);   // the actor next to the activations
+    return p.staged ? ac_launch<true>(env_id, p.grid, p.lds_bytes, stream, a) : ac_launch<false>(env_id, p.grid, p.lds_bytes, stream, a);
 }

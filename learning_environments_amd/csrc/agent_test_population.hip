@@ -9,13 +9,14 @@
 // lenv_dueling_se_inner_loop), the shared LayerNorm is ln_rows_forward of lenv_ln.cuh.  Every dot product is the k-ascending fmaf chain from 0,
 // then the bias, then the activation, so the Q values carry the bits of the GEMM-queue forward and of the register-resident DDQN kernel.
 //
-// Grid (agent, block of at most AT_TB episodes), 512 threads.  The episodes of a block advance in lock-step; a finished one idles until the
+// Grid (agent, block of at most TP_TB episodes), 512 threads.  The episodes of a block advance in lock-step; a finished one idles until the
 // block ends.  A forward item is (output unit j, group of AT_EPT episodes): consecutive lanes own consecutive units, so the activation reads
 // of a wave are LDS broadcasts whatever the row stride, and a weight is loaded once for the group's episodes.  The env state of episode e
 // lives in the registers of thread e.
-// Dynamic LDS (floats), rows = min(T, AT_TB):  two activation buffers [rows][W], W = the widest layer (H, or 2 F for the two head hidden
-// layers of a dueling agent, rounded up to 4) | q_layer_norm with two or more hidden layers: [rows][H | 1] for ln_rows_forward | the agent's
-// parameters where they still fit into 160 KiB, every weight matrix transposed (k-major: conflict-free for lanes on consecutive units);
+// The block's episodes and their alive mask, the dynamic-LDS layout, the staging and the hidden layers are the shared pieces of
+// lenv_at_layer.cuh (tp_block, tp_stage_mlp; the hidden-layer loop of tp_trunk is written out below) and lenv_tp_layout.h (tp_lds_layout); the launch plan is tp_launch_plan of lenv_host.h.  Here W = the
+// widest layer (H, or 2 F for the two head hidden layers of a dueling agent, rounded up to 4), and the agent's parameters are staged where
+// they still fit into 160 KiB (AT_LDS_LIMIT), every weight matrix transposed (k-major: conflict-free for lanes on consecutive units);
 // otherwise the weights are read from global memory, a lane streaming its unit's row.  The widest admitted shape (H 512, three hidden layers,
 // LayerNorm) takes 2 * 16 * 512 + 16 * 513 floats = 96.1 KiB.
 #include <hip/hip_runtime.h>
@@ -28,11 +29,9 @@
 
 namespace lenv {
 
-constexpr int AT_TB = 16;                      // episodes of one workgroup
 constexpr int AT_XLD = 8;                      // row stride of the observation rows
 constexpr int AT_MAXS = 6, AT_MAXA = 3;        // the widest observation (Acrobot) and the most actions of the three envs
-constexpr int AT_LNBUF = AT_TB * (D_MAXH | 1); // ln_rows_forward: every row of a block in one chunk
-constexpr int AT_MAX_REPEAT = 64;
+constexpr int AT_LNBUF = TP_TB * (D_MAXH | 1); // ln_rows_forward: every row of a block in one chunk
 constexpr size_t AT_LDS_LIMIT = 160 * 1024 - 1024;   // dynamic bytes next to the static arrays below (under 1 KiB)
 
 struct AtArgs {
@@ -48,28 +47,24 @@ template <bool ST>
 __global__ __launch_bounds__(DNT) void agent_test_population_kernel(const AtArgs a)
 {
     extern __shared__ __align__(16) float lds[];
-    __shared__ __align__(16) float xin[AT_TB * AT_XLD];            // the observation each live episode acts on
-    __shared__ float qadv[AT_TB * 4], vhead[AT_TB];                // Q(s, .) of a plain agent / the advantage head; the value head
+    __shared__ __align__(16) float xin[TP_TB * AT_XLD];            // the observation each live episode acts on
+    __shared__ float qadv[TP_TB * 4], vhead[TP_TB];                // Q(s, .) of a plain agent / the advantage head; the value head
     __shared__ unsigned alive_mask;
     const int tid = threadIdx.x;
     const int64_t agent = blockIdx.x;
     const int S = a.S, A = a.A, H = a.H, L = a.L, F = a.F, T = a.T;
     const bool plain = a.plain != 0, ln = a.ln != 0;
-    const int ep0 = blockIdx.y * AT_TB, rows = T - ep0 < AT_TB ? T - ep0 : AT_TB, rows_max = T < AT_TB ? T : AT_TB;
+    const TpBlock blk = tp_block(T);
+    const int ep0 = blk.ep0, rows = blk.rows;
     const DuelOffsets po = duel_param_offsets(S, A, H, F, L, plain, ln);
 
-    float *buf0 = lds, *buf1 = lds + rows_max * a.W;
+    const TpLds lay = tp_lds_layout(blk.rows_max, a.W, ln, H);
+    float *buf0 = lds, *buf1 = lds + lay.act, *lnbuf = buf1 + lay.act, *wst = lnbuf + lay.ln;
     auto buf = [&](int i) { return (i & 1) ? buf1 : buf0; };
-    float *lnbuf = buf1 + rows_max * a.W;
-    float *wst = lnbuf + (ln ? rows_max * (H | 1) : 0);
     const float *gpar = a.params + agent * a.P;
     const float *par = ST ? wst : gpar;
     if (ST) {
-        for (int p = tid; p < a.P; p += DNT) wst[p] = gpar[p];     // biases, LayerNorm, and the matrices' places
-        __syncthreads();
-        int n_in = S;
-        for (int l = 0; l < L; ++l) { at_stage_transposed(wst + po.oWf[l], gpar + po.oWf[l], H, n_in, tid); n_in = H; }
-        at_stage_transposed(wst + po.oWf[L], gpar + po.oWf[L], F, H, tid);
+        tp_stage_mlp(wst, gpar, a.P, po.oWf, L, S, H, F, tid);
         if (!plain) {
             at_stage_transposed(wst + po.oWv1, gpar + po.oWv1, F, F, tid);
             at_stage_transposed(wst + po.oWa1, gpar + po.oWa1, F, F, tid);
@@ -92,13 +87,15 @@ __global__ __launch_bounds__(DNT) void agent_test_population_kernel(const AtArgs
 #pragma unroll
         for (int i = 0; i < AT_MAXS; ++i) if (i < S) xin[tid * AT_XLD + i] = obs[i];
     }
-    if (tid == 0) alive_mask = (1u << rows) - 1u;                  // rows <= AT_TB = 16
+    tp_alive_init(&alive_mask, rows, tid);
     __syncthreads();
 
     const int ldh = ln ? H : (H + 3) & ~3;                         // ln_rows_forward takes dense rows
     for (int t = 0; t < a.max_steps; t += a.k_rep) {               // base_agent.py:194 range(0, max_steps, same_action_num)
         const unsigned alive = alive_mask;
         // ---- Q(s, .) of the live episodes: Critic_DQN / Critic_DuelingDQN (models/actor_critic.py:84-122) ----
+        // (tp_trunk written out: it takes the offsets through pointers, and po's are computed in registers here, not kernel arguments as in the
+        // two actor kernels -- handing them over cost the 2-256-256-3 MountainCar agent 1.8 %, docs/notebook_test_population_refactor.md)
         const float *in = xin;
         int n_in = S, ldi = AT_XLD;
         for (int l = 0; l < L; ++l) {
@@ -164,10 +161,9 @@ __global__ __launch_bounds__(DNT) void agent_test_population_kernel(const AtArgs
             for (int i = 0; i < AT_MAXS; ++i) if (i < S) xin[tid * AT_XLD + i] = obs[i];
             ep_rew = ep_rew + r32;
             tlen += nstep; ++n_agent;
-            if (dn) { live = false; atomicAnd(&alive_mask, ~(1u << tid)); }
+            if (dn) { live = false; tp_retire(&alive_mask, tid); }
         }
-        __syncthreads();
-        if (alive_mask == 0) break;                                // uniform; the next write comes behind further barriers
+        if (tp_all_retired(&alive_mask)) break;
     }
     if (mine) { a.returns[ep] = (double)ep_rew; a.env_steps[ep] = tlen; a.agent_steps[ep] = n_agent; }
 }
@@ -185,14 +181,12 @@ static int at_shape(const lenv_ddqn_cfg *cfg, AtArgs &a)
     const int S = cfg->state_dim, A = cfg->num_actions, H = cfg->q_hidden, L = cfg->q_layers, F = plain ? A : cfg->feature_dim, T = cfg->test_episodes;
     if (cfg->q_act == LENV_ACT_PRELU) return LENV_ERR_UNSUPPORTED;     // a trained slope in the reference; refused as the generic kernel refuses it
     if (L < 1 || L > D_MAXL || H < 1 || H > D_MAXH || F < 1 || F > D_MAXW || T < 1 || T > D_MAXW) return LENV_ERR_UNSUPPORTED;
-    if (cfg->same_action_num < 0 || cfg->same_action_num > AT_MAX_REPEAT) return LENV_ERR_UNSUPPORTED;
-    if (!((cfg->env_id == LENV_ENV_CARTPOLE && S == 4 && A == 2) || (cfg->env_id == LENV_ENV_ACROBOT && S == 6 && A == 3) ||
-          (cfg->env_id == LENV_ENV_MOUNTAINCAR && S == 2 && A == 3)))
-        return LENV_ERR_UNSUPPORTED;
+    if (cfg->same_action_num < 0 || cfg->same_action_num > TP_MAX_REPEAT) return LENV_ERR_UNSUPPORTED;
+    if (!lenv_host::tp_discrete_env_ok(cfg->env_id, S, A)) return LENV_ERR_UNSUPPORTED;
     a.env_id = cfg->env_id; a.S = S; a.A = A; a.H = H; a.L = L; a.F = F; a.act = cfg->q_act; a.prelu = cfg->q_prelu; a.plain = plain ? 1 : 0;
     a.ln = (cfg->q_layer_norm != 0 && L >= 2) ? 1 : 0;
-    a.T = T; a.max_steps = cfg->max_steps; a.k_rep = cfg->same_action_num > 1 ? cfg->same_action_num : 1;
-    a.cap = (cfg->max_steps + a.k_rep - 1) / a.k_rep;
+    a.T = T; a.max_steps = cfg->max_steps;
+    lenv_host::tp_repeat(a, cfg->max_steps, cfg->same_action_num);
     a.P = duel_param_offsets(S, A, H, F, L, plain, a.ln != 0).P;
     const int hw = (H + 3) & ~3, fw = 2 * ((F + 3) & ~3);
     a.W = plain || hw > fw ? hw : fw;
@@ -212,22 +206,16 @@ extern "C" int lenv_agent_test_population(const lenv_ddqn_cfg *cfg, const float 
                                           float *row_state, int32_t *row_action, float *row_next_state, float *row_reward, float *row_done,
                                           void *stream)
 {
-    if (!cfg || !params || !rng_keys || !returns || !env_steps || !agent_steps || agents < 0) return LENV_ERR_INVALID;
-    const int n_rows = (row_state != nullptr) + (row_action != nullptr) + (row_next_state != nullptr) + (row_reward != nullptr) + (row_done != nullptr);
-    if (n_rows != 0 && n_rows != 5) return LENV_ERR_INVALID;
-    AtArgs a{};
-    const int rc = at_shape(cfg, a);
+    int rc = lenv_host::tp_check_args({ cfg, params, rng_keys, returns, env_steps, agent_steps }, agents, row_state, row_action, row_next_state, row_reward, row_done);
     if (rc != LENV_OK) return rc;
-    if (agents == 0) return LENV_OK;
-    if (agents > 0x7fffffff) return LENV_ERR_UNSUPPORTED;
+    AtArgs a{};
+    rc = at_shape(cfg, a);
+    if (rc != LENV_OK || agents == 0) return rc;
+    if ((rc = lenv_host::tp_agents_rc(agents, 0x7fffffff)) != LENV_OK) return rc;
     a.params = params; a.rng_keys = rng_keys; a.episode_offset = episode_offset; a.reset_states = reset_states;
     a.returns = returns; a.env_steps = env_steps; a.agent_steps = agent_steps;
     a.row_state = row_state; a.row_action = row_action; a.row_next_state = row_next_state; a.row_reward = row_reward; a.row_done = row_done;
-    const int rows_max = a.T < AT_TB ? a.T : AT_TB;
-    size_t lds_bytes = (2 * (size_t)rows_max * a.W + (a.ln ? (size_t)rows_max * (a.H | 1) : 0)) * sizeof(float);
-    const bool staged = lds_bytes + (size_t)a.P * sizeof(float) <= AT_LDS_LIMIT;         // the parameters next to the activations
-    if (staged) lds_bytes += (size_t)a.P * sizeof(float);
-    const dim3 grid((unsigned)agents, (unsigned)((a.T + AT_TB - 1) / AT_TB));
-    if (staged) return lenv_host::launch(agent_test_population_kernel<true>, grid, dim3(DNT), lds_bytes, stream, a);
-    return lenv_host::launch(agent_test_population_kernel<false>, grid, dim3(DNT), lds_bytes, stream, a);
+    const lenv_host::TpPlan p = lenv_host::tp_launch_plan(agents, a.T, a.W, a.ln != 0, a.H, a.P, AT_LDS_LIMIT);    // the parameters next to the activations
+    if (p.staged) return lenv_host::launch(agent_test_population_kernel<true>, p.grid, dim3(DNT), p.lds_bytes, stream, a);
+    return lenv_host::launch(agent_test_population_kernel<false>, p.grid, dim3(DNT), p.lds_bytes, stream, a);
 }

@@ -15,12 +15,12 @@
 //   temp = td3d_temperature(gumbel_temp, max(learn_calls - 1, 0)): the fused loop reads the temperature before it counts a learn call.
 // With a gumbel / noise tape g / z = tape[agent][e][step][k] and that stream is not drawn.
 //
-// Grid (agent, block of at most DA_TB episodes), 512 threads.  The episodes of a block advance in lock-step; a finished one idles until the
-// block ends.  A forward item is (output unit j, group of AT_EPT episodes).  The fp64 env state of episode e lives in the registers of thread
-// e, which also applies the head and the noise to its row (A <= 3) and keeps the episode's books.
-// Dynamic LDS (floats), rows = min(T, DA_TB): two activation buffers [rows][W], W = H rounded up to 4 | with LayerNorm and two or more hidden
-// layers: [rows][H | 1] for ln_rows_forward | the actor's parameters where all of it stays below DA_LDS_LIMIT, every weight matrix
-// transposed (k-major); otherwise the weights are read from global memory, a lane streaming its unit's row.
+// Grid (agent, block of at most TP_TB episodes), 512 threads.  The episodes of a block advance in lock-step; a finished one idles until the
+// block ends.  The fp64 env state of episode e lives in the registers of thread e, which also applies the head and the noise to its row
+// (A <= 3) and keeps the episode's books.
+// The block's episodes and their alive mask, the dynamic-LDS layout, the staging and the hidden layers are the shared pieces of
+// lenv_at_layer.cuh (tp_block, tp_stage_mlp, tp_trunk) and lenv_tp_layout.h (tp_lds_layout); the launch plan is tp_launch_plan of lenv_host.h.  Here W = H rounded
+// up to 4, and the actor is staged where all of it stays below DA_LDS_LIMIT.
 // __launch_bounds__(DNT, 4): four waves per SIMD, i.e. at most 128 VGPRs.  Without the bound the six instantiations compile to 135..142 VGPRs
 // (three waves per SIMD: one workgroup of 8 waves per CU, and the staging rule below rests on two); with it to 128 VGPRs and a scratch frame
 // of 12..44 B per lane.
@@ -34,10 +34,9 @@
 
 namespace lenv {
 
-constexpr int DA_TB = 16;                      // episodes of one workgroup
 constexpr int DA_XLD = 8;                      // row stride of the observation rows (Acrobot's 6, rounded up to 4)
 constexpr int DA_ALD = 4;                      // row stride of the raw actor outputs (at most 3 actions)
-constexpr int DA_LNBUF = DA_TB * (TD_MAXW | 1);     // ln_rows_forward: every row of a block in one chunk
+constexpr int DA_LNBUF = TP_TB * (TD_MAXW | 1);     // ln_rows_forward: every row of a block in one chunk
 constexpr int DA_MAXT = 64;                    // test_episodes the fused entry admits (td3d_layout)
 // The rule of actor_test_population.hip (AC_LDS_LIMIT): the actor is staged where the workgroup's LDS stays within half a CU's 160 KiB, so that
 // two workgroups still share a CU; the static arrays below take under 1 KiB.
@@ -60,30 +59,23 @@ __global__ __launch_bounds__(DNT, 4) void discrete_actor_test_population_kernel(
 {
     constexpr int S = ENVD == LENV_ENV_CARTPOLE ? 4 : (ENVD == LENV_ENV_ACROBOT ? 6 : 2);
     constexpr int A = ENVD == LENV_ENV_CARTPOLE ? 2 : 3;
-    static_assert(S <= DA_XLD && A <= DA_ALD && A <= TD_MAXA && DA_TB <= 32, "row strides and the alive mask");
+    static_assert(S <= DA_XLD && A <= DA_ALD && A <= TD_MAXA && TP_TB <= 32, "row strides and the alive mask");
     extern __shared__ __align__(16) float lds[];
-    __shared__ __align__(16) float xin[DA_TB * DA_XLD];            // the observation each live episode acts on
-    __shared__ __align__(16) float araw[DA_TB * DA_ALD];           // the actor's last Linear + bias
+    __shared__ __align__(16) float xin[TP_TB * DA_XLD];            // the observation each live episode acts on
+    __shared__ __align__(16) float araw[TP_TB * DA_ALD];           // the actor's last Linear + bias
     __shared__ unsigned alive_mask;
     const int tid = threadIdx.x;
     const int64_t agent = blockIdx.x;
     const int H = a.H, L = a.L, T = a.T;
     const bool ln = a.ln != 0;
-    const int ep0 = blockIdx.y * DA_TB, rows = T - ep0 < DA_TB ? T - ep0 : DA_TB, rows_max = T < DA_TB ? T : DA_TB;
+    const TpBlock blk = tp_block(T);
+    const int ep0 = blk.ep0, rows = blk.rows;
 
-    float *buf0 = lds, *buf1 = lds + rows_max * a.W;
-    auto buf = [&](int i) { return (i & 1) ? buf1 : buf0; };
-    float *lnbuf = buf1 + rows_max * a.W;
-    float *wst = lnbuf + (ln ? rows_max * (H | 1) : 0);
+    const TpLds lay = tp_lds_layout(blk.rows_max, a.W, ln, H);
+    float *buf0 = lds, *buf1 = lds + lay.act, *lnbuf = buf1 + lay.act, *wst = lnbuf + lay.ln;
     const float *gpar = a.params + agent * a.P;                    // actor | critic_1 | critic_2: the actor comes first
     const float *par = ST ? wst : gpar;
-    if (ST) {
-        for (int p = tid; p < a.Pa; p += DNT) wst[p] = gpar[p];     // biases, LayerNorm, and the matrices' places
-        __syncthreads();
-        int n_in = S;
-        for (int l = 0; l < L; ++l) { at_stage_transposed(wst + a.oW[l], gpar + a.oW[l], H, n_in, tid); n_in = H; }
-        at_stage_transposed(wst + a.oW[L], gpar + a.oW[L], A, H, tid);
-    }
+    if (ST) tp_stage_mlp(wst, gpar, a.Pa, a.oW, L, S, H, A, tid);
 
     // ---- env.reset() of every episode of the block ----
     const uint64_t key = a.rng_keys[agent];
@@ -105,24 +97,14 @@ __global__ __launch_bounds__(DNT, 4) void discrete_actor_test_population_kernel(
 #pragma unroll
         for (int i = 0; i < S; ++i) xin[tid * DA_XLD + i] = obs[i];
     }
-    if (tid == 0) alive_mask = (1u << rows) - 1u;                  // rows <= DA_TB = 16
+    tp_alive_init(&alive_mask, rows, tid);
     __syncthreads();
 
-    const int ldh = ln ? H : (H + 3) & ~3;                         // ln_rows_forward takes dense rows
     for (int t = 0; t < a.max_steps; ++t) {
         const unsigned alive = alive_mask;
         // ---- Actor_TD3_discrete.net on the live episodes (models/actor_critic.py:22-35) ----
-        const float *in = xin;
-        int n_in = S, ldi = DA_XLD;
-        for (int l = 0; l < L; ++l) {
-            float *out = buf(l);
-            const bool at_ln = ln && l >= 1;
-            at_layer<ST>(par + a.oW[l], par + a.ob[l], n_in, H, in, ldi, out, ldh, rows, !at_ln, a.act, 0.0f, alive, tid);
-            __syncthreads();
-            if (at_ln) ln_rows_forward<DA_LNBUF>(lnbuf, out, rows, H, par + a.oLN, par + a.oLN + H, nullptr, nullptr, a.act, 0.0f);
-            in = out; n_in = H; ldi = ldh;
-        }
-        at_layer<ST>(par + a.oW[L], par + a.ob[L], H, A, in, ldi, araw, DA_ALD, rows, false, 0, 0.0f, alive, tid);
+        const TpAct h = tp_trunk<ST, DA_LNBUF>(par, a.oW, a.ob, a.oLN, L, H, ln, xin, S, DA_XLD, buf0, buf1, lnbuf, rows, a.act, 0.0f, alive, tid);
+        at_layer<ST>(par + a.oW[L], par + a.ob[L], H, A, h.x, h.ld, araw, DA_ALD, rows, false, 0, 0.0f, alive, tid);
         __syncthreads();
         // ---- select_test_action (:169-171), then EnvWrapper.step on the real env with action.argmax() ----
         if (live) {
@@ -159,10 +141,9 @@ __global__ __launch_bounds__(DNT, 4) void discrete_actor_test_population_kernel(
 #pragma unroll
             for (int i = 0; i < S; ++i) xin[tid * DA_XLD + i] = obs[i];
             ep_rew = ep_rew + r32;
-            if (dn) { live = false; atomicAnd(&alive_mask, ~(1u << tid)); }
+            if (dn) { live = false; tp_retire(&alive_mask, tid); }
         }
-        __syncthreads();
-        if (alive_mask == 0) break;                                // uniform; the next write comes behind further barriers
+        if (tp_all_retired(&alive_mask)) break;
     }
     if (mine) { a.returns[ep] = (double)ep_rew; a.env_steps[ep] = tlen; a.agent_steps[ep] = tlen; }
 }
@@ -177,9 +158,7 @@ static int da_shape(const lenv_td3d_cfg *cfg, DaArgs &a)
     if (cfg->max_steps < 1) return LENV_ERR_INVALID;
     const int S = cfg->state_dim, A = cfg->action_dim, H = cfg->hidden, L = cfg->layers, T = cfg->test_episodes;
     // the envelope of td3d_layout, as far as the actor and the test go
-    if (!((cfg->env_id == LENV_ENV_CARTPOLE && S == 4 && A == 2) || (cfg->env_id == LENV_ENV_ACROBOT && S == 6 && A == 3) ||
-          (cfg->env_id == LENV_ENV_MOUNTAINCAR && S == 2 && A == 3)))
-        return LENV_ERR_UNSUPPORTED;
+    if (!lenv_host::tp_discrete_env_ok(cfg->env_id, S, A)) return LENV_ERR_UNSUPPORTED;
     if (cfg->act == LENV_ACT_PRELU || cfg->act < 0 || cfg->act > LENV_ACT_PRELU) return LENV_ERR_UNSUPPORTED;   // a trained slope in the reference
     if (L < 1 || L > TD_MAXL || H < 1 || H > TD_MAXW || T < 1 || T > DA_MAXT || !(cfg->gumbel_temp > 0.0)) return LENV_ERR_UNSUPPORTED;
     DMlpOff ma, mc;
@@ -214,22 +193,16 @@ extern "C" int lenv_td3d_test_population(const lenv_td3d_cfg *cfg, const float *
                                          int64_t agents, double *returns, int32_t *env_steps, int32_t *agent_steps, float *row_state,
                                          float *row_action, float *row_next_state, float *row_reward, float *row_done, void *stream)
 {
-    if (!cfg || !params || !rng_keys || !returns || !env_steps || !agent_steps || agents < 0) return LENV_ERR_INVALID;
-    const int n_rows = (row_state != nullptr) + (row_action != nullptr) + (row_next_state != nullptr) + (row_reward != nullptr) + (row_done != nullptr);
-    if (n_rows != 0 && n_rows != 5) return LENV_ERR_INVALID;
-    DaArgs a{};
-    const int rc = da_shape(cfg, a);
+    int rc = lenv_host::tp_check_args({ cfg, params, rng_keys, returns, env_steps, agent_steps }, agents, row_state, row_action, row_next_state, row_reward, row_done);
     if (rc != LENV_OK) return rc;
-    if (agents == 0) return LENV_OK;
-    if (agents > 0x7fffffff) return LENV_ERR_UNSUPPORTED;
+    DaArgs a{};
+    rc = da_shape(cfg, a);
+    if (rc != LENV_OK || agents == 0) return rc;
+    if ((rc = lenv_host::tp_agents_rc(agents, 0x7fffffff)) != LENV_OK) return rc;
     a.params = params; a.rng_keys = rng_keys; a.episode_offset = episode_offset; a.learn_calls = learn_calls; a.reset_states = reset_states;
     a.gumbel = gumbel; a.noise = noise;
     a.returns = returns; a.env_steps = env_steps; a.agent_steps = agent_steps;
     a.row_state = row_state; a.row_action = row_action; a.row_next_state = row_next_state; a.row_reward = row_reward; a.row_done = row_done;
-    const int rows_max = a.T < DA_TB ? a.T : DA_TB;
-    size_t lds_bytes = (2 * (size_t)rows_max * a.W + (a.ln ? (size_t)rows_max * (a.H | 1) : 0)) * sizeof(float);
-    const bool staged = lds_bytes + (size_t)a.Pa * sizeof(float) <= DA_LDS_LIMIT;          // the actor next to the activations
-    if (staged) lds_bytes += (size_t)a.Pa * sizeof(float);
-    const dim3 grid((unsigned)agents, (unsigned)((a.T + DA_TB - 1) / DA_TB));
-    return staged ? da_launch<true>(cfg->env_id, grid, lds_bytes, stream, a) : da_launch<false>(cfg->env_id, grid, lds_bytes, stream, a);
+    const lenv_host::TpPlan p = lenv_host::tp_launch_plan(agents, a.T, a.W, a.ln != 0, a.H, a.Pa, DA_LDS_LIMIT);   // the actor next to the activations
+    return p.staged ? da_launch<true>(cfg->env_id, p.grid, p.lds_bytes, stream, a) : da_launch<false>(cfg->env_id, p.grid, p.lds_bytes, stream, a);
 }

@@ -8,6 +8,7 @@
 
 #include "../../include/lenv_hip.h"
 #include "lenv_device.cuh"
+#include "lenv_tp_layout.h"       // TP_TB and tp_lds_layout: the test-population kernels' own layout function, read by tp_launch_plan
 
 namespace lenv_host {
 
@@ -75,6 +76,54 @@ inline int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds_bytes, v
         return LENV_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, grid, block, lds_bytes, static_cast<hipStream_t>(stream), args...);
     return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
+}
+
+// ---- the test-population entries (agent / actor / discrete_actor / ql _test_population.hip) ----
+
+// `required` (cfg, the inputs, the three per-episode outputs) all given, agents >= 0, and the five row arrays all or none: else LENV_ERR_INVALID
+inline int tp_check_args(std::initializer_list<const void *> required, int64_t agents, const void *row_state, const void *row_action,
+                         const void *row_next_state, const void *row_reward, const void *row_done)
+{
+    for (const void *p : required) if (!p) return LENV_ERR_INVALID;
+    if (agents < 0) return LENV_ERR_INVALID;
+    const int n_rows = (row_state != nullptr) + (row_action != nullptr) + (row_next_state != nullptr) + (row_reward != nullptr) + (row_done != nullptr);
+    return n_rows != 0 && n_rows != 5 ? LENV_ERR_INVALID : LENV_OK;
+}
+
+// behind the shape checks and the `agents == 0` return: more agents than the grid (or the entry's index arithmetic) takes
+inline int tp_agents_rc(int64_t agents, int64_t max_agents) { return agents > max_agents ? LENV_ERR_UNSUPPORTED : LENV_OK; }
+
+// base_agent.py:194 range(0, max_steps, same_action_num): env steps per agent step, and the agent steps (the rows) an episode can take
+template <class Args> inline void tp_repeat(Args &a, int max_steps, int same_action_num)
+{
+    a.k_rep = same_action_num > 1 ? same_action_num : 1;
+    a.cap = (max_steps + a.k_rep - 1) / a.k_rep;
+}
+
+// the real envs of the entries with their observation and action widths
+inline bool tp_cont_env_ok(int env_id, int S, int A)
+{
+    return (env_id == LENV_ENV_CHEETAH_STANDIN && S == 17 && A == 6) || (env_id == LENV_ENV_PENDULUM && S == 3 && A == 1) ||
+           (env_id == LENV_ENV_CMC && S == 2 && A == 1);
+}
+inline bool tp_discrete_env_ok(int env_id, int S, int A)
+{
+    return (env_id == LENV_ENV_CARTPOLE && S == 4 && A == 2) || (env_id == LENV_ENV_ACROBOT && S == 6 && A == 3) ||
+           (env_id == LENV_ENV_MOUNTAINCAR && S == 2 && A == 3);
+}
+
+// The launch of the three MLP kernels: the dynamic LDS of tp_lds_layout, with the `params_to_stage` floats behind it where all of it stays
+// within `limit` bytes (the kernel's ST instantiation then), on the grid (agent, block of TP_TB episodes).
+struct TpPlan { size_t lds_bytes; bool staged; dim3 grid; };
+inline TpPlan tp_launch_plan(int64_t agents, int T, int W, bool ln, int H, int params_to_stage, size_t limit)
+{
+    TpPlan p;
+    const lenv::TpLds lay = lenv::tp_lds_layout(T < lenv::TP_TB ? T : lenv::TP_TB, W, ln, H);
+    p.lds_bytes = (2 * (size_t)lay.act + lay.ln) * sizeof(float);
+    p.staged = p.lds_bytes + (size_t)params_to_stage * sizeof(float) <= limit;
+    if (p.staged) p.lds_bytes += (size_t)params_to_stage * sizeof(float);
+    p.grid = dim3((unsigned)agents, (unsigned)((T + lenv::TP_TB - 1) / lenv::TP_TB));
+    return p;
 }
 
 // Wave-chain kernels, a chain on a team of G workgroups.  Workgroups per chain: the first G of `candidates` (largest first) that cfg->team_size

@@ -18,7 +18,7 @@
 namespace lenv {
 
 constexpr int QT_NT = 64;                      // threads of a workgroup
-constexpr int QT_MAXA = 8, QT_MAXT = 128, QT_MAX_REPEAT = 64;
+constexpr int QT_MAXA = 8, QT_MAXT = 128;
 
 struct QtArgs {
     int N, A, start, max_steps, T, k_rep, cap;
@@ -69,12 +69,11 @@ static int qt_shape(const lenv_ql_cfg *cfg, QtArgs &a)
 {
     if (cfg->max_steps < 1) return LENV_ERR_INVALID;
     if (cfg->n_actions < 1 || cfg->n_actions > QT_MAXA || cfg->test_episodes < 1 || cfg->test_episodes > QT_MAXT || cfg->same_action_num < 0 ||
-        cfg->same_action_num > QT_MAX_REPEAT || cfg->n_states < 1 || cfg->start_state < 0 || cfg->start_state >= cfg->n_states ||
+        cfg->same_action_num > TP_MAX_REPEAT || cfg->n_states < 1 || cfg->start_state < 0 || cfg->start_state >= cfg->n_states ||
         (int64_t)cfg->n_states * cfg->n_actions > 0x7fffffff)
         return LENV_ERR_UNSUPPORTED;
     a.N = cfg->n_states; a.A = cfg->n_actions; a.start = cfg->start_state; a.max_steps = cfg->max_steps; a.T = cfg->test_episodes;
-    a.k_rep = cfg->same_action_num > 1 ? cfg->same_action_num : 1;
-    a.cap = (cfg->max_steps + a.k_rep - 1) / a.k_rep;
+    lenv_host::tp_repeat(a, cfg->max_steps, cfg->same_action_num);
     return LENV_OK;
 }
 
@@ -91,14 +90,13 @@ extern "C" int lenv_ql_test_population(const lenv_ql_cfg *cfg, const double *q_t
                                        int32_t *row_state, int32_t *row_action, int32_t *row_next_state, float *row_reward, float *row_done,
                                        void *stream)
 {
-    if (!cfg || !q_table || !next_state || !reward || !done || !returns || !env_steps || !agent_steps || agents < 0) return LENV_ERR_INVALID;
-    const int n_rows = (row_state != nullptr) + (row_action != nullptr) + (row_next_state != nullptr) + (row_reward != nullptr) + (row_done != nullptr);
-    if (n_rows != 0 && n_rows != 5) return LENV_ERR_INVALID;
-    QtArgs a{};
-    const int rc = qt_shape(cfg, a);
+    int rc = lenv_host::tp_check_args({ cfg, q_table, next_state, reward, done, returns, env_steps, agent_steps }, agents, row_state, row_action, row_next_state,
+                                      row_reward, row_done);
     if (rc != LENV_OK) return rc;
-    if (agents == 0) return LENV_OK;
-    if (agents > 0x7fffffff / QT_MAXT) return LENV_ERR_UNSUPPORTED;
+    QtArgs a{};
+    rc = qt_shape(cfg, a);
+    if (rc != LENV_OK || agents == 0) return rc;
+    if ((rc = lenv_host::tp_agents_rc(agents, 0x7fffffff / QT_MAXT)) != LENV_OK) return rc;
     a.agents = agents; a.q_table = q_table; a.next_state = next_state; a.reward = reward; a.done = done;
     a.returns = returns; a.env_steps = env_steps; a.agent_steps = agent_steps;
     a.row_state = row_state; a.row_action = row_action; a.row_next_state = row_next_state; a.row_reward = row_reward; a.row_done = row_done;

@@ -195,6 +195,51 @@ def agent_test_num_params(cfg):
     return sum(fi * fo + fo for fi, fo in dims) + (2 * H if cfg.q_layer_norm and L >= 2 else 0)
 
 
+def _mlp_num_params(n_in, hidden, layers, n_out, ln):
+    """Parameters of an MLP n_in - `layers` x hidden - n_out with the shared LayerNorm (weight | bias) from two hidden layers on."""
+    return (n_in * hidden + hidden) + (layers - 1) * (hidden * hidden + hidden) + (2 * hidden if ln and layers >= 2 else 0) + (n_out * hidden + n_out)
+
+
+def _tp_inputs(cap_entry, cap_args, params, P, rng_keys, T, vectors, reset_states, SD, tapes=None, A=0):
+    """The input checks the *_test_population wrappers share: params fp32 [agents,P], rng_keys int64 [agents], `vectors` (name -> optional int64
+    [agents]), reset_states optional fp64 [agents,T,SD] (SD or a callable that gives it), `tapes` (name -> optional fp32 [agents,T,cap,A]).  Returns (agents, cap)."""
+    _chk(params, torch.float32, "params"); _chk(rng_keys, torch.int64, "rng_keys")
+    for name, v in (tapes or {}).items():
+        _chk(v, torch.float32, name)
+    for name, v in vectors.items():
+        _chk(v, torch.int64, name)
+    _chk(reset_states, torch.float64, "reset_states")
+    cap = _count(cap_entry, *cap_args)
+    if callable(SD):                     # the env's state words, looked up only once the entry has admitted cfg's env
+        SD = SD()
+    if params.dim() != 2 or params.shape[1] != P:
+        raise ValueError("params must be [agents,%d]" % P)
+    n = params.shape[0]
+    if tuple(rng_keys.shape) != (n,):
+        raise ValueError("rng_keys must be [agents]")
+    for name, v in vectors.items():
+        if v is not None and tuple(v.shape) != (n,):
+            raise ValueError("%s must be [agents]" % name)
+    if reset_states is not None and tuple(reset_states.shape) != (n, T, SD):
+        raise ValueError("reset_states must be [agents,%d,%d]" % (T, SD))
+    for name, v in (tapes or {}).items():
+        if v is not None and tuple(v.shape) != (n, T, cap, A):
+            raise ValueError("%s must be [agents,%d,%d,%d]" % (name, T, cap, A))
+    return n, cap
+
+
+def _tp_outputs(dev, n, T, cap, want_rows, state_shape, state_dtype, action_shape, action_dtype):
+    """returns / env_steps / agent_steps [agents,T] and, with want_rows, the five row tensors [agents,T,cap(,...)] (states and actions of the
+    given trailing shape and dtype), zero-filled: (the dict the wrappers return, the eight output pointers in ABI order)."""
+    z = lambda dt, *shape: torch.zeros((n, T) + shape, dtype=dt, device=dev)
+    out = dict(returns=z(torch.float64), env_steps=z(torch.int32), agent_steps=z(torch.int32))
+    if want_rows:
+        out.update(row_state=z(state_dtype, cap, *state_shape), row_action=z(action_dtype, cap, *action_shape),
+                   row_next_state=z(state_dtype, cap, *state_shape), row_reward=z(torch.float32, cap), row_done=z(torch.float32, cap))
+    names = ("returns", "env_steps", "agent_steps", "row_state", "row_action", "row_next_state", "row_reward", "row_done")
+    return out, [_ptr(out.get(k)) for k in names]
+
+
 def agent_test_population(cfg, params, rng_keys, episode_offset=None, reset_states=None, want_rows=True):
     """BaseAgent.test of a population of trained DDQN / DuelingDDQN agents in one launch (lenv_agent_test_population): agent i, parameters
     params[i] (fp32 [agents,P] in the layout of the fused loops' final_online), runs T = cfg.test_episodes greedy episodes on the real env.
@@ -204,31 +249,12 @@ def agent_test_population(cfg, params, rng_keys, episode_offset=None, reset_stat
     row_reward / row_done fp32 [agents,T,cap]; slots at or beyond agent_steps[i][e] are zero (the kernel does not write them)."""
     dev = require_device()
     L = _lib.lib()
-    _chk(params, torch.float32, "params"); _chk(rng_keys, torch.int64, "rng_keys")
-    _chk(episode_offset, torch.int64, "episode_offset"); _chk(reset_states, torch.float64, "reset_states")
-    cap = _count("lenv_agent_test_rows_cap", C.byref(cfg))
-    P, T, S = agent_test_num_params(cfg), cfg.test_episodes, cfg.state_dim
-    if params.dim() != 2 or params.shape[1] != P:
-        raise ValueError("params must be [agents,%d]" % P)
-    n = params.shape[0]
-    if tuple(rng_keys.shape) != (n,):
-        raise ValueError("rng_keys must be [agents]")
-    if episode_offset is not None and tuple(episode_offset.shape) != (n,):
-        raise ValueError("episode_offset must be [agents]")
-    if reset_states is not None and tuple(reset_states.shape) != (n, T, 4):
-        raise ValueError("reset_states must be [agents,%d,4]" % T)
-    out = dict(returns=torch.zeros((n, T), dtype=torch.float64, device=dev), env_steps=torch.zeros((n, T), dtype=torch.int32, device=dev),
-               agent_steps=torch.zeros((n, T), dtype=torch.int32, device=dev))
-    rows = {}
-    if want_rows:
-        rows = dict(row_state=torch.zeros((n, T, cap, S), dtype=torch.float32, device=dev), row_action=torch.zeros((n, T, cap), dtype=torch.int32, device=dev),
-                    row_next_state=torch.zeros((n, T, cap, S), dtype=torch.float32, device=dev), row_reward=torch.zeros((n, T, cap), dtype=torch.float32, device=dev),
-                    row_done=torch.zeros((n, T, cap), dtype=torch.float32, device=dev))
-    rc = L.lenv_agent_test_population(C.byref(cfg), _ptr(params), _ptr(rng_keys), _ptr(episode_offset), _ptr(reset_states), n, _ptr(out["returns"]),
-                                      _ptr(out["env_steps"]), _ptr(out["agent_steps"]), _ptr(rows.get("row_state")), _ptr(rows.get("row_action")),
-                                      _ptr(rows.get("row_next_state")), _ptr(rows.get("row_reward")), _ptr(rows.get("row_done")), _stream())
+    T, S = cfg.test_episodes, cfg.state_dim
+    n, cap = _tp_inputs("lenv_agent_test_rows_cap", (C.byref(cfg),), params, agent_test_num_params(cfg), rng_keys, T, dict(episode_offset=episode_offset),
+                        reset_states, 4)
+    out, ptrs = _tp_outputs(dev, n, T, cap, want_rows, (S,), torch.float32, (), torch.int32)
+    rc = L.lenv_agent_test_population(C.byref(cfg), _ptr(params), _ptr(rng_keys), _ptr(episode_offset), _ptr(reset_states), n, *ptrs, _stream())
     _lib.check(rc, "lenv_agent_test_population")
-    out.update(rows)
     return out
 
 
@@ -245,13 +271,10 @@ def actor_test_num_params(kind, cfg):
     (lenv_ppo_num_params).  Computed from the network fields alone, so cfg's training fields may be anything."""
     k = _actor_kind(kind)
     S, A, H, L = cfg.state_dim, cfg.action_dim, cfg.hidden, cfg.layers
-
-    def net(n_in, n_out, ln):
-        return (n_in * H + H) + (L - 1) * (H * H + H) + (2 * H if ln and L >= 2 else 0) + (n_out * H + n_out)
     if k == _lib.ACTOR_TD3:
         ln = bool(cfg.use_layer_norm)
-        return net(S, A, ln) + 2 * net(S + A, 1, ln)
-    return A + net(S, A, False) + net(S, 1, False)
+        return _mlp_num_params(S, H, L, A, ln) + 2 * _mlp_num_params(S + A, H, L, 1, ln)
+    return A + _mlp_num_params(S, H, L, A, False) + _mlp_num_params(S, H, L, 1, False)
 
 
 def actor_test_population(kind, cfg, params, rng_keys, episode_offset=None, reset_states=None, noise=None, want_rows=True):
@@ -269,46 +292,21 @@ def actor_test_population(kind, cfg, params, rng_keys, episode_offset=None, rese
     k = _actor_kind(kind)
     if not isinstance(cfg, Td3Cfg if k == _lib.ACTOR_TD3 else PpoCfg):
         raise TypeError("actor_test_population: kind %r takes a %s" % (kind, "Td3Cfg" if k == _lib.ACTOR_TD3 else "PpoCfg"))
-    _chk(params, torch.float32, "params"); _chk(rng_keys, torch.int64, "rng_keys"); _chk(noise, torch.float32, "noise")
-    _chk(episode_offset, torch.int64, "episode_offset"); _chk(reset_states, torch.float64, "reset_states")
-    cap = _count("lenv_actor_test_rows_cap", k, C.byref(cfg))
-    P, T, S, A = actor_test_num_params(k, cfg), cfg.test_episodes, cfg.state_dim, cfg.action_dim
-    SD = REAL_ENV_DIMS[int(cfg.env_id)][1]
-    if params.dim() != 2 or params.shape[1] != P:
-        raise ValueError("params must be [agents,%d]" % P)
-    n = params.shape[0]
-    if tuple(rng_keys.shape) != (n,):
-        raise ValueError("rng_keys must be [agents]")
-    if episode_offset is not None and tuple(episode_offset.shape) != (n,):
-        raise ValueError("episode_offset must be [agents]")
-    if reset_states is not None and tuple(reset_states.shape) != (n, T, SD):
-        raise ValueError("reset_states must be [agents,%d,%d]" % (T, SD))
-    if noise is not None and tuple(noise.shape) != (n, T, cap, A):
-        raise ValueError("noise must be [agents,%d,%d,%d]" % (T, cap, A))
-    out = dict(returns=torch.zeros((n, T), dtype=torch.float64, device=dev), env_steps=torch.zeros((n, T), dtype=torch.int32, device=dev),
-               agent_steps=torch.zeros((n, T), dtype=torch.int32, device=dev))
-    rows = {}
-    if want_rows:
-        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-        rows = dict(row_state=f32(n, T, cap, S), row_action=f32(n, T, cap, A), row_next_state=f32(n, T, cap, S), row_reward=f32(n, T, cap),
-                    row_done=f32(n, T, cap))
-    rc = L.lenv_actor_test_population(k, C.byref(cfg), _ptr(params), _ptr(rng_keys), _ptr(episode_offset), _ptr(reset_states), _ptr(noise), n,
-                                      _ptr(out["returns"]), _ptr(out["env_steps"]), _ptr(out["agent_steps"]), _ptr(rows.get("row_state")),
-                                      _ptr(rows.get("row_action")), _ptr(rows.get("row_next_state")), _ptr(rows.get("row_reward")),
-                                      _ptr(rows.get("row_done")), _stream())
+    T, S, A = cfg.test_episodes, cfg.state_dim, cfg.action_dim
+    n, cap = _tp_inputs("lenv_actor_test_rows_cap", (k, C.byref(cfg)), params, actor_test_num_params(k, cfg), rng_keys, T,
+                        dict(episode_offset=episode_offset), reset_states, lambda: REAL_ENV_DIMS[int(cfg.env_id)][1], dict(noise=noise), A)
+    out, ptrs = _tp_outputs(dev, n, T, cap, want_rows, (S,), torch.float32, (A,), torch.float32)
+    rc = L.lenv_actor_test_population(k, C.byref(cfg), _ptr(params), _ptr(rng_keys), _ptr(episode_offset), _ptr(reset_states), _ptr(noise), n, *ptrs,
+                                      _stream())
     _lib.check(rc, "lenv_actor_test_population")
-    out.update(rows)
     return out
 
 
 def td3d_test_num_params(cfg):
     """Row width of `params` in td3d_test_population: actor | critic_1 | critic_2 with each net's shared LayerNorm (lenv_td3d_num_params).
     Computed from the network fields alone, so cfg's training fields may be anything."""
-    S, A, H, L = cfg.state_dim, cfg.action_dim, cfg.hidden, cfg.layers
-
-    def net(n_in, n_out):
-        return (n_in * H + H) + (L - 1) * (H * H + H) + (2 * H if cfg.use_layer_norm and L >= 2 else 0) + (n_out * H + n_out)
-    return net(S, A) + 2 * net(S + A, 1)
+    S, A, H, L, ln = cfg.state_dim, cfg.action_dim, cfg.hidden, cfg.layers, bool(cfg.use_layer_norm)
+    return _mlp_num_params(S, H, L, A, ln) + 2 * _mlp_num_params(S + A, H, L, 1, ln)
 
 
 def td3d_test_population(cfg, params, rng_keys, episode_offset=None, learn_calls=None, reset_states=None, gumbel=None, noise=None, want_rows=True):
@@ -326,36 +324,13 @@ def td3d_test_population(cfg, params, rng_keys, episode_offset=None, learn_calls
     L = _lib.lib()
     if not isinstance(cfg, Td3dCfg):
         raise TypeError("td3d_test_population takes a Td3dCfg")
-    _chk(params, torch.float32, "params"); _chk(rng_keys, torch.int64, "rng_keys"); _chk(gumbel, torch.float32, "gumbel"); _chk(noise, torch.float32, "noise")
-    _chk(episode_offset, torch.int64, "episode_offset"); _chk(learn_calls, torch.int64, "learn_calls"); _chk(reset_states, torch.float64, "reset_states")
-    cap = _count("lenv_td3d_test_rows_cap", C.byref(cfg))
-    P, T, S, A = td3d_test_num_params(cfg), cfg.test_episodes, cfg.state_dim, cfg.action_dim
-    if params.dim() != 2 or params.shape[1] != P:
-        raise ValueError("params must be [agents,%d]" % P)
-    n = params.shape[0]
-    if tuple(rng_keys.shape) != (n,):
-        raise ValueError("rng_keys must be [agents]")
-    for name, v in (("episode_offset", episode_offset), ("learn_calls", learn_calls)):
-        if v is not None and tuple(v.shape) != (n,):
-            raise ValueError("%s must be [agents]" % name)
-    if reset_states is not None and tuple(reset_states.shape) != (n, T, 4):
-        raise ValueError("reset_states must be [agents,%d,4]" % T)
-    for name, v in (("gumbel", gumbel), ("noise", noise)):
-        if v is not None and tuple(v.shape) != (n, T, cap, A):
-            raise ValueError("%s must be [agents,%d,%d,%d]" % (name, T, cap, A))
-    out = dict(returns=torch.zeros((n, T), dtype=torch.float64, device=dev), env_steps=torch.zeros((n, T), dtype=torch.int32, device=dev),
-               agent_steps=torch.zeros((n, T), dtype=torch.int32, device=dev))
-    rows = {}
-    if want_rows:
-        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
-        rows = dict(row_state=f32(n, T, cap, S), row_action=f32(n, T, cap, A), row_next_state=f32(n, T, cap, S), row_reward=f32(n, T, cap),
-                    row_done=f32(n, T, cap))
+    T, S, A = cfg.test_episodes, cfg.state_dim, cfg.action_dim
+    n, cap = _tp_inputs("lenv_td3d_test_rows_cap", (C.byref(cfg),), params, td3d_test_num_params(cfg), rng_keys, T,
+                        dict(episode_offset=episode_offset, learn_calls=learn_calls), reset_states, 4, dict(gumbel=gumbel, noise=noise), A)
+    out, ptrs = _tp_outputs(dev, n, T, cap, want_rows, (S,), torch.float32, (A,), torch.float32)
     rc = L.lenv_td3d_test_population(C.byref(cfg), _ptr(params), _ptr(rng_keys), _ptr(episode_offset), _ptr(learn_calls), _ptr(reset_states),
-                                     _ptr(gumbel), _ptr(noise), n, _ptr(out["returns"]), _ptr(out["env_steps"]), _ptr(out["agent_steps"]),
-                                     _ptr(rows.get("row_state")), _ptr(rows.get("row_action")), _ptr(rows.get("row_next_state")),
-                                     _ptr(rows.get("row_reward")), _ptr(rows.get("row_done")), _stream())
+                                     _ptr(gumbel), _ptr(noise), n, *ptrs, _stream())
     _lib.check(rc, "lenv_td3d_test_population")
-    out.update(rows)
     return out
 
 
@@ -381,18 +356,9 @@ def ql_test_population(cfg, q_table, tables, want_rows=True):
             raise ValueError("tables[%r] must be [%d,%d]" % (name, N, A))
         tabs.append(t.contiguous())
     n = q_table.shape[0]
-    out = dict(returns=torch.zeros((n, T), dtype=torch.float64, device=dev), env_steps=torch.zeros((n, T), dtype=torch.int32, device=dev),
-               agent_steps=torch.zeros((n, T), dtype=torch.int32, device=dev))
-    rows = {}
-    if want_rows:
-        z = lambda dt: torch.zeros((n, T, cap), dtype=dt, device=dev)
-        rows = dict(row_state=z(torch.int32), row_action=z(torch.int32), row_next_state=z(torch.int32), row_reward=z(torch.float32),
-                    row_done=z(torch.float32))
-    rc = L.lenv_ql_test_population(C.byref(cfg), _ptr(q_table), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), n, _ptr(out["returns"]),
-                                   _ptr(out["env_steps"]), _ptr(out["agent_steps"]), _ptr(rows.get("row_state")), _ptr(rows.get("row_action")),
-                                   _ptr(rows.get("row_next_state")), _ptr(rows.get("row_reward")), _ptr(rows.get("row_done")), _stream())
+    out, ptrs = _tp_outputs(dev, n, T, cap, want_rows, (), torch.int32, (), torch.int32)
+    rc = L.lenv_ql_test_population(C.byref(cfg), _ptr(q_table), _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), n, *ptrs, _stream())
     _lib.check(rc, "lenv_ql_test_population")
-    out.update(rows)
     return out
 
 

@@ -157,6 +157,9 @@ COMPOSE_CASES = {
     "cartpole_plain": dict(env="CartPole-v0", dueling=False, H=24, L=1, T=3, max_steps=20),
     "mountaincar_dueling_repeat2": dict(env="MountainCar-v0", dueling=True, H=20, L=2, F=8, T=3, max_steps=20, san=2, act="relu"),
     "acrobot_plain_ln_repeat3": dict(env="Acrobot-v1", dueling=False, H=33, L=2, T=3, max_steps=20, san=3, ln=True),
+    # 6-208-208-3 with LayerNorm: 45 971 floats, past the 40 704 that fit next to the activations, so the weights are read from global
+    # memory; T 17 = a second workgroup per agent with one episode
+    "acrobot_plain_unstaged_ln_T17_repeat2": dict(env="Acrobot-v1", dueling=False, H=208, L=2, T=17, max_steps=8, san=2, ln=True),
 }
 
 

@@ -6,89 +6,54 @@ under __launch_bounds__(512, 4): the staging rule wants two workgroups of 8 wave
 instantiations take 135..142), at the price of a small scratch frame, which is bounded here too."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "learning_environments_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+from population_build_common import HIPCC, SHARED_HEADER, episodes_per_workgroup, kernels, lds_limit, source
+
 SRC = "discrete_actor_test_population"
 QL_SRC = "ql_test_population"
 
 
-def _makefile_flags(obj):
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    flags = re.search(r"^FLAGS = (.*)$", text, re.M).group(1).replace("$(ARCH)", "gfx950").replace("$(EXTRA)", "").split()
-    for m in re.finditer(r"^(.*?): EXTRA \+= (.*)$", text, re.M):
-        if obj in m.group(1).split():
-            flags += m.group(2).split()
-    return [f for f in flags if f not in ("-fPIC", "-Wall", "-Wno-unused-parameter")]
-
-
-def _constant(src, name):
-    return int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
-
-
-def _largest_dynamic_lds(src):
+def _largest_dynamic_lds():
     """The entry's dynamic LDS (the layout at the top of the source file): two activation buffers [rows][W] and, with the shared LayerNorm,
-    [rows][H | 1], rows = min(T, DA_TB); the actor is staged only where all of it fits below the limit the source states.  Largest over the
+    [rows][H | 1], rows = min(T, TP_TB); the actor is staged only where all of it fits below the limit the source states.  Largest over the
     admitted envelope: the limit itself (a staged launch) or the widest unstaged shape."""
-    tb = _constant(src, "DA_TB")
-    limit = re.search(r"DA_LDS_LIMIT = (\d+) \* 1024 - (\d+);", src)
-    limit = int(limit.group(1)) * 1024 - int(limit.group(2))
+    tb, limit = episodes_per_workgroup(SRC), lds_limit(SRC, "DA")
     widest = max(4 * (2 * tb * ((H + 3) & ~3) + tb * (H | 1)) for H in (1, 511, 512))
     return limit, max(limit, widest)
 
 
-def _kernels(tmp_path, src):
-    out = str(tmp_path / (src + ".s"))
-    subprocess.check_call([HIPCC] + _makefile_flags("_build/%s.o" % src) + ["-I", os.path.join(ROOT, "include"), "-S", "--cuda-device-only",
-                                                                             os.path.join(CSRC, src + ".hip"), "-o", out],
-                          stderr=subprocess.DEVNULL)
-    kernels, cur = {}, None
-    for line in open(out).read().splitlines():
-        m = re.match(r"^(_ZN[A-Za-z0-9_]*):", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-        if cur is not None:
-            for key, pat in (("scratch", r"; ScratchSize: (\d+)"), ("lds", r"; LDSByteSize: (\d+)"), ("vgpr", r"; NumVgprs: (\d+)"), ("sgpr", r"; NumSgprs: (\d+)")):
-                m2 = re.search(pat, line)
-                if m2:
-                    cur[key] = int(m2.group(1))
-    return kernels
-
-
 def test_sources_are_part_of_the_library_build():
-    text = open(os.path.join(CSRC, "Makefile")).read()
+    text = source("Makefile")
     srcs = re.search(r"^SRCS = (.*)$", text, re.M).group(1).split()
     deps = re.search(r"^_build/%\.o: (.*)$", text, re.M).group(1).split()
     for s in (SRC, QL_SRC):
         assert s + ".hip" in srcs
-        src = open(os.path.join(CSRC, s + ".hip")).read()
+        src = source(s + ".hip")
         assert "getenv" not in src, "no environment knobs"
         assert "asm" not in src.replace("same", ""), "no inline assembly"
-    for header in ("lenv_td3d_actor.cuh", "lenv_ql_policy.cuh", "lenv_at_layer.cuh"):
+    for header in ("lenv_td3d_actor.cuh", "lenv_ql_policy.cuh", SHARED_HEADER):
         assert header in deps, header
     # the shared pieces live in the headers alone: the fused kernels include them and define none of them
-    fused = open(os.path.join(CSRC, "td3_discrete_inner_loop.hip")).read()
+    fused = source("td3_discrete_inner_loop.hip")
     assert '#include "lenv_td3d_actor.cuh"' in fused
     for name in ("float det_gumbel(", "float td3d_temperature(", "int argmax_first(", "void gumbel_softmax_row(", "void dmlp_off(", "STREAM_TD3D_GUMBEL_TEST ="):
-        assert name not in fused and name in open(os.path.join(CSRC, "lenv_td3d_actor.cuh")).read(), name
-        assert name not in open(os.path.join(CSRC, SRC + ".hip")).read(), name
-    ql = open(os.path.join(CSRC, "ql_rn_inner_loop.hip")).read()
+        assert name not in fused and name in source("lenv_td3d_actor.cuh"), name
+        assert name not in source(SRC + ".hip"), name
+    ql = source("ql_rn_inner_loop.hip")
     assert '#include "lenv_ql_policy.cuh"' in ql and "int ql_argmax_f32(" not in ql
-    assert "int ql_argmax_f32(" in open(os.path.join(CSRC, "lenv_ql_policy.cuh")).read()
+    assert "int ql_argmax_f32(" in source("lenv_ql_policy.cuh")
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 @pytest.mark.timeout(600)
 def test_discrete_actor_test_kernel_resources(tmp_path):
-    kernels = _kernels(tmp_path, SRC)
-    mine = {n: k for n, k in kernels.items() if "37discrete_actor_test_population_kernel" in n}
-    assert len(mine) == 6, sorted(kernels)                # three envs x (actor staged in LDS / read from global memory)
-    src = open(os.path.join(CSRC, SRC + ".hip")).read()
-    staged_dyn, dyn = _largest_dynamic_lds(src)
+    found = kernels(tmp_path, SRC)
+    mine = {n: k for n, k in found.items() if "37discrete_actor_test_population_kernel" in n}
+    assert len(mine) == 6, sorted(found)                # three envs x (actor staged in LDS / read from global memory)
+    src = source(SRC + ".hip")
+    staged_dyn, dyn = _largest_dynamic_lds()
     assert "__launch_bounds__(DNT, 4)" in src
     for name, k in sorted(mine.items()):
         print("%s: ScratchSize %s B/lane, static LDS %s B (+ at most %d B dynamic, %d B with a staged actor), %s VGPRs, %s SGPRs"
@@ -102,9 +67,9 @@ def test_discrete_actor_test_kernel_resources(tmp_path):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 @pytest.mark.timeout(600)
 def test_ql_test_kernel_resources(tmp_path):
-    kernels = _kernels(tmp_path, QL_SRC)
-    mine = {n: k for n, k in kernels.items() if "25ql_test_population_kernel" in n}
-    assert len(mine) == 1, sorted(kernels)
+    found = kernels(tmp_path, QL_SRC)
+    mine = {n: k for n, k in found.items() if "25ql_test_population_kernel" in n}
+    assert len(mine) == 1, sorted(found)
     for name, k in mine.items():
         print("%s: ScratchSize %s B/lane, static LDS %s B, %s VGPRs, %s SGPRs" % (name, k.get("scratch"), k.get("lds"), k.get("vgpr"), k.get("sgpr")))
         assert k.get("lds") == 0 and k.get("scratch") == 0
