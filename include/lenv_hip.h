@@ -44,9 +44,15 @@ enum { LENV_RNG_COUNTER = 0, LENV_RNG_TAPE = 1 };
 /* lenv_ddqn_cfg / lenv_td3_cfg `kernel_variant` bits (0 = the fastest kernel that takes the launch; the bits exist for A/B timing and for
  * the parity tests that hold the kernels against each other -- every variant produces the same bits):
  * NO_WAVECHAIN keeps the GEMM-queue kernel where a wave-chain kernel exists, GENERIC skips the shape-specialised instantiations,
- * TEAM_NARROW keeps whole forward items per lane in DDQN teams of three and more (default there: every item cut over the idle lanes). */
+ * TEAM_NARROW keeps whole forward items per lane in DDQN teams of three and more (default there: every item cut over the idle lanes),
+ * NO_EARLY_GRAD keeps the published CartPole DDQN shape on the pass-major forward deal with one workgroup barrier between the minibatch
+ * forward and the gradient (default there: chunk-aligned deal, a gradient chunk starts when the waves that hold its items are done). */
 enum { LENV_VARIANT_NO_WAVECHAIN = 1, LENV_VARIANT_GENERIC = 2, LENV_VARIANT_TEAM_NARROW = 4,
-       LENV_VARIANT_NO_DIRECT = 8 };   /* NO_DIRECT: the GEMM-queue kernels keep narrow nets on the product queue too (A/B timing, kernel-vs-kernel tests) */
+       LENV_VARIANT_NO_DIRECT = 8,     /* NO_DIRECT: the GEMM-queue kernels keep narrow nets on the product queue too (A/B timing, kernel-vs-kernel tests) */
+       LENV_VARIANT_NO_EARLY_GRAD = 16 };
+/* lenv_inner_out::status of a chain whose gradient wave gave up waiting for the "forward done" tags of its chunk's waves (the bounded
+ * wait of the early-gradient DDQN instantiation: an internal error, no correct run reaches the budget) */
+enum { LENV_STATUS_EARLY_GRAD_WAIT = -11 };
 
 /* models/model_utils.py:4-39 */
 typedef struct {
@@ -149,7 +155,7 @@ typedef struct {
 typedef struct {
     double *score;              /* [chains] statistics.mean(final test returns)   GTN_worker.py:209 */
     int64_t *stats;             /* [chains,4] episodes_run, train_steps, learn_steps, test_steps */
-    int32_t *status;            /* [chains] 0 ok, <0 internal error: -2..-5 tape underrun (eps / action / replay / reset), -6 replay index out of range, -7 unexpected LDS placement, -8 per-chain hyper-parameter outside cfg's maxima */
+    int32_t *status;            /* [chains] 0 ok, <0 internal error: -2..-5 tape underrun (eps / action / replay / reset), -6 replay index out of range, -7 unexpected LDS placement, -8 per-chain hyper-parameter outside cfg's maxima, -10 a team member gave up (team_size), -11 LENV_STATUS_EARLY_GRAD_WAIT */
     double *episode_test_mean;  /* [chains,train_episodes]  reward_list_train (NaN past early-out) */
     int32_t *episode_len;       /* [chains,train_episodes] */
     double *final_returns;      /* [chains,test_episodes] */
@@ -231,6 +237,14 @@ int64_t lenv_ddqn_se_lds_bytes(const lenv_ddqn_cfg *cfg /*HOST*/);
  * beyond the first eight waves of the workgroup, *parts = the number of pieces each of them is cut into over the hidden-unit pairs
  * (0 = plain layout: nothing spills, too much spills, the net is too narrow to cut, or the shared rows do not fit LDS). */
 int lenv_ddqn_se_forward_split(const lenv_ddqn_cfg *cfg /*HOST*/, int32_t *items, int32_t *parts);
+/* The chunk-aligned deal of the forward items of the early-gradient instantiation (diagnostic, host only, no device call): for a cfg that a
+ * counter-mode launch with one workgroup per chain and without a step trace runs on that instantiation (the published CartPole shape,
+ * kernel_variant without GENERIC / NO_EARLY_GRAD, VirtualEnv, test_mode 0) the return value is the number of gradient chunks n > 0,
+ * item_of_lane[t] (768 words, one per thread of the workgroup) = pass * batch_size + sample of the forward item whose output layer thread t
+ * runs -- a whole item on the first eight waves, the chain of a spilled item (always pass 2) on the lanes behind them -- or -1, and
+ * chunk_wave_mask[c] (n words) = bit w set when wave w = t / 64 holds an item of a sample of chunk c: the waves whose "forward done" tags
+ * the gradient of chunk c waits for.  Every other cfg: 0 = no early gradient, nothing is written.  Negative: LENV_ERR_*. */
+int lenv_ddqn_se_forward_deal(const lenv_ddqn_cfg *cfg /*HOST*/, int32_t *item_of_lane, int32_t *chunk_wave_mask);
 /* Workgroups per chain lenv_ddqn_se_inner_loop would use for a counter-mode launch of `chains` chains on the current device: > 1 when
  * the launch leaves enough CUs idle for every member of every chain to be resident (shards of a population spread over several
  * GPUs); the members deal the minibatch by whole gradient micro-chunks and meet once per learn step -- same bits for every team

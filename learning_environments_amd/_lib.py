@@ -11,7 +11,7 @@ ACT = {"identity": 0, "relu": 1, "leakyrelu": 2, "tanh": 3, "prelu": 4}
 ENV = {"CartPole-v0": 0, "Acrobot-v1": 1, "HalfCheetah-v3": 2, "MountainCar-v0": 3, "Pendulum-v0": 4, "MountainCarContinuous-v0": 5}
 RNG_COUNTER, RNG_TAPE = 0, 1
 ACTOR_TD3, ACTOR_PPO = 0, 1                      # LENV_ACTOR_*: the `kind` of lenv_actor_test_population (its cfg is a Td3Cfg / PpoCfg)
-VARIANT_NO_WAVECHAIN, VARIANT_GENERIC, VARIANT_TEAM_NARROW, VARIANT_NO_DIRECT = 1, 2, 4, 8     # lenv_ddqn_cfg / lenv_td3_cfg kernel_variant bits (A/B timing, kernel-vs-kernel parity tests)
+VARIANT_NO_WAVECHAIN, VARIANT_GENERIC, VARIANT_TEAM_NARROW, VARIANT_NO_DIRECT, VARIANT_NO_EARLY_GRAD = 1, 2, 4, 8, 16     # lenv_ddqn_cfg / lenv_td3_cfg kernel_variant bits (A/B timing, kernel-vs-kernel parity tests)
 TD3_RESUME_WORDS = 32                            # LENV_TD3_RESUME_WORDS: int64 words of a chain's record between two segment launches
 DUELING_RESUME_WORDS = 32                        # LENV_DUELING_RESUME_WORDS: the same for lenv_dueling_se_inner_loop_segment
 PPO_RESUME_WORDS = 32                            # LENV_PPO_RESUME_WORDS: the same for lenv_ppo_rn_inner_loop_segment
@@ -210,6 +210,7 @@ SIGNATURES = {
     "lenv_ddqn_se_lds_bytes": (_i64, [_P(DdqnCfg)]),
     "lenv_ddqn_se_team_size": (C.c_int, [_P(DdqnCfg), _i64]),
     "lenv_ddqn_se_forward_split": (C.c_int, [_P(DdqnCfg), _P(_i32), _P(_i32)]),
+    "lenv_ddqn_se_forward_deal": (C.c_int, [_P(DdqnCfg), _P(_i32), _P(_i32)]),
     "lenv_ddqn_se_inner_loop": (C.c_int, [_P(DdqnCfg)] + _DDQN_RUN),
     "lenv_dueling_se_workspace_bytes": (C.c_size_t, [_P(DdqnCfg), _i64]),
     "lenv_dueling_num_params": (_i64, [_P(DdqnCfg)]),

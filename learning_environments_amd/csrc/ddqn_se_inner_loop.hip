@@ -19,6 +19,8 @@
 // prefetch their minibatch rows; then the 3*B (sample, pass) forward items run one per thread (pass-major, dense),
 // one thread per sample forms the TD error, up to 12 waves back-propagate + reduce the batch gradient in
 // micro-chunks, one thread per parameter applies Adam + Polyak.
+// The published CartPole shape deals the forward items chunk-aligned and starts a gradient chunk when the waves that hold its items are
+// done (EGRAD / FwdDeal below): no workgroup barrier between forward and gradient.
 // Arithmetic order is the oracle's canonical order (oracle/lenv_oracle.h) => results are bit-identical.
 #include "lenv_device.cuh"
 
@@ -48,16 +50,22 @@ constexpr int MAX_PPT = 2;        // Q-net parameters owned per thread (P_agent 
 
 // Diagnostic build only (-DLENV_PHASE_TIMING): per-phase shader-clock totals of chain 0, never in the shipped library.
 #ifdef LENV_PHASE_TIMING
-__device__ unsigned long long g_phase_cycles[64];
-#define PT_DECL unsigned long long pt_last = __builtin_readcyclecounter(), pt_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pt_own[4] = {0, 0, 0, 0}
+__device__ unsigned long long g_phase_cycles[96];      // [64 + 2 w], [65 + 2 w]: wave w's chunk start / partials written
+#define PT_DECL unsigned long long pt_last = __builtin_readcyclecounter(), pt_step0 = pt_last, pt_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pt_own[6] = {0, 0, 0, 0, 0, 0}
 #define PT_MARK(i) do { unsigned long long pt_now = __builtin_readcyclecounter(); pt_acc[i] += pt_now - pt_last; pt_last = pt_now; } while (0)
 // own-work stamp: time since the last PT_MARK at which THIS wave reached the coming barrier (no reset)
 #define PT_OWN(i) do { pt_own[i] += __builtin_readcyclecounter() - pt_last; } while (0)
+// stamps measured from the top of the learning step: [4] the wave's gradient chunk starts (its inputs are there), [5] its partials are written;
+// [1] of a full-item wave of the early-gradient build: its "forward done" tag is stored
+#define PT_STEP0 do { pt_step0 = __builtin_readcyclecounter(); } while (0)
+#define PT_ABS(i) do { pt_own[i] += __builtin_readcyclecounter() - pt_step0; } while (0)
 #define PT_FLUSH(first, n) do { if (chain == 0) for (int pi = 0; pi < (n); ++pi) g_phase_cycles[(first) + pi] = pt_acc[pi]; } while (0)
 #else
 #define PT_DECL
 #define PT_MARK(i)
 #define PT_OWN(i)
+#define PT_STEP0
+#define PT_ABS(i)
 #define PT_FLUSH(first, n)
 #endif
 
@@ -123,6 +131,76 @@ constexpr InnerLayout make_inner_layout(int S, int A, int Hq, int Hse, int B, in
     }
     return a;
 }
+
+// EARLY GRADIENT (kernel template flag EGRAD: the published CartPole shape on one workgroup per chain).  With the pass-major deal
+// (item = pass * B + b, dense over the threads) every sample has an item on one of the waves that finish the minibatch forward last,
+// so no gradient chunk can start before all of them have: the interval ends in a workgroup barrier at which eight of twelve waves idle
+// for a fifth of it.  This deal is CHUNK-ALIGNED instead.  The nw - 4 full-item waves form two groups of `half` lanes:
+//   group A   all three passes of the first SA = split_L samples (whole chunks: split_L is a multiple of the chunk), pass-major;
+//   group B   passes 0 and 1 of the other SB = B - SA samples and pass 2 of the last SB - split_L of them, pass-major; what does not fit
+//             its lanes (3 B - split_L = 2 half, so exactly the lanes group A leaves free) goes to the tail of group A;
+//   spill     slot li (split layout: cut over the four last waves, its output chain on lane li behind the full-item waves) holds pass 2
+//             of sample SA + li -- a pass-2 item as before, only the sample behind a slot changes.
+// B = 199, chunk 17: A = chunks 0 .. 4 (255 items, lane 255 takes pass 2 of sample 198), B = chunks 5 .. 11, spill = pass 2 of chunks 5 .. 9.
+// Any bijection of (pass, sample) onto lanes leaves every arithmetic operation and its operands as they were: the bits do not change.
+// chunk_wave_mask[c] = the waves that hold an item of chunk c (the spilled items: the wave of their chain lane, which has seen all four
+// waves' activation rows); the wave that runs chunk c's gradient waits for exactly those waves' tags (FWD_DONE below) -- there is no
+// workgroup barrier between forward and gradient.  chunk_of_wave: group A's chunks on group A's waves and the first speculation wave,
+// group B's on its own waves and the two chain waves, the short last chunk on the env wave (which enters the gradient last).
+struct FwdDeal {
+    int ok, SA, SB, half, a0;          // a0: first lane of group A (0, or `half`: the groups' waves swapped -- which of them is the late one is a measurement)
+    int chunk_wave_mask[16], chunk_of_wave[16], wave_mask[16];      // wave_mask[w] = chunk_wave_mask[chunk_of_wave[w]]
+};
+#ifndef LENV_DDQN_EG_A_LATE
+#define LENV_DDQN_EG_A_LATE 0          // 1: group A on the second four waves (A/B builds)
+#endif
+#ifndef LENV_DDQN_EG_FWD_PRIO
+// s_setprio of a full-item wave from the top of its forward to its "forward done" tag: the waves still in their pair loop go before the
+// gradient waves beside them on the SIMD (0 = none: 2 115 instead of 2 138 evals/s, docs/notebook_ddqn_early_gradient.md)
+#define LENV_DDQN_EG_FWD_PRIO 1
+#endif
+constexpr bool fwd_deal_ok(const InnerLayout &L, int B, int nw)
+{
+    const int F = (nw - 4) * 64, half = F / 2;
+    return L.rc == LENV_OK && nw == 12 && L.split_D > 0 && L.split_L == 3 * B - F && L.split_L % L.chunk == 0 && 3 * L.split_L <= half &&
+           B - L.split_L >= L.split_L && L.n_chunks == nw;
+}
+// forward item of thread t as (pass << 16) | sample, -1 = none (only for a shape with fwd_deal_ok)
+constexpr int fwd_deal_item(const InnerLayout &L, int B, int nw, int a0, int t)
+{
+    const int F = (nw - 4) * 64, half = F / 2, SA = L.split_L, SB = B - SA;
+    if (t >= F) return t - F < L.split_L ? (2 << 16) | (SA + t - F) : -1;
+    int i = t - (half - a0);                                      // index in group B's order
+    if (t >= a0 && t < a0 + half) {
+        const int u = t - a0;
+        if (u < 3 * SA) { const int pass = (u >= SA ? 1 : 0) + (u >= 2 * SA ? 1 : 0); return (pass << 16) | (u - pass * SA); }
+        i = half + u - 3 * SA;
+    }
+    if (i < SB) return SA + i;
+    if (i < 2 * SB) return (1 << 16) | (SA + i - SB);
+    return SA + L.split_L + i - 2 * SB < B ? (2 << 16) | (SA + L.split_L + i - 2 * SB) : -1;
+}
+constexpr FwdDeal make_fwd_deal(const InnerLayout &L, int B, int nt, int nw, int a_late)
+{
+    FwdDeal d{};
+    if (!fwd_deal_ok(L, B, nw)) return d;
+    d.half = (nw - 4) * 32; d.a0 = a_late ? d.half : 0; d.SA = L.split_L; d.SB = B - L.split_L;
+    for (int t = 0; t < nt; ++t) {
+        const int it = fwd_deal_item(L, B, nw, d.a0, t);
+        if (it >= 0) d.chunk_wave_mask[(it & 0xffff) / L.chunk] |= 1 << (t >> 6);
+    }
+    // (nw == 12) chunk run by wave w when group A sits on waves 0 .. 3; with the groups swapped, so are the waves w and w ^ 4
+    constexpr int cow[12] = {0, 4, 1, 2, 6, 10, 7, 9, 5, 8, 3, 11};
+    for (int w = 0; w < nw; ++w) {
+        const int ww = (a_late && w < 8) ? w ^ 4 : w;
+        d.chunk_of_wave[ww] = cow[w];
+        d.wave_mask[ww] = d.chunk_wave_mask[cow[w]];
+    }
+    int seen = 0;
+    for (int w = 0; w < nw; ++w) seen |= 1 << d.chunk_of_wave[w];
+    d.ok = seen == (1 << nw) - 1;                                 // every chunk has its wave
+    return d;
+}
 // The published one-hidden-layer DDQN configurations of the reference, each with its own shape-specialised instantiation (SHAPE
 // template parameter of the kernel): env, S, A, Q-net width / activation, batch, SE width / activation, test episodes, max_steps.
 // chunk is the package's pick_grad_chunk value for the shape (the launch must carry the same one).
@@ -170,6 +248,44 @@ __device__ __forceinline__ void lds_flag_wait(const float *p, int tag)
 {
     while (*(volatile lds_int *)((lds_int *)const_cast<float *>(p)) != tag) __builtin_amdgcn_s_sleep(2);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// "Forward done" tags of the early-gradient instantiation (FwdDeal): word w of fwd_done (the twelve words of the 16-word cur_state block
+// that a four-dimensional state leaves free: the layout does not grow) holds the last learning step whose
+// forward results wave w has written (w < NW - 4: its items' qres / h rows / state and reward rows; NW - 4, NW - 3: the spilled items' qres).
+// THE RULE THAT MAKES EVERY WAIT ON A TAG FINITE: the store of a waited-for tag (these, and the env wave's ctrl[5]) is executed
+// unconditionally by its wave in every learning step, no data-dependent branch lies between the top of the step and that store, and the
+// tag is the monotonically increasing step number step_tag (a stale word never equals a later step's tag).  The waits are bounded all
+// the same: a protocol slip must not hang a CU.  They count their polls in a scalar register; a poll is an LDS round trip plus s_sleep 2,
+// 200 cycles and more, and the interval they cover is 11 k cycles, so 2^20 polls (2 * 10^8 cycles, 0.1 s) is four orders of magnitude
+// beyond any correct run.  A wave that gives up reports LENV_STATUS_EARLY_GRAD_WAIT, skips its chunk and never waits again.
+constexpr int FWD_DONE = 4;           // first tag word inside the cur_state block
+constexpr int EG_POLL_BUDGET = 1 << 20;
+// true when every wave of `mask` (bits 0 .. NW-1) has published `tag`; lane w < NW polls wave w's word
+__device__ __forceinline__ bool lds_tags_wait(const float *tags, unsigned mask, int tag, int lane)
+{
+    const volatile lds_int *p = (lds_int *)const_cast<float *>(tags) + (lane < NW ? lane : 0);
+    int polls = 0;                                                 // uniform: a scalar register
+    for (;;) {
+        const unsigned done = (unsigned)__builtin_amdgcn_ballot_w64(*p == tag);
+        if ((done & mask) == mask) break;
+        polls = __builtin_amdgcn_readfirstlane(polls + 1);         // (pins the count to a scalar register)
+        if (polls > EG_POLL_BUDGET) return false;
+        __builtin_amdgcn_s_sleep(2);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return true;
+}
+__device__ __forceinline__ bool lds_flag_wait_bounded(const float *p, int tag)
+{
+    int polls = 0;
+    while (__builtin_amdgcn_readfirstlane(*(volatile lds_int *)((lds_int *)const_cast<float *>(p))) != tag) {    // (uniform: the count stays scalar)
+        polls = __builtin_amdgcn_readfirstlane(polls + 1);         // (pins the count to a scalar register)
+        if (polls > EG_POLL_BUDGET) return false;
+        __builtin_amdgcn_s_sleep(2);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return true;
 }
 
 __device__ __forceinline__ void wave_sync()
@@ -343,10 +459,14 @@ __device__ __forceinline__ void real_env_obs(const double (&st)[4], float (&obs)
 // (fp64 state, TimeLimit at max_steps) and shapes the reward with the perturbed reward network theta (S -> se_hidden -> 1), whose phi(s') it keeps
 // for the next step; there is nothing to speculate on.  Its own instantiations (one workgroup per chain), so that the VirtualEnv builds carry none
 // of it.  Oracle: ddqn_se_chain_impl's reward_env branch.
-template <int ENV, int S, int A, int QACT, int PPT, int SHAPE = 0, bool TEAM = false, bool TWIDE = false, bool RENV = false>
+// EGRAD = the early-gradient form of the published CartPole shape on one workgroup per chain (FwdDeal above): chunk-aligned forward deal,
+// per-wave "forward done" tags instead of the barrier between forward and gradient.  kernel_variant NO_EARLY_GRAD selects the same shape's
+// instantiation without it (pass-major deal, barrier B2), as do all TEAM launches.
+template <int ENV, int S, int A, int QACT, int PPT, int SHAPE = 0, bool TEAM = false, bool TWIDE = false, bool RENV = false, bool EGRAD = false>
 __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
 {
     static_assert(!TWIDE || TEAM, "TWIDE is a TEAM layout");
+    static_assert(!EGRAD || (SHAPE == 1 && !TEAM && !RENV), "early gradient: the published CartPole shape, one workgroup per chain");
     static_assert(!RENV || (SHAPE == 0 && !TEAM), "RewardEnv / real-env training: generic one-workgroup instantiations only");
     extern __shared__ __align__(16) float lds[];
     const lenv_ddqn_cfg &cfg = a.cfg;
@@ -356,6 +476,8 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
     static_assert(!FIXED || (SPEC.env == ENV && SPEC.S == S && SPEC.A == A && SPEC.q_act == QACT), "shape table entry vs instantiation");
     constexpr InnerLayout LC = make_inner_layout(S, A, FIX_HQ, FIX_HSE, FIX_B, FIX_T, FIX_CHUNK, NT, NW, MAX_PPT, MAX_B);
     static_assert(!FIXED || LC.rc == LENV_OK, "the fixed shape must fit");
+    constexpr FwdDeal FD = make_fwd_deal(LC, FIX_B, NT, NW, LENV_DDQN_EG_A_LATE);
+    static_assert(!EGRAD || FD.ok, "the early-gradient deal needs a chunk-aligned split");
 #define LV(f) (FIXED ? LC.f : a.L.f)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // TEAM: block x + 8 k is member k % G of chain 8 (k / G) + x -- consecutive blocks go to consecutive XCDs, so a chain's members share one
@@ -387,6 +509,8 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
     float *wscr = lds + LV(o_wscr) + wave * ((Hq + 63) & ~63);
     float *se_hw = se_h + (wave & 1) * 3 * HseP;      // per-wave SE hidden scratch (waves NW-2 / NW-1)
     float *cand = lds + LV(o_cand), *cur_state = lds + LV(o_cur_state);
+    static_assert(!EGRAD || (S <= FWD_DONE && FWD_DONE + NW <= 16), "the tags share the cur_state block with the state");
+    [[maybe_unused]] float *fwd_done = cur_state + FWD_DONE;    // EGRAD: the waves' "forward done" tags
     float *hB = lds + LV(o_hB), *sB = lds + LV(o_sB), *rda = lds + LV(o_rda), *dqB = lds + LV(o_dqB);
     float *qres = lds + LV(o_qres), *part = lds + LV(o_part), *newrow = lds + LV(o_newrow);
     float *ctrl = lds + LV(o_ctrl);            // [0..1] done (double buffered by step parity), [2] break, [8..] wave step counts (every use is barrier-separated)
@@ -463,6 +587,7 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
         }
     }
     if (tid < 8 + NW) ctrl[tid] = 0.0f;
+    if constexpr (EGRAD) { if (tid < NW) fwd_done[tid] = 0.0f; }
     // GB2_LANE (the published CartPole shape: 57 hidden units in rows of 58 words): the output-bias gradient gb2[a] = sum_b dm_b[a] is the
     // output-weight gradient of a virtual hidden unit whose activation is 1.0 -- fma(dm, 1.0, acc) and acc + dm round the same sum once.  The
     // idle lane 57 of every gradient wave plays that unit (the pad word of every h row holds 1.0 from here on; the forward never writes it:
@@ -534,8 +659,11 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
     const int split_li = wide ? wide_item % Bm : (h_lane ? split_u % SPLIT_L : 0), split_part = wide ? (h_lane ? tid / WIDE_L : 0) : (h_lane ? split_u / SPLIT_L : 0);
     const bool chain_lane = !wide && split && split_u >= 0 && tid < 3 * Bm;
     const bool split_wave = !wide && split && wave >= SPLIT_W0 && wave < SPLIT_W0 + 4;
-    const int fwd_pass = wide ? wide_item / Bm : ((split && split_u >= 0) ? 2 : (tid < Bm ? 0 : (tid < 2 * Bm ? 1 : 2)));
-    const int fwd_b = wide ? mb0 + split_li : ((split && split_u >= 0) ? mb0 + SPLIT_T0 + split_li - 2 * Bm : mb0 + tid - fwd_pass * Bm);
+    // EGRAD: the chunk-aligned deal instead (FwdDeal); a spill slot keeps its lanes and its pass, only the sample behind it changes
+    const int eg_item = EGRAD ? fwd_deal_item(LC, FIX_B, NW, FD.a0, tid < SPLIT_T0 ? tid : SPLIT_T0 + split_li) : 0;
+    const int fwd_pass = EGRAD ? eg_item >> 16 : (wide ? wide_item / Bm : ((split && split_u >= 0) ? 2 : (tid < Bm ? 0 : (tid < 2 * Bm ? 1 : 2))));
+    const int fwd_b = EGRAD ? eg_item & 0xffff
+                            : (wide ? mb0 + split_li : ((split && split_u >= 0) ? mb0 + SPLIT_T0 + split_li - 2 * Bm : mb0 + tid - fwd_pass * Bm));
     const bool full_item = !wide && (split ? tid < SPLIT_T0 : tid < 3 * Bm);  // runs all pairs of its item, output layer included
     const bool fwd_active = full_item || h_lane;          // samples a replay row
     // WIDE: the LDS row that holds the activations of (pass, sample index bi inside the member's share)
@@ -764,6 +892,14 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
         for (int m = 1; m < G; ++m) same = same && __hip_atomic_load(team_bar + 1 + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == x0;
         team_same_xcd = same;
     }
+    // EGRAD: this wave's gradient chunk and the waves whose tags it waits for (FwdDeal: compile-time tables, selected by the wave number)
+    [[maybe_unused]] int eg_chunk = 0;
+    [[maybe_unused]] unsigned eg_mask = 0u;
+    [[maybe_unused]] bool eg_dead = false;                      // a bounded wait ran out (LENV_STATUS_EARLY_GRAD_WAIT): no more waiting
+    if constexpr (EGRAD) {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) if (wave == w) { eg_chunk = FD.chunk_of_wave[w]; eg_mask = (unsigned)FD.wave_mask[w]; }
+    }
     PT_DECL;
     for (int episode = 0; episode < cfg.train_episodes; ++episode) {
         if (budgeted && (int64_t)train_steps + test_steps > cfg.step_budget) { timed_out_at = episode; break; }   // uniform
@@ -803,9 +939,11 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
             // row being appended, and the speculation wave (needs the new state), wait for that flag.
             const int step_tag = train_steps + 1;
             PT_MARK(9);
+            PT_STEP0;
             // split layout: what the four third waves do up to the spilled items' output layers is the critical path of the forward
             // interval (the SIMDs' arbiters otherwise serve the older waves first and these rows arrive last)
             if (split_wave && learning) __builtin_amdgcn_s_setprio(3);
+            if constexpr (EGRAD && LENV_DDQN_EG_FWD_PRIO > 0) { if (wave < SPLIT_W0 && learning) __builtin_amdgcn_s_setprio(LENV_DDQN_EG_FWD_PRIO); }
             if (wave == ENV_WAVE) {
                 // ---- select_train_action (DDQN.py:97-104) ----
                 if (!nx_valid) draw_action(train_steps);
@@ -1015,6 +1153,9 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                         if (jp < npairs) finish(pa, jp, 2 * jp + 1 < Hqf, F{});
 #pragma unroll
                         for (int aa = 0; aa < A; ++aa) qres[(fwd_pass * MAX_B + fwd_b) * A + aa] = q[aa] + W[npairs * PR + aa];
+                        // EGRAD: everything this full-item wave owes the gradient is written (a wave's LDS operations execute in order)
+                        if constexpr (EGRAD) { if (lane == 0) lds_flag_store(fwd_done + wave, step_tag); PT_ABS(1); }
+                        if constexpr (EGRAD && LENV_DDQN_EG_FWD_PRIO > 0) { if (wave < SPLIT_W0) __builtin_amdgcn_s_setprio(0); }   // (scalar guard: s_setprio ignores EXEC)
                     } else if (wide) {
                         // WIDE h-only lane: `len` pairs from p0 on, the same trip count in every lane and no condition in the loop (a pair is
                         // always stored whole: for an odd width the second word of the last pair is the row's pad word; loads past the last
@@ -1117,8 +1258,10 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                             }
                         }
 #pragma unroll
-                        for (int aa = 0; aa < A; ++aa) qres[(2 * MAX_B + (mb0 + tid - 2 * Bm)) * A + aa] = q[aa] + q_tgt[npairs * PR + aa];
+                        for (int aa = 0; aa < A; ++aa) qres[(2 * MAX_B + (EGRAD ? FD.SA + split_u : mb0 + tid - 2 * Bm)) * A + aa] = q[aa] + q_tgt[npairs * PR + aa];   // (EGRAD: slot split_u holds sample SA + split_u)
                     }
+                    // EGRAD: the spilled items' results of this chain wave are written (by the wave, whether or not a lane had a chain)
+                    if constexpr (EGRAD) { if (lane == 0) lds_flag_store(fwd_done + wave, step_tag); }
                 }
                 if (split_wave) __builtin_amdgcn_s_setprio(0);
                 if (wide) {
@@ -1207,8 +1350,15 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                   }
                 }
                 PT_OWN(0);
-                __syncthreads();                               // B2
+                if constexpr (!EGRAD) __syncthreads();         // B2 (EGRAD: none -- a chunk waits for the tags of the waves that hold its items)
                 PT_MARK(3);
+                // EGRAD: the appended row's LDS copy is the env wave's; without B2 a wave that needs it waits for that wave's tag of this step
+                // (as the forward does at its top) -- bounded, like the chunk's wait below
+                [[maybe_unused]] bool eg_go = !eg_dead;
+                if constexpr (EGRAD) {
+                    if (eg_go && wave != ENV_WAVE && __builtin_amdgcn_ballot_w64(fwd_active && my_idx == new_pos) != 0)
+                        eg_go = lds_flag_wait_bounded(ctrl + 5, step_tag);
+                }
                 if (fwd_active && my_idx == new_pos) {             // next step samples the row appended in this one: the LDS copy is still there
 #pragma unroll
                     for (int v = 0; v < RS / 4; ++v) rowv[v] = *reinterpret_cast<const float4 *>(newrow + 4 * v);
@@ -1217,8 +1367,14 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                 // lane = hidden unit j.  Per sample (canonical order, oracle orc_ddqn_learn): da = dq*W2[a_b][j] (as a sum over
                 // the action masks, exactly one term non-zero), dz = act'(h)*da, gW1[j][:] += dz*s, gb1[j] += dz,
                 // gW2[a][j] += dqm[a]*h, gb2[a] += dqm[a] -- adding an exact zero leaves the other actions' sums untouched.
-                if (wave < mc1 - mc0) {
-                    const int cg = mc0 + wave;                         // (TEAM: this member's chunks; else mc0 = 0, mc1 = n_chunks)
+                // EGRAD: every wave runs the chunk FwdDeal gives it, as soon as the waves that hold the chunk's items have published this step's tag
+                if constexpr (EGRAD) {
+                    if (eg_go) eg_go = lds_tags_wait(fwd_done, eg_mask, step_tag, lane);
+                    if (!eg_go) { eg_dead = true; status = LENV_STATUS_EARLY_GRAD_WAIT; }
+                }
+                PT_ABS(4);
+                if (EGRAD ? eg_go : wave < mc1 - mc0) {
+                    const int cg = EGRAD ? eg_chunk : mc0 + wave;      // (TEAM: this member's chunks; else mc0 = 0, mc1 = n_chunks)
                     const int b0 = cg * LV(chunk), b1 = (b0 + LV(chunk) < B) ? b0 + LV(chunk) : B;
                     float *pc = part + cg * P;
                     // TEAM: the chunk's partials also go to the chain's exchange buffer (copy of this learn step's parity) for the other members
@@ -1354,6 +1510,7 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                     }
                 }
                 PT_OWN(2);
+                PT_ABS(5);
                 if constexpr (TEAM) {
                     // The other members' chunks, into the LDS rows the Adam phase sums in chunk order: every thread polls ITS granules
                     // (loads that go to the XCD's L2, which the members share and their stores write through to) until they carry this step's
@@ -1559,6 +1716,7 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
     if (tid == ENV_WAVE * 64) { if (chain == 0) { g_phase_cycles[10] = pt_acc[0]; g_phase_cycles[11] = pt_acc[1]; } }
     if (chain == 0 && lane == 0) {       // own-work stamps (forward, TD, gradient, Adam) of every wave
         for (int pi = 0; pi < 4; ++pi) g_phase_cycles[12 + 4 * wave + pi] = pt_own[pi];
+        g_phase_cycles[64 + 2 * wave] = pt_own[4]; g_phase_cycles[65 + 2 * wave] = pt_own[5];
     }
 #endif
     if (tid == 0) {
@@ -1712,7 +1870,7 @@ static int inner_check(const lenv_ddqn_cfg *cfg)
 #ifdef LENV_PHASE_TIMING
 extern "C" int lenv_debug_phase_cycles(unsigned long long *host_out)
 {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(lenv::g_phase_cycles), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -4;
+    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(lenv::g_phase_cycles), sizeof(unsigned long long) * 96) == hipSuccess ? 0 : -4;
 }
 #endif
 
@@ -1737,6 +1895,29 @@ extern "C" int lenv_ddqn_se_forward_split(const lenv_ddqn_cfg *cfg, int32_t *ite
     if (rc != LENV_OK) return rc;
     *items = a.L.split_L; *parts = a.L.split_D;
     return LENV_OK;
+}
+
+// The early-gradient instantiation's deal (FwdDeal) for the cfgs that a one-workgroup counter-mode launch runs on it; host only
+extern "C" int lenv_ddqn_se_forward_deal(const lenv_ddqn_cfg *cfg, int32_t *item_of_lane, int32_t *chunk_wave_mask)
+{
+    if (!cfg || !item_of_lane || !chunk_wave_mask) return LENV_ERR_INVALID;
+    int rc = inner_check(cfg);
+    if (rc != LENV_OK) return rc;
+    InnerArgs a;
+    rc = inner_layout(cfg, a);
+    if (rc != LENV_OK) return rc;
+    if (cfg->rng_mode != LENV_RNG_COUNTER || cfg_disables_fixed_shape(cfg) || (cfg->kernel_variant & LENV_VARIANT_NO_EARLY_GRAD) || published_shape(cfg, a.L) != 1)
+        return 0;
+    constexpr ShapeSpec sp = kShapes[1];
+    constexpr InnerLayout LC = make_inner_layout(sp.S, sp.A, sp.Hq, sp.Hse, sp.B, sp.T, sp.chunk, NT, NW, MAX_PPT, MAX_B);
+    constexpr FwdDeal FD = make_fwd_deal(LC, sp.B, NT, NW, LENV_DDQN_EG_A_LATE);
+    static_assert(FD.ok, "the published CartPole shape has an early-gradient deal");
+    for (int t = 0; t < NT; ++t) {
+        const int it = fwd_deal_item(LC, sp.B, NW, FD.a0, t);
+        item_of_lane[t] = it < 0 ? -1 : (it >> 16) * sp.B + (it & 0xffff);
+    }
+    for (int c = 0; c < LC.n_chunks; ++c) chunk_wave_mask[c] = FD.chunk_wave_mask[c];
+    return LC.n_chunks;
 }
 
 // floats per chain of the team exchange area: 16 barrier words + two copies (learn-step parity) of the chunk partials as 8-byte
@@ -1892,7 +2073,8 @@ extern "C" int lenv_ddqn_se_inner_loop(const lenv_ddqn_cfg *cfg, const float *th
     InnerKern kern = cfg->synthetic_env_type == 1 ? ddqn_generic_kernel<false, false, true>(cfg, a.L) : ddqn_generic_kernel<false, false, false>(cfg, a.L);
     if (cfg->rng_mode == LENV_RNG_COUNTER && !out->trace_action && !cfg_disables_fixed_shape(cfg)) {
         switch (published_shape(cfg, a.L)) {
-        case 1: kern = ddqn_se_inner_kernel<LENV_ENV_CARTPOLE, 4, 2, LENV_ACT_TANH, 1, 1>; break;
+        case 1: kern = (cfg->kernel_variant & LENV_VARIANT_NO_EARLY_GRAD) ? ddqn_se_inner_kernel<LENV_ENV_CARTPOLE, 4, 2, LENV_ACT_TANH, 1, 1>
+                                                                        : ddqn_se_inner_kernel<LENV_ENV_CARTPOLE, 4, 2, LENV_ACT_TANH, 1, 1, false, false, false, true>; break;
         case 2: kern = ddqn_se_inner_kernel<LENV_ENV_CARTPOLE, 4, 2, LENV_ACT_RELU, 1, 2>; break;
         case 3: kern = ddqn_se_inner_kernel<LENV_ENV_ACROBOT, 6, 3, LENV_ACT_LEAKYRELU, 2, 3>; break;
         default: break;

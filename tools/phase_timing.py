@@ -31,7 +31,7 @@ master.step(0)
 torch.cuda.synchronize()
 import time
 t0 = time.time(); master.step(1); torch.cuda.synchronize(); dt = time.time() - t0
-buf = (C.c_ulonglong * 64)()
+buf = (C.c_ulonglong * 96)()                       # (a build from before the chunk stamps fills 64)
 _lib.lib().lenv_debug_phase_cycles.argtypes = [C.POINTER(C.c_ulonglong)]
 assert _lib.lib().lenv_debug_phase_cycles(buf) == 0
 names = ["(unused)", "(unused)", "phaseA+wait(B1)", "forward(B2)", "td-error(B3)", "grad-reduce(B4)", "adam(B5)", "test", "-", "loop-overhead",
@@ -45,4 +45,9 @@ print("own-work cycles before each barrier (forward | split layout: rows written
 steps = max(1, int(master.inner.stats[0][2]))
 for slot, w in enumerate(range(12)):
     print("  wave %2d: " % w + " | ".join("%7.0f" % (buf[12 + 4 * slot + i] / steps) for i in range(4)))
+if any(buf[64:96]):
+    print("cycles from the top of the learn step (forward-done tag stored (full-item waves of the early-gradient build) | gradient chunk starts | partials written):")
+    for w in range(12):
+        tag = buf[12 + 4 * w + 1] / steps if w < 8 else 0
+        print("  wave %2d: %7.0f | %7.0f | %7.0f" % (w, tag, buf[64 + 2 * w] / steps, buf[65 + 2 * w] / steps))
 print("phase totals per learn step: " + ", ".join("%s %.0f" % (names[i], buf[i] / steps) for i in (2, 3, 4, 5, 6)))
