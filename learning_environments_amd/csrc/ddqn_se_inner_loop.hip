@@ -159,6 +159,25 @@ struct FwdDeal {
 // gradient waves beside them on the SIMD (0 = none: 2 115 instead of 2 138 evals/s, docs/notebook_ddqn_early_gradient.md)
 #define LENV_DDQN_EG_FWD_PRIO 1
 #endif
+#ifndef LENV_DDQN_EG_POLL_SLEEP
+#define LENV_DDQN_EG_POLL_SLEEP 2      // s_sleep between two polls of the "forward done" tags (0 = none; A/B builds)
+#endif
+#ifndef LENV_DDQN_GRAD_PIPE
+// the one-workgroup instantiations of the published CartPole shape keep two sample groups' LDS reads of a gradient chunk in flight
+// (0 = the loop every other instantiation runs, for A/B builds; docs/notebook_ddqn_grad_pipeline.md)
+#define LENV_DDQN_GRAD_PIPE 1
+#endif
+#ifndef LENV_DDQN_GRAD_PIPE_GRP
+// samples per group: 3 (17 = 3 + 3 + 3 + 3 + 3 + 2; two sets of 21 registers, the kernel stays a dozen VGPRs under its cap of 168) or
+// 4 (17 = 4 + 4 + 4 + 4 + 1; two sets of 28: at the cap, and the same schedule then spills 24-44 B -- docs/notebook_ddqn_grad_pipeline.md)
+#define LENV_DDQN_GRAD_PIPE_GRP 3
+#endif
+// the sample groups of a chunk at B = 199 in chunks of 17: the twelve samples every chunk has are GP_NS groups of GP_GRP, the five more of a
+// full chunk follow in the same pipeline (GP_NF groups in all); group k is samples gp_first(k) .. gp_first(k) + gp_size(k) - 1 of the chunk
+constexpr int GP_GRP = LENV_DDQN_GRAD_PIPE_GRP, GP_NS = 12 / GP_GRP, GP_NF = (17 + GP_GRP - 1) / GP_GRP, GP_MAXN = GP_GRP;
+static_assert(GP_GRP == 3 || GP_GRP == 4, "groups of three or four samples");
+constexpr int gp_first(int k) { return k * GP_GRP; }
+constexpr int gp_size(int k) { return 17 - k * GP_GRP < GP_GRP ? 17 - k * GP_GRP : GP_GRP; }
 constexpr bool fwd_deal_ok(const InnerLayout &L, int B, int nw)
 {
     const int F = (nw - 4) * 64, half = F / 2;
@@ -271,7 +290,9 @@ __device__ __forceinline__ bool lds_tags_wait(const float *tags, unsigned mask, 
         if ((done & mask) == mask) break;
         polls = __builtin_amdgcn_readfirstlane(polls + 1);         // (pins the count to a scalar register)
         if (polls > EG_POLL_BUDGET) return false;
-        __builtin_amdgcn_s_sleep(2);
+#if LENV_DDQN_EG_POLL_SLEEP > 0
+        __builtin_amdgcn_s_sleep(LENV_DDQN_EG_POLL_SLEEP);
+#endif
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     return true;
@@ -420,10 +441,11 @@ __device__ __forceinline__ int wave_q_argmax(const float *W, const float *W2rows
     return arg;
 }
 
-template <int ENV>
+// PIN_COEF: the sine / cosine polynomials' coefficients are made where they are used (det_coef), not carried in registers through the run
+template <int ENV, bool PIN_COEF = false>
 __device__ __forceinline__ void real_env_step(double (&st)[4], int action, double &rew, int &done)
 {
-    if constexpr (ENV == LENV_ENV_CARTPOLE) cartpole_step(st, action, rew, done);
+    if constexpr (ENV == LENV_ENV_CARTPOLE) cartpole_step<PIN_COEF>(st, action, rew, done);
     else acrobot_step(st, action, rew, done);
 }
 
@@ -594,6 +616,14 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
     // the last pair stores its first word only), and the per-sample packed add that every lane spent on gb2 is gone from the loop.
     constexpr bool GB2_LANE = SHAPE == 1 && !TWIDE && A == 2 && (FIX_HQ & 1) == 1 && FIX_HQ < 64;
     if constexpr (GB2_LANE) { for (int b = tid; b < B; b += NT) hB[b * HP + FIX_HQ] = 1.0f; }
+    // GPIPE (the same shape on one workgroup per chain): the sample loop of a gradient chunk is written out for the shape's literal chunk
+    // sizes, 17 and 12, in groups of GP_GRP samples with the LDS reads of group g + 1 issued before the arithmetic of group g (see there)
+    constexpr bool GPIPE = LENV_DDQN_GRAD_PIPE != 0 && SHAPE == 1 && !TEAM && !TWIDE;
+    static_assert(!GPIPE || (GB2_LANE && S == 4 && FIX_CHUNK == 17 && FIX_B % FIX_CHUNK == 12 && 4 * LC.HP <= 255),
+                  "the written-out gradient groups are those of B = 199 in chunks of 17, h rows within the ds_read2 offset range");
+    // (the short last chunk requests one group behind its twelve samples and drops it: those rows must lie inside the workgroup's LDS)
+    static_assert(!GPIPE || (LC.o_hB + (FIX_B + GP_GRP) * LC.HP <= LC.lds_floats && LC.o_sB + (FIX_B + GP_GRP) * 4 <= LC.lds_floats
+                             && LC.o_dqB + (FIX_B + GP_GRP) * 4 <= LC.lds_floats), "the dropped group's rows");
     for (int i = tid; i < LV(n_chunks4) * P; i += NT) part[i] = 0.0f;  // padding chunk slots stay +0 (see the Adam phase)
     __syncthreads();
 
@@ -784,7 +814,7 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                 real_env_obs<ENV, S>(st, obs);
                 const int act = wave_q_argmax<S, A, PR, QACT>(q_onl, q_w2, HqP, obs, wscr, Hq, cfg.q_prelu, lane, tanh_tab, tl);
                 double rew; int done;
-                real_env_step<ENV>(st, act, rew, done);
+                real_env_step<ENV, GPIPE>(st, act, rew, done);     // (GPIPE: twenty registers back for the gradient's second register set)
                 ep_reward = ep_reward + (float)rew;
                 ++my_steps; ++ep_steps;
                 if (done) break;
@@ -1382,10 +1412,65 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                     // step's value -- the hand-off needs no fence and no separate flag
                     float2 *xg = TEAM ? reinterpret_cast<float2 *>(a.team_ws + chain * a.team_stride + 16) + ((int64_t)(learn_it & 1) * LV(n_chunks4) + cg) * P : nullptr;
                     const float xtag = __int_as_float(learn_it + 1);
+                    // GPIPE: lane = hidden unit for the whole chunk (Hq < 64), the samples in the groups of gp_first / gp_size above.  Two
+                    // register sets take the groups alternately -- no set is ever copied into the other -- and a group's reads are issued
+                    // before the arithmetic of the group ahead of it, so the waits in between are counted, never lgkmcnt(0) with a group
+                    // outstanding.  The rows are addressed as integers in the LDS address space (the dynamic LDS starts at 0, checked at
+                    // the kernel's top) behind a register the compiler cannot see through: a group's reads then differ in their immediate
+                    // offsets only, and the h column (rows HP words apart) and the 16-byte dq rows pair up into ds_read2_b32 / ds_read2_b64
+                    // -- seven reads per group of three, eight per group of four; lgkmcnt counts to 15.
+                    // What does not depend on the TD error -- the lane's output weights and the first group's h and state rows -- is
+                    // requested HERE, in the round trip of the TD error's own reads; only the dq rows wait for the store and the fence.
+                    typedef __attribute__((address_space(3))) const float lds_cf;
+                    typedef __attribute__((address_space(3))) const v2f lds_cv2;
+                    typedef float gp_f4 __attribute__((ext_vector_type(4)));
+                    typedef __attribute__((address_space(3))) const gp_f4 lds_cf4;
+                    [[maybe_unused]] float gp_h[2][GP_MAXN], gp_s[2][GP_MAXN][SP];
+                    [[maybe_unused]] v2f gp_d[2][GP_MAXN], gp_w2 = {0.0f, 0.0f};
+                    [[maybe_unused]] lds_cf *gp_dp = nullptr, *gp_sp = nullptr;
+                    [[maybe_unused]] uint32_t gp_ha = 0u;          // the h word of the first sample of the next group to request (they go in order)
+                    // group k's h column and state rows / its dq rows, into register set k & 1.  The h address moves on with the groups, again
+                    // behind an empty asm: offsets from the chunk's first row leave the ds_read2 range after eight samples, and the address
+                    // registers the compiler then makes inside a request are taken from the words just requested -- a wait for them,
+                    // lgkmcnt(0).  It is moved where registers are free: behind the arithmetic of the group before (gp_run).
+                    [[maybe_unused]] auto gp_issue_hs = [&](auto k_tag) {
+                        constexpr int K = decltype(k_tag)::value, N = gp_size(K), O = gp_first(K);
+                        lds_cf *hp = reinterpret_cast<lds_cf *>(static_cast<uintptr_t>(gp_ha));
+#pragma unroll
+                        for (int u = 0; u < N; ++u) gp_h[K & 1][u] = hp[u * LC.HP];
+#pragma unroll
+                        for (int u = 0; u < N; ++u) {
+                            const gp_f4 f = *reinterpret_cast<lds_cf4 *>(gp_sp + SP * (O + u));
+                            gp_s[K & 1][u][0] = f.x; gp_s[K & 1][u][1] = f.y; gp_s[K & 1][u][2] = f.z; gp_s[K & 1][u][3] = f.w;
+                        }
+                    };
+                    [[maybe_unused]] auto gp_issue_d = [&](auto k_tag) {
+                        constexpr int K = decltype(k_tag)::value, N = gp_size(K), O = gp_first(K);
+#pragma unroll
+                        for (int u = 0; u < N; ++u) gp_d[K & 1][u] = *reinterpret_cast<lds_cv2 *>(gp_dp + 4 * (O + u));
+                    };
+                    // (td_lane: the lane number behind an empty asm -- a wave's chunk never changes, and the per-lane addresses of this block
+                    // would otherwise each sit in a register of their own through the whole learn step; formed here they cost an add apiece)
+                    [[maybe_unused]] int td_lane = lane;
+                    if constexpr (GPIPE) {
+                        asm volatile("" : "+v"(td_lane));
+                        const bool jv = td_lane < Hq;
+                        uint32_t ha = 4u * (uint32_t)(LC.o_hB + b0 * LC.HP + ((jv || td_lane == Hq) ? td_lane : 0));
+                        uint32_t da = 4u * (uint32_t)(LC.o_dqB + 4 * b0), sa = 4u * (uint32_t)(LC.o_sB + SP * b0);
+                        uint32_t wa = 4u * (uint32_t)(LC.o_q_onl + ((jv ? td_lane : 0) >> 1) * PR + OW2 + (td_lane & 1) * A);
+                        asm volatile("" : "+v"(ha), "+v"(da), "+v"(sa));
+                        gp_ha = ha;
+                        gp_dp = reinterpret_cast<lds_cf *>(static_cast<uintptr_t>(da));
+                        gp_sp = reinterpret_cast<lds_cf *>(static_cast<uintptr_t>(sa));
+                        gp_w2 = *reinterpret_cast<lds_cv2 *>(static_cast<uintptr_t>(wa));
+                        gp_issue_hs(std::integral_constant<int, 0>{});
+                        gp_ha += 4u * (uint32_t)(gp_size(0) * LC.HP);
+                        asm volatile("" : "+v"(gp_ha));
+                    }
                     // TD target and dLoss/dQ(s,a) of the chunk's own samples (DDQN.py:82-86; mse_loss backward = 2/B * diff), one
                     // lane per sample: nobody else reads these rows, so the chunk goes on behind a wave-level fence -- no
                     // workgroup barrier between the TD error and the gradient
-                    for (int b = b0 + lane; b < b1; b += 64) {
+                    for (int b = b0 + (GPIPE ? td_lane : lane); b < b1; b += 64) {
                         const float g32 = a.f_gamma, norm = a.f_norm;
                         // every LDS word the sample needs is requested before the first is used: one round trip, not three
                         // (reward/done/action -> argmax row -> the two selected entries); the selections are register moves
@@ -1409,13 +1494,18 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                         *reinterpret_cast<float4 *>(dqB + 4 * b) = dm;
                     }
                     wave_sync();
-                    for (int j = lane; j < ((Hq + 63) & ~63); j += 64) {
+                    for (int j = lane; j < (GPIPE ? 64 : ((Hq + 63) & ~63)); j += 64) {
                         const bool jv = j < Hq;
                         float gW1[S], gW2[A], gb2[A], w2j[A], gb1 = 0.0f;
 #pragma unroll
                         for (int i = 0; i < S; ++i) gW1[i] = 0.0f;
+                        if constexpr (GPIPE) {
+#pragma unroll
+                            for (int aa = 0; aa < A; ++aa) { gW2[aa] = 0.0f; gb2[aa] = 0.0f; w2j[aa] = jv ? gp_w2[aa] : 0.0f; }
+                        } else {
 #pragma unroll
                         for (int aa = 0; aa < A; ++aa) { gW2[aa] = 0.0f; gb2[aa] = 0.0f; w2j[aa] = jv ? q_onl[(j >> 1) * PR + OW2 + (j & 1) * A + aa] : 0.0f; }
+                        }
                         // one sample: everything in canonical order (oracle orc_ddqn_learn)
                         auto accumulate = [&](float h, const float4 dm4, const float (&sv)[SP]) {
                             const float dm[3] = {dm4.x, dm4.y, dm4.z};
@@ -1456,6 +1546,41 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                         // running pointers (one add per round each): h column of this lane, dq rows and state rows of the chunk
                         // (vzero: a zero the compiler cannot see through -- it keeps the two wave-uniform row pointers in VGPRs, so a
                         // group's reads differ in their immediate offsets only instead of each getting its own s_add + v_mov)
+                        if constexpr (GPIPE) {
+                            // groups k .. stop - 1 of a chunk of n_groups: request group k + 1, then group k's arithmetic.  The scheduling
+                            // barriers keep the compiler from moving a group's reads behind the arithmetic they are to overlap.  The second word of a
+                            // ds_read2_b32 lands in an odd register and the packed gW2 update wants h in an even one: that move is written out
+                            // at the head of the arithmetic -- the compiler's own copy sits right behind the read and waits for it there.
+                            auto gp_run = [&](auto k_tag) {
+                                constexpr int K = decltype(k_tag)::value;
+                                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                                for (int u = 1; u < gp_size(K); u += 2) asm volatile("v_mov_b32 %0, %1" : "=v"(gp_h[K & 1][u]) : "v"(gp_h[K & 1][u]));
+#pragma unroll
+                                for (int u = 0; u < gp_size(K); ++u)
+                                    accumulate(gp_h[K & 1][u], make_float4(gp_d[K & 1][u].x, gp_d[K & 1][u].y, 0.0f, 0.0f), gp_s[K & 1][u]);
+                                // (the sums are needed HERE: without this the compiler sinks a group's arithmetic past the branches below to the
+                                // chunk's end, and every group's operands stay live at once)
+                                if constexpr (K + 1 < GP_NF) gp_ha += 4u * (uint32_t)(gp_size(K + 1) * LC.HP);      // (group k + 1 is on its way)
+                                asm volatile("" : "+v"(gW1[0]), "+v"(gW1[1]), "+v"(gW1[2]), "+v"(gW1[3]), "+v"(gb1), "+v"(gW2[0]), "+v"(gW2[1]), "+v"(gp_ha));
+                                __builtin_amdgcn_sched_barrier(0);
+                            };
+                            auto gp_stages = [&](auto self, auto k_tag, auto stop_tag, auto n_tag) -> void {
+                                constexpr int K = decltype(k_tag)::value, STOP = decltype(stop_tag)::value, NG = decltype(n_tag)::value;
+                                if constexpr (K + 1 < NG) { gp_issue_hs(std::integral_constant<int, K + 1>{}); gp_issue_d(std::integral_constant<int, K + 1>{}); }
+                                gp_run(k_tag);
+                                if constexpr (K + 1 < STOP) self(self, std::integral_constant<int, K + 1>{}, stop_tag, n_tag);
+                            };
+                            using I0 = std::integral_constant<int, 0>; using INS = std::integral_constant<int, GP_NS>;
+                            using INF = std::integral_constant<int, GP_NF>;
+                            gp_issue_d(I0{});
+                            // a full chunk: its last five samples go on in the same pipeline -- no tail loop, no round trip of its own.  The group
+                            // behind the twelfth sample is requested by the short chunk too and not used there (its rows lie behind the batch's
+                            // last, inside the workgroup's LDS -- asserted at GPIPE): a request inside a branch ends in the compiler's register
+                            // copies of its h words, which wait for them.
+                            gp_stages(gp_stages, I0{}, INS{}, INF{});
+                            if (b1 - b0 == FIX_CHUNK) gp_stages(gp_stages, INS{}, INF{}, INF{});
+                        } else {
                         int vzero;
                         asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
                         const float *hp = hB + ((jv || (GB2_LANE && j == Hq)) ? j : 0) + b0 * HP, *dqp = dqB + 4 * b0 + vzero, *sp = sB + SP * b0 + vzero;
@@ -1485,12 +1610,17 @@ __global__ __launch_bounds__(NT) void ddqn_se_inner_kernel(const InnerArgs a)
                             load_s(sp, sv);
                             accumulate(h, dm4, sv);
                         }
+                        }
+                        // GPIPE: the partials' addresses are formed here, from a lane number the compiler cannot trace back -- it otherwise carries
+                        // them (a wave's chunk never changes) in registers of their own through the whole learn step
+                        int js = j;
+                        if constexpr (GPIPE) asm volatile("" : "+v"(js));
                         if (jv) {
 #pragma unroll
-                            for (int i = 0; i < S; ++i) pc[j * S + i] = gW1[i];
-                            pc[Hq * S + j] = gb1;
+                            for (int i = 0; i < S; ++i) pc[js * S + i] = gW1[i];
+                            pc[Hq * S + js] = gb1;
 #pragma unroll
-                            for (int aa = 0; aa < A; ++aa) pc[Hq * S + Hq + aa * Hq + j] = gW2[aa];
+                            for (int aa = 0; aa < A; ++aa) pc[Hq * S + Hq + aa * Hq + js] = gW2[aa];
                             if constexpr (TEAM) {
 #pragma unroll
                                 for (int i = 0; i < S; ++i) xg[j * S + i] = make_float2(gW1[i], xtag);
