@@ -665,6 +665,45 @@ int lenv_td3d_rn_inner_loop(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_td3d_r
                             const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
                             const lenv_td3d_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace, size_t workspace_bytes,
                             const lenv_td3_out *out /*HOST*/, void *stream);
+/* The two TD3_discrete_vary inner loops in EPISODE SEGMENTS (ABI 7, functions only; the siblings of lenv_td3_rn_inner_loop_segment): a launch
+ * runs episodes [episode_begin, episode_end) of every chain on the SEG instantiations of the same kernel and leaves a resume record per chain;
+ * the next launch (episode_begin = the last episode_end) goes on from it.  For every split 0 = e0 < e1 < .. < ek = train_episodes the k launches
+ * leave every lenv_td3_out array and the traces bit-identical to one lenv_td3d_inner_loop / lenv_td3d_rn_inner_loop launch.
+ *   episode_begin == 0: the arena is initialised from agent_init; the record is written, never read.
+ *   episode_begin  > 0: nothing in the arena is initialised (parameters, targets, Adam m / v, the replay ring, the early-out meter); the perturbed
+ *     SE / reward net is staged again from theta / eps / worker / sign.  The caller passes the same workspace (untouched in between), out
+ *     arrays, tapes, hp and theta / eps / worker / sign as to the earlier segments.  A chain whose record does not say "next episode ==
+ *     episode_begin" writes status -10 and does nothing else; a chain whose record says finished returns at once.
+ * The closing part (final test, score, final_returns, the NaN / time-out padding of unrun episodes, final_params) runs once per chain, in the
+ * segment in which the chain ends (train_episodes reached, early out, step_budget time-out).  A segment that ends with the chain unfinished
+ * writes the cumulative stats and final_params (a checkpoint) and nothing else of the closing part.
+ * Refused with LENV_ERR_INVALID, before `chains == 0` is accepted: !(0 <= episode_begin < episode_end <= cfg->train_episodes), resume == NULL,
+ * and whatever the continued entry refuses, with its code (a cfg it does not support: LENV_ERR_UNSUPPORTED, also for zero chains).
+ * workspace_bytes: lenv_td3d_workspace_bytes / lenv_td3d_rn_workspace_bytes.
+ * The record (opaque to callers), int64 words per chain:
+ *    0 next episode to run            1 finished (0 / 1)               2 status so far (0 ok, else the minimum of the chain's codes)
+ *    3 timed_out_at (-1: no time-out) 4 n_rand (random actions drawn)  5 n_actn (train-action Gumbel / noise rows drawn)
+ *    6 n_testn (test rows drawn from the tapes)  7 n_test_ep (test episodes run)  8 learn_it (learn calls)
+ *    9 train_steps (agent steps; ring position = train_steps % capacity)   10 test_steps   11 episodes_run
+ *   12 trace cursor: rows of the step trace written, before the trace_cap clamp (one row per agent step: always equal to word 9)
+ *   13..16 bit patterns of the doubles beta1^t, beta2^t of the critic optimizer, then of the actor optimizer
+ *   17 policy_it (delayed policy updates made: the row counter of the actor's Gumbel draws)
+ *   18 bit pattern (low 32 bits) of the annealed Gumbel temperature as the acting steps read it: the schedule value of the LAST learn call,
+ *      which is one schedule step behind the value at learn_it               19..31 reserved (0)
+ * The early-out meter (the per-episode test means) lives in the arena.
+ * Status of a failing chain and the double meaning of -10: as documented at lenv_td3_rn_inner_loop_segment. */
+#define LENV_TD3D_RESUME_WORDS 32
+int lenv_td3d_inner_loop_segment(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_chain_hp *hp /*HOST struct of device arrays, may be NULL*/,
+                                 const float *theta, const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
+                                 const uint64_t *rng_keys, const lenv_td3d_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace,
+                                 size_t workspace_bytes, const lenv_td3_out *out /*HOST*/, int32_t episode_begin, int32_t episode_end,
+                                 int64_t *resume /*DEVICE [chains, LENV_TD3D_RESUME_WORDS]*/, void *stream);
+int lenv_td3d_rn_inner_loop_segment(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_td3d_rn_cfg *rn /*HOST*/,
+                                    const lenv_chain_hp *hp /*HOST struct of device arrays, may be NULL*/, const float *theta, const float *eps,
+                                    const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                                    const lenv_td3d_tapes *tapes /*HOST, may be NULL*/, int64_t chains, void *workspace, size_t workspace_bytes,
+                                    const lenv_td3_out *out /*HOST*/, int32_t episode_begin, int32_t episode_end,
+                                    int64_t *resume /*DEVICE [chains, LENV_TD3D_RESUME_WORDS]*/, void *stream);
 /* fresh agents: nn.Linear default init from the chain key's counter stream, LayerNorm weight 1 / bias 0 */
 int lenv_td3d_agent_init(const lenv_td3d_cfg *cfg /*HOST*/, const lenv_chain_hp *hp /*may be NULL*/, const uint64_t *rng_keys,
                          int64_t chains, float *agent_init, void *stream);

@@ -15,6 +15,7 @@ VARIANT_NO_WAVECHAIN, VARIANT_GENERIC, VARIANT_TEAM_NARROW, VARIANT_NO_DIRECT, V
 TD3_RESUME_WORDS = 32                            # LENV_TD3_RESUME_WORDS: int64 words of a chain's record between two segment launches
 DUELING_RESUME_WORDS = 32                        # LENV_DUELING_RESUME_WORDS: the same for lenv_dueling_se_inner_loop_segment
 PPO_RESUME_WORDS = 32                            # LENV_PPO_RESUME_WORDS: the same for lenv_ppo_rn_inner_loop_segment
+TD3D_RESUME_WORDS = 32                           # LENV_TD3D_RESUME_WORDS: the same for lenv_td3d_inner_loop_segment / lenv_td3d_rn_inner_loop_segment
 STATUS_TEAM_GAVE_UP = -10                        # a team member waited too long for the others: repeat the launch with team_size 1
 STATUS_WRONG_SEGMENT = -10                       # the same value from lenv_td3_rn_inner_loop_segment: the chain's record names another episode_begin
                                                  # (segment launches never run on a team; engine.run_checked's retry is for single launches only)
@@ -189,6 +190,7 @@ _vp, _i32, _i64, _f64, _P = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.POIN
 # workspace, workspace_bytes, out, stream
 _DDQN_RUN = [_vp] * 6 + [_P(Tapes), _i64, _vp, C.c_size_t, _P(InnerOut), _vp]
 _TD3_RUN = [_vp] * 6 + [_P(Td3Tapes), _i64, _vp, C.c_size_t, _P(Td3Out), _vp]
+_TD3D_RUN = [_vp] * 6 + [_P(Td3dTapes), _i64, _vp, C.c_size_t, _P(Td3Out), _vp]
 _NES_DRAW_TAIL = [_i64, _i64, C.c_float, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _vp]
 _NES_RANK_HEAD = [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _f64, _i32, _f64, _vp]
 
@@ -260,13 +262,13 @@ SIGNATURES = {
     "lenv_td3d_workspace_bytes": (C.c_size_t, [_P(Td3dCfg), _i64]),
     "lenv_td3d_num_params": (_i64, [_P(Td3dCfg), _P(_i64), _P(_i64)]),
     "lenv_td3d_se_num_params": (_i64, [_P(Td3dCfg)]),
-    "lenv_td3d_inner_loop": (C.c_int, [_P(Td3dCfg), _P(ChainHp), _vp, _vp, _vp, _vp, _vp, _vp, _P(Td3dTapes), _i64, _vp, C.c_size_t,
-                                       _P(Td3Out), _vp]),
+    "lenv_td3d_inner_loop": (C.c_int, [_P(Td3dCfg), _P(ChainHp)] + _TD3D_RUN),
+    "lenv_td3d_inner_loop_segment": (C.c_int, [_P(Td3dCfg), _P(ChainHp)] + _TD3D_RUN[:-1] + [_i32, _i32, _vp, _vp]),
     "lenv_td3d_agent_init": (C.c_int, [_P(Td3dCfg), _P(ChainHp), _vp, _i64, _vp, _vp]),
     "lenv_td3d_rn_workspace_bytes": (C.c_size_t, [_P(Td3dCfg), _P(Td3dRnCfg), _i64]),
     "lenv_td3d_rn_num_params": (_i64, [_P(Td3dCfg), _P(Td3dRnCfg)]),
-    "lenv_td3d_rn_inner_loop": (C.c_int, [_P(Td3dCfg), _P(Td3dRnCfg), _P(ChainHp), _vp, _vp, _vp, _vp, _vp, _vp, _P(Td3dTapes), _i64, _vp,
-                                          C.c_size_t, _P(Td3Out), _vp]),
+    "lenv_td3d_rn_inner_loop": (C.c_int, [_P(Td3dCfg), _P(Td3dRnCfg), _P(ChainHp)] + _TD3D_RUN),
+    "lenv_td3d_rn_inner_loop_segment": (C.c_int, [_P(Td3dCfg), _P(Td3dRnCfg), _P(ChainHp)] + _TD3D_RUN[:-1] + [_i32, _i32, _vp, _vp]),
     "lenv_ppo_rows": (_i64, [_P(PpoCfg)]),
     "lenv_ppo_num_params": (_i64, [_P(PpoCfg), _P(_i64), _P(_i64)]),
     "lenv_ppo_rn_num_params": (_i64, [_P(PpoCfg)]),

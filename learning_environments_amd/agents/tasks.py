@@ -125,12 +125,14 @@ class DdqnVaryTask(_VaryAgents):
         self._init_vary(config["agents"][self.agent_key])
         self.icm_bounds = _icm_bounds(engine, self.cfg)
 
-    def make_inner(self, chains, want_episode_stats=True):
-        return self.engine.make_inner(self.cfg, chains, want_episode_stats=want_episode_stats, vary=True)
+    def make_inner(self, chains, want_episode_stats=True, **kw):
+        """kw: InnerLoop's own keywords (segments=True: the launch will run as episode segments -- the same GEMM-tiled kernel, same bits)"""
+        return self.engine.make_inner(self.cfg, chains, want_episode_stats=want_episode_stats, vary=True, **kw)
 
-    def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
+    def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init, **run_kw):
+        """run_kw: run()'s own keywords (episodes_per_launch, on_segment)"""
         self._fresh_agents(inner, keys_t)
-        return self.engine.inner_scores(inner, theta, eps, chain_worker, chain_sign, None, keys_t)
+        return self.engine.inner_scores(inner, theta, eps, chain_worker, chain_sign, None, keys_t, **run_kw)
 
     def needs_agent_init(self):
         return False          # drawn inside scores(), once the chains' shapes are known
@@ -243,12 +245,13 @@ class Td3DiscreteTask(_VaryAgents):
             self.name = "td3_discrete_rn"
         self._init_vary(base)
 
-    def make_inner(self, chains, want_episode_stats=False):
-        return self.engine.make_inner_td3d(self.cfg, chains, want_episode_stats=want_episode_stats, vary=self.vary, rn=self.rn)
+    def make_inner(self, chains, want_episode_stats=False, **kw):
+        return self.engine.make_inner_td3d(self.cfg, chains, want_episode_stats=want_episode_stats, vary=self.vary, rn=self.rn, **kw)
 
-    def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init):
+    def scores(self, inner, theta, eps, chain_worker, chain_sign, keys_t, agent_init, **run_kw):
+        """run_kw: run()'s own keywords (episodes_per_launch, on_segment)"""
         self._fresh_agents(inner, keys_t, draw_hp=self.vary)
-        return self.engine.inner_scores_td3(inner, theta, eps, chain_worker, chain_sign, None, keys_t)
+        return self.engine.inner_scores_td3(inner, theta, eps, chain_worker, chain_sign, None, keys_t, **run_kw)
 
     def needs_agent_init(self):
         return False          # drawn inside scores() (the LayerNorm parameters are not uniform draws)

@@ -53,16 +53,60 @@ struct Td3dArgs {
     int64_t a_params, a_targets, a_m, a_v, a_grad, a_replay, a_xc, a_xn, a_xa, a_hc1[TD_MAXL], a_hc2[TD_MAXL], a_ha[TD_MAXL], a_ht[TD_MAXL],
         a_xh1[TD_MAXL], a_xh2[TD_MAXL], a_xha[TD_MAXL], a_rs1, a_rs2, a_rsa, a_d[2], a_dx, a_raw, a_ys, a_dz, a_meter, a_se;
     lenv_td3d_rn_cfg rn;                       // RENV instantiations: the reward net (theta / P_se are its parameters)
+    // lenv_td3d_inner_loop_segment / lenv_td3d_rn_inner_loop_segment (the SEG instantiations): episodes [ep_begin, ep_end) of every chain, resume
+    // records [chains, LENV_TD3D_RESUME_WORDS]; behind everything the other instantiations read
+    int ep_begin, ep_end; int64_t *resume;
 };
 
-template <int ENVD, bool RENV = false>
+// The resume record of a chain after a segment (include/lenv_hip.h documents the words): thread 0, behind the barrier that follows the threads'
+// atomicMin into the folded status
+__device__ __forceinline__ void td3d_write_record(int64_t *rec, int next_episode, int finished, int status, int timed_out_at, int64_t n_rand,
+                                                  int64_t n_actn, int64_t n_testn, int64_t n_test_ep, int64_t learn_it, int train_steps,
+                                                  int test_steps, int episodes_run, const double *pows, int64_t policy_it, float temp)
+{
+    rec[0] = next_episode; rec[1] = finished; rec[2] = status; rec[3] = timed_out_at;
+    rec[4] = n_rand; rec[5] = n_actn; rec[6] = n_testn; rec[7] = n_test_ep; rec[8] = learn_it;
+    rec[9] = train_steps; rec[10] = test_steps; rec[11] = episodes_run; rec[12] = train_steps;
+    for (int i = 0; i < 4; ++i) rec[13 + i] = __double_as_longlong(pows[i]);
+    rec[17] = policy_it; rec[18] = (int64_t)__float_as_uint(temp);
+    for (int w = 19; w < LENV_TD3D_RESUME_WORDS; ++w) rec[w] = 0;
+}
+
+// SEG (lenv_td3d_inner_loop_segment / lenv_td3d_rn_inner_loop_segment, include/lenv_hip.h) = the same kernel over the episodes
+// [a.ep_begin, a.ep_end).  What the loop carries from episode to episode outside the arena is read from / written to the chain's resume record:
+// the counters n_rand, n_actn, n_testn, n_test_ep, learn_it, policy_it, train_steps (also the ring position and the step-trace cursor),
+// test_steps, episodes_run; the four Adam powers; the status; timed_out_at; and the annealed temperature `temp` as it stands (set from
+// learn_it BEFORE the increment in learn and read by the acting steps that follow: td3d_temperature(learn_it) after a boundary would be one
+// schedule step ahead).  The perturbed SE / reward net (arena) is staged by every segment, the agent only by the first; the closing part runs
+// in the segment in which the chain ends.
+// LDS between episodes: misc[0..64) is cleared by every launch, and no control word is read before it is rewritten inside an episode --
+// ctrl[10..11] are written by thread 0 of adam() in front of the barrier its readers wait at, ctrl[14..15] likewise inside mlp_row1,
+// ictrl[4] by thread 0 in every step of test_phase before `alive` reads it, ictrl[3] by thread 0 at the end of every episode before `brk`
+// reads it.  state / action / newrow / xse / nse / xs_d are rewritten from the reset on; xt_d / ret / ep_rew / tlen / tflag by every
+// test_phase before it reads them.  The arena's batch buffers (xc, xn, xa, the activations, grad, dbuf, rawb, ysb, dzb, dxb, rs*) are filled
+// by a learn step before that step reads them.  phi_s / have_phi / ep_len / tr_reward are registers born inside an episode.  So the record
+// needs no LDS word and the arena carries params, targets, Adam m / v, the replay ring, the meter and the staged nets.
+// Its own instantiations: the code of the others is what it was.
+
+template <int ENVD, bool RENV = false, bool SEG = false>
 __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs a)
 {
     extern __shared__ __align__(16) float lds[];
     const lenv_td3d_cfg &cfg = a.cfg;
     const int tid = threadIdx.x;
     const int64_t chain = blockIdx.x;
-    if (threadIdx.x == 0 && a.out.status) a.out.status[chain] = 0;
+    [[maybe_unused]] int64_t *rec = nullptr;
+    [[maybe_unused]] const bool fresh = !SEG || a.ep_begin == 0;          // the arena is initialised by this launch
+    if constexpr (SEG) {
+        rec = a.resume + chain * LENV_TD3D_RESUME_WORDS;
+        if (!fresh) {                                    // uniform per chain
+            if (rec[1] == 1) return;                     // finished in an earlier segment: the chain and its outputs stay as they are
+            if (rec[0] != (int64_t)a.ep_begin) { if (tid == 0 && a.out.status) a.out.status[chain] = -10; return; }
+        }
+        if (threadIdx.x == 0 && a.out.status && fresh) a.out.status[chain] = 0;
+    } else {
+        if (threadIdx.x == 0 && a.out.status) a.out.status[chain] = 0;
+    }
     constexpr int S = ENVD == LENV_ENV_CARTPOLE ? 4 : (ENVD == LENV_ENV_ACROBOT ? 6 : 2);
     constexpr int A = ENVD == LENV_ENV_CARTPOLE ? 2 : 3;
     constexpr int SA = S + A;
@@ -74,7 +118,11 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
     const int T = cfg.test_episodes, Hse = cfg.se_hidden, Lse = cfg.se_layers, se_act = cfg.se_act, RS = a.RS;
     const int policy_delay = cfg.policy_delay;
     if (vary && (H < 1 || H > cfg.hidden || L < 1 || L > cfg.layers || B < 1 || B > Bm)) {   // uniform per chain
-        if (tid == 0) { if (a.out.status) a.out.status[chain] = -8; a.out.score[chain] = 0.0; }
+        if (tid == 0) {
+            if (a.out.status) a.out.status[chain] = -8;
+            a.out.score[chain] = 0.0;
+            if constexpr (SEG) { for (int w = 0; w < LENV_TD3D_RESUME_WORDS; ++w) rec[w] = 0; rec[1] = 1; rec[2] = -8; rec[3] = -1; }
+        }
         return;
     }
     DMlpOff mo_actor, mo_critic, mo_se[3];
@@ -131,13 +179,13 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
     double *meter = reinterpret_cast<double *>(arena + a.a_meter);
     float *sep = arena + a.a_se;
 
-    // ---- stage the perturbed SE (GTN_worker.py:165-175) and the fresh agent ----
+    // ---- stage the perturbed SE (GTN_worker.py:165-175) and the fresh agent (SEG: the agent in the first segment only) ----
     {
         const float sg = a.eps ? a.sign[chain] : 0.0f;
         const float *e = a.eps ? a.eps + (int64_t)a.worker[chain] * a.P_se : nullptr;
         for (int i = tid; i < a.P_se; i += DNT) sep[i] = e ? fma32(sg, e[i], a.theta[i]) : a.theta[i];
     }
-    for (int p = tid; p < P; p += DNT) {
+    if (fresh) for (int p = tid; p < P; p += DNT) {
         const float w = a.agent_init[chain * a.P + p];
         params[p] = w; targets[p] = w; adam_m[p] = 0.0f; adam_v[p] = 0.0f;
     }
@@ -153,6 +201,16 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
     const int rb_cap = (int)a.rb_cap;
     float temp = td3d_temperature(cfg.gumbel_temp, 0);                  // gumbel_temp_annealed = steps[0] (TD3_discrete_vary.py:60)
     const float astd = (float)cfg.action_std;
+    int timed_out_at = -1;
+    if constexpr (SEG) {
+        if (!fresh) {                                    // every thread its copy, like the counters of a single launch
+            status = (int)rec[2]; timed_out_at = (int)rec[3];
+            n_rand = rec[4]; n_actn = rec[5]; n_testn = rec[6]; n_test_ep = rec[7]; learn_it = rec[8];
+            train_steps = (int)rec[9]; test_steps = (int)rec[10]; episodes_run = (int)rec[11];
+            for (int i = 0; i < 4; ++i) pows[i] = __longlong_as_double(rec[13 + i]);
+            policy_it = rec[17]; temp = __uint_as_float((unsigned)rec[18]);
+        }
+    }
 
     GemmQueue gq(cmds);
 
@@ -364,10 +422,11 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
 
     const float g32 = (float)cfg.gamma;
     const bool budgeted = cfg.step_budget > 0;
-    int timed_out_at = -1;
     const bool no_test_env = cfg.test_mode == 1;      // BaseAgent.train(env, test_env=None): lenv_ddqn_cfg::test_mode
+    [[maybe_unused]] bool early_out = false;          // SEG: the loop ended at the early out
+    const int ep_first = SEG ? a.ep_begin : 0, ep_last = SEG ? a.ep_end : cfg.train_episodes;
     TDP_DECL;
-    for (int episode = 0; episode < cfg.train_episodes; ++episode) {
+    for (int episode = ep_first; episode < ep_last; ++episode) {
         if (budgeted && (int64_t)train_steps + test_steps > cfg.step_budget) { timed_out_at = episode; break; }   // uniform
         const bool learning = episode >= cfg.init_episodes;
         // env.reset(): VirtualEnv.reset -> reset_env.reset() (virtual_env.py:33-41)
@@ -609,7 +668,28 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
         __syncthreads();
         const int brk = ictrl[3];
         __syncthreads();
-        if (brk) break;
+        if (brk) { if constexpr (SEG) early_out = true; break; }
+    }
+    // misc[MISC_STATUS_FOLD] (an int): the SEG instantiations' fold of the threads' status codes (0 after the clear of misc; the control words in
+    // use are ctrl[10..11], ctrl[14..15] and ictrl[3..4] = misc[35..36])
+    [[maybe_unused]] constexpr int MISC_STATUS_FOLD = 48;
+    if constexpr (SEG) {
+        if (!early_out && timed_out_at < 0 && a.ep_end < cfg.train_episodes) {
+            // the chain goes on in the next segment: a checkpoint (cumulative stats, the parameters so far) and the record
+            int *st_fold = reinterpret_cast<int *>(misc + MISC_STATUS_FOLD);
+            if (status != 0) { atomicMin(st_fold, status); if (a.out.status) atomicMin(&a.out.status[chain], status); }
+            if (a.out.final_params) for (int p = tid; p < P; p += DNT) a.out.final_params[chain * a.P + p] = params[p];
+            __syncthreads();
+            if (tid == 0) {
+                if (a.out.stats) {
+                    a.out.stats[chain * 4 + 0] = episodes_run; a.out.stats[chain * 4 + 1] = train_steps;
+                    a.out.stats[chain * 4 + 2] = learn_it; a.out.stats[chain * 4 + 3] = test_steps;
+                }
+                td3d_write_record(rec, a.ep_end, 0, *st_fold, timed_out_at, n_rand, n_actn, n_testn, n_test_ep, learn_it, train_steps, test_steps,
+                                  episodes_run, pows, policy_it, temp);
+            }
+            return;
+        }
     }
     const int64_t remaining = cfg.step_budget - ((int64_t)train_steps + test_steps);     // time_remaining - elapsed
     const int test_before = test_steps;
@@ -659,6 +739,13 @@ __global__ __launch_bounds__(DNT) void td3_discrete_inner_kernel(const Td3dArgs 
 #endif
     if (a.out.final_params) for (int p = tid; p < P; p += DNT) a.out.final_params[chain * a.P + p] = params[p];
     if (a.out.status && status != 0) atomicMin(&a.out.status[chain], status);
+    if constexpr (SEG) {
+        int *st_fold = reinterpret_cast<int *>(misc + MISC_STATUS_FOLD);
+        if (status != 0) atomicMin(st_fold, status);
+        __syncthreads();
+        if (tid == 0) td3d_write_record(rec, a.ep_end, 1, *st_fold, timed_out_at, n_rand, n_actn, n_testn, n_test_ep, learn_it, train_steps, test_steps,
+                                        episodes_run, pows, policy_it, temp);
+    }
 }
 
 // Fresh agents (actor | critic_1 | critic_2): nn.Linear's default init U(-1/sqrt(fan_in), 1/sqrt(fan_in)) from the chain key's
@@ -803,13 +890,21 @@ extern "C" int lenv_td3d_agent_init(const lenv_td3d_cfg *cfg, const lenv_chain_h
     return hipGetLastError() == hipSuccess ? LENV_OK : LENV_ERR_LAUNCH;
 }
 
+// the launch behind lenv_td3d_inner_loop / lenv_td3d_rn_inner_loop (seg.on false: one launch from the first episode to the final test) and their
+// _segment entries (seg.on true: episodes [seg.begin, seg.end) on the SEG instantiations)
 static int td3d_launch(const lenv_td3d_cfg *cfg, const lenv_td3d_rn_cfg *rn, const lenv_chain_hp *hp, const float *theta, const float *eps,
                        const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
                        const lenv_td3d_tapes *tapes, int64_t chains, void *workspace, size_t workspace_bytes,
-                       const lenv_td3_out *out, void *stream)
+                       const lenv_td3_out *out, void *stream, const lenv_host::Segment &seg = lenv_host::Segment{})
 {
-    if (!lenv_host::launch_args_ok(cfg, hp, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, out, lenv_host::Segment{}) || !theta)
+    if (!lenv_host::launch_args_ok(cfg, hp, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, out, seg) || !theta)
         return LENV_ERR_INVALID;
+    if (seg.on) {                                      // what the continued entry refuses, also for a launch without chains
+        Td3dArgs probe;
+        size_t probe_lds;
+        const int prc = td3d_layout(cfg, probe, &probe_lds, rn);
+        if (prc != LENV_OK) return prc;
+    }
     if (chains == 0) return LENV_OK;
     Td3dArgs a;
     size_t lds_bytes;
@@ -819,8 +914,14 @@ static int td3d_launch(const lenv_td3d_cfg *cfg, const lenv_td3d_rn_cfg *rn, con
     lenv_host::fill_args(a, cfg, theta, eps, worker, sign, agent_init, rng_keys, tapes, workspace, out);
     lenv_host::fill_hp(a, hp);
     a.rn = rn ? *rn : lenv_td3d_rn_cfg{};
+    lenv_host::fill_segment(a, cfg, seg);
     void (*kern)(const Td3dArgs) = nullptr;
-    if (cfg->env_id == LENV_ENV_CARTPOLE) kern = rn ? td3_discrete_inner_kernel<LENV_ENV_CARTPOLE, true> : td3_discrete_inner_kernel<LENV_ENV_CARTPOLE>;
+    if (seg.on) {
+        if (cfg->env_id == LENV_ENV_CARTPOLE) kern = rn ? td3_discrete_inner_kernel<LENV_ENV_CARTPOLE, true, true> : td3_discrete_inner_kernel<LENV_ENV_CARTPOLE, false, true>;
+        else if (cfg->env_id == LENV_ENV_ACROBOT) kern = rn ? td3_discrete_inner_kernel<LENV_ENV_ACROBOT, true, true> : td3_discrete_inner_kernel<LENV_ENV_ACROBOT, false, true>;
+        else kern = rn ? td3_discrete_inner_kernel<LENV_ENV_MOUNTAINCAR, true, true> : td3_discrete_inner_kernel<LENV_ENV_MOUNTAINCAR, false, true>;
+    }
+    else if (cfg->env_id == LENV_ENV_CARTPOLE) kern = rn ? td3_discrete_inner_kernel<LENV_ENV_CARTPOLE, true> : td3_discrete_inner_kernel<LENV_ENV_CARTPOLE>;
     else if (cfg->env_id == LENV_ENV_ACROBOT) kern = rn ? td3_discrete_inner_kernel<LENV_ENV_ACROBOT, true> : td3_discrete_inner_kernel<LENV_ENV_ACROBOT>;
     else kern = rn ? td3_discrete_inner_kernel<LENV_ENV_MOUNTAINCAR, true> : td3_discrete_inner_kernel<LENV_ENV_MOUNTAINCAR>;
     return lenv_host::launch(kern, dim3((unsigned)chains), dim3(DNT), lds_bytes, stream, a);
@@ -859,6 +960,26 @@ extern "C" int lenv_td3d_rn_inner_loop(const lenv_td3d_cfg *cfg, const lenv_td3d
 {
     if (!rn) return LENV_ERR_INVALID;
     return td3d_launch(cfg, rn, hp, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, stream);
+}
+
+extern "C" int lenv_td3d_inner_loop_segment(const lenv_td3d_cfg *cfg, const lenv_chain_hp *hp, const float *theta, const float *eps,
+                                            const int32_t *worker, const float *sign, const float *agent_init, const uint64_t *rng_keys,
+                                            const lenv_td3d_tapes *tapes, int64_t chains, void *workspace, size_t workspace_bytes,
+                                            const lenv_td3_out *out, int32_t episode_begin, int32_t episode_end, int64_t *resume, void *stream)
+{
+    return td3d_launch(cfg, nullptr, hp, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, stream,
+                       lenv_host::Segment{true, episode_begin, episode_end, resume});
+}
+
+extern "C" int lenv_td3d_rn_inner_loop_segment(const lenv_td3d_cfg *cfg, const lenv_td3d_rn_cfg *rn, const lenv_chain_hp *hp, const float *theta,
+                                               const float *eps, const int32_t *worker, const float *sign, const float *agent_init,
+                                               const uint64_t *rng_keys, const lenv_td3d_tapes *tapes, int64_t chains, void *workspace,
+                                               size_t workspace_bytes, const lenv_td3_out *out, int32_t episode_begin, int32_t episode_end,
+                                               int64_t *resume, void *stream)
+{
+    if (!rn) return LENV_ERR_INVALID;
+    return td3d_launch(cfg, rn, hp, theta, eps, worker, sign, agent_init, rng_keys, tapes, chains, workspace, workspace_bytes, out, stream,
+                       lenv_host::Segment{true, episode_begin, episode_end, resume});
 }
 
 #ifdef LENV_PHASE_TIMING

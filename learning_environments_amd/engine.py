@@ -557,8 +557,9 @@ class _SegmentedInnerLoop(_InnerLoopBase):
     def _prefix_args(self):
         return tuple(getattr(self, "_%s_arg" % p)() for p in self.prefix)
 
-    def run(self, theta, eps, worker, sign, agent_init, rng_keys=None, tapes=None, episodes_per_launch=None, on_segment=None):
-        """episodes_per_launch None: one launch from the first episode to the final test (asynchronous).  An integer: the same inner loop
+    def run(self, theta, eps, worker, sign, agent_init=None, rng_keys=None, tapes=None, episodes_per_launch=None, on_segment=None):
+        """agent_init None: the drawn self.agent_init, for the families that keep one (the *_vary agents, Td3DiscreteInnerLoop).
+        episodes_per_launch None: one launch from the first episode to the final test (asynchronous).  An integer: the same inner loop
         as a series of segment launches of that many episodes each (run_segment; same bits for every split).  After each segment the
         chains' `finished` words and statuses come to the host (one small copy, the only synchronisation), on_segment(episodes_done,
         finished_count) is called if given, then -- after the callback, so that it sees the segment in which a chain failed -- a bad status
@@ -750,14 +751,15 @@ class Td3InnerLoop(_SegmentedInnerLoop):
                             trace_cap)
 
 
-class Td3DiscreteInnerLoop(_InnerLoopBase):
+class Td3DiscreteInnerLoop(_SegmentedInnerLoop):
     """Owns the workspace/outputs of lenv_td3d_inner_loop (TD3_discrete_vary on a VirtualEnv) for a fixed (cfg, chains).
     vary=True: cfg carries the maximal batch_size / hidden / layers, every chain runs with its own draw (set_hp).
     rn (a _lib.Td3dRnCfg): the chains train on RewardEnv(real env) / the real env instead, through lenv_td3d_rn_inner_loop; theta is the
-    reward net."""
+    reward net.  agent_init None (run's default): the drawn self.agent_init, with or without vary."""
     Out, Tapes, final, trace_spec = Td3Out, Td3dTapes, "final_params", _TD3_TRACE
     cfg_type, hp_fields = Td3dCfg, ("batch_size", "hidden", "layers")
     num_params_fn, agent_init_fn = "lenv_td3d_num_params", "lenv_td3d_agent_init"
+    resume_words = _lib.TD3D_RESUME_WORDS
 
     def __init__(self, cfg, chains, want_episode_stats=True, want_final_params=False, trace_cap=0, vary=False, rn=None):
         super().__init__(cfg, chains)
@@ -767,9 +769,11 @@ class Td3DiscreteInnerLoop(_InnerLoopBase):
         self.p_actor, self.p_critic = pa.value, pc.value
         self.rn = rn
         if rn is None:
+            self.entry, self.segment_entry, self.prefix = ("lenv_td3d_inner_loop",) * 2, "lenv_td3d_inner_loop_segment", ("hp",)
             self.p_theta = int(L.lenv_td3d_se_num_params(C.byref(cfg)))
             ws_bytes = L.lenv_td3d_workspace_bytes(C.byref(cfg), self.chains)
         else:
+            self.entry, self.segment_entry, self.prefix = ("lenv_td3d_rn_inner_loop",) * 2, "lenv_td3d_rn_inner_loop_segment", ("rn", "hp")
             self.p_theta = _count("lenv_td3d_rn_num_params", C.byref(cfg), C.byref(rn))
             ws_bytes = L.lenv_td3d_rn_workspace_bytes(C.byref(cfg), C.byref(rn), self.chains)
         self._init_vary(vary)
@@ -777,19 +781,16 @@ class Td3DiscreteInnerLoop(_InnerLoopBase):
             self.agent_init = torch.zeros((self.chains, self.p_agent), dtype=torch.float32, device=self.dev)
         self._alloc_outputs(ws_bytes, want_episode_stats, want_final_params, trace_cap)
 
-    def run(self, theta, eps, worker, sign, agent_init=None, rng_keys=None, tapes=None):
+    def _rn_arg(self):
+        return C.byref(self.rn)
+
+    def _launch_args(self, theta, eps, worker, sign, agent_init, rng_keys, tapes, segment=False):
         if agent_init is None:
             agent_init = self.agent_init
         args = self._run_args(theta, eps, worker, sign, agent_init, rng_keys, tapes)
         if theta.numel() != self.p_theta:
             raise ValueError("theta must hold %d %s parameters" % (self.p_theta, "SE" if self.rn is None else "reward-net"))
-        if self.rn is None:
-            rc = _lib.lib().lenv_td3d_inner_loop(C.byref(self.cfg), self._hp_arg(), *args)
-            _lib.check(rc, "lenv_td3d_inner_loop")
-        else:
-            rc = _lib.lib().lenv_td3d_rn_inner_loop(C.byref(self.cfg), C.byref(self.rn), self._hp_arg(), *args)
-            _lib.check(rc, "lenv_td3d_rn_inner_loop")
-        return self.score
+        return args
 
 
 class PpoInnerLoop(_SegmentedInnerLoop):
@@ -944,8 +945,8 @@ class HipNesEngine(object):
     def make_inner_td3d(self, cfg, chains, **kw):
         return Td3DiscreteInnerLoop(cfg, chains, **kw)
 
-    def inner_scores_td3(self, inner, theta, eps, worker, sign, agent_init, rng_keys):
-        return inner.run(theta, eps, worker, sign, agent_init, rng_keys=rng_keys)
+    def inner_scores_td3(self, inner, theta, eps, worker, sign, agent_init, rng_keys, **run_kw):
+        return inner.run(theta, eps, worker, sign, agent_init, rng_keys=rng_keys, **run_kw)
 
     def make_inner_ppo(self, cfg, chains, **kw):
         return PpoInnerLoop(cfg, chains, **kw)
@@ -965,8 +966,8 @@ class HipNesEngine(object):
     def inner_scores_ql_se(self, inner, theta, eps, worker, sign, rng_keys):
         return inner.run(theta, eps, worker, sign, rng_keys=rng_keys)
 
-    def inner_scores(self, inner, theta, eps, worker, sign, agent_init, rng_keys):
-        return inner.run(theta, eps, worker, sign, agent_init, rng_keys=rng_keys)
+    def inner_scores(self, inner, theta, eps, worker, sign, agent_init, rng_keys, **run_kw):
+        return inner.run(theta, eps, worker, sign, agent_init, rng_keys=rng_keys, **run_kw)
 
     def check_status(self, inner):
         st = inner.status.cpu()

@@ -82,7 +82,7 @@ def _task_config(train_env, config, agent_name):
 
 
 def train_test_agents(train_env, test_env, config, agents_num, agent_name="DDQN_vary", train_episodes=1000, vary_hp=True, seed=0, replay=None,
-                      model_index=0):
+                      model_index=0, episodes_per_launch=None, on_segment=None):
     """Returns (reward_list, train_steps_needed, episodes_needed) like the reference: reward_list[i] = the i-th agent's list of
     real-env test returns (BaseAgent.test), train_steps_needed[i] = [sum(episode_length)], episodes_needed[i] = [len(reward_train)].
 
@@ -90,22 +90,48 @@ def train_test_agents(train_env, test_env, config, agents_num, agent_name="DDQN_
     `_vary` agent with vary_hp off IS its base agent, DDQN_vary.py:16-21).  `seed` / `model_index` key the agents' counter RNG streams
     (the reference draws from the process-global generators).  replay = dict(hp=[...], agent_init=[...], tapes={name: [per-agent array]}):
     the recorded draws of a reference run, replayed in tape mode (parity tests); the returned dict `train_test_agents.last` holds the
-    per-agent training lists (reward_train, episode_length) of the last call."""
-    return _launch([train_env], test_env, config, agents_num, agent_name, train_episodes, vary_hp, seed, replay, [model_index])[0]
+    per-agent training lists (reward_train, episode_length) of the last call.
+
+    episodes_per_launch (None: one launch from the first episode to the closing test, as ever): the same launch as a series of resumable
+    segments of that many training episodes each -- same lists, bit for bit.  TD3_discrete_vary (vary_hp on or off) and the *_vary DDQN agents
+    with vary_hp on have a segment entry; a fixed-shape DDQN / DuelingDDQN launch (vary_hp off) runs on the register-resident or wave-chain
+    kernels, which have none: ValueError.  on_segment(episodes_done, finished_count) is called after every segment (one small copy to the
+    host); the series ends as soon as every agent has finished."""
+    return _launch([train_env], test_env, config, agents_num, agent_name, train_episodes, vary_hp, seed, replay, [model_index],
+                   episodes_per_launch=episodes_per_launch, on_segment=on_segment)[0]
 
 
 def train_test_agents_models(train_envs, test_env, config, agents_num, agent_name="DDQN_vary", train_episodes=1000, vary_hp=True, seed=0,
-                             model_indices=None):
+                             model_indices=None, episodes_per_launch=None, on_segment=None):
     """The model loop of experiments/syn_env_run_vary_hp.py:47-117 as ONE fused launch: `agents_num` agents on every env of `train_envs`
     (loaded SE checkpoints of one experiment -- same shapes --, or the real env repeated: mode 0) = len(train_envs) * agents_num chains, chain
     (m, i) reading model m's weights.  Returns [train_test_agents(train_envs[m], ..., model_index=model_indices[m]) for m], bit for bit
-    (tests/test_run_vary_hp.py) -- where the reference spreads the models over a multiprocessing pool (:66-72,102-110), here they fill the GPU."""
+    (tests/test_run_vary_hp.py) -- where the reference spreads the models over a multiprocessing pool (:66-72,102-110), here they fill the GPU.
+    episodes_per_launch / on_segment: as train_test_agents."""
     if model_indices is None:
         model_indices = list(range(len(train_envs)))
-    return _launch(list(train_envs), test_env, config, agents_num, agent_name, train_episodes, vary_hp, seed, None, list(model_indices))
+    return _launch(list(train_envs), test_env, config, agents_num, agent_name, train_episodes, vary_hp, seed, None, list(model_indices),
+                   episodes_per_launch=episodes_per_launch, on_segment=on_segment)
 
 
-def _launch(train_envs, test_env, config, agents_num, agent_name, train_episodes, vary_hp, seed, replay, model_indices, settings=None):
+def _segment_keywords(task, episodes_per_launch, on_segment):
+    """(make_inner's keywords, run's keywords) of a launch in episode segments; two empty dicts for the single launch, so that a task or an
+    engine that knows nothing of segments is called as before."""
+    if episodes_per_launch is None:
+        return {}, {}
+    if int(episodes_per_launch) < 1:
+        raise ValueError("episodes_per_launch must be at least 1")
+    run_kw = dict(episodes_per_launch=int(episodes_per_launch), on_segment=on_segment)
+    if isinstance(task, tasks.Td3DiscreteTask):
+        return {}, run_kw
+    if isinstance(task, tasks.DdqnVaryTask):
+        return dict(segments=True), run_kw         # already on the GEMM-tiled kernel: the segment entry changes no bits
+    raise ValueError("episodes_per_launch: the '%s' launch (vary_hp off: the fixed-shape register-resident / wave-chain kernels) has no segment "
+                     "entry; run it without episodes_per_launch, or with vary_hp on" % task.name)
+
+
+def _launch(train_envs, test_env, config, agents_num, agent_name, train_episodes, vary_hp, seed, replay, model_indices, settings=None,
+            episodes_per_launch=None, on_segment=None):
     key = agent_name.lower()
     if key not in HARNESS_AGENTS:
         raise NotImplementedError("train_test_agents: agent '%s' (the harness scripts train %s)" % (agent_name, sorted(HARNESS_AGENTS)))
@@ -126,7 +152,8 @@ def _launch(train_envs, test_env, config, agents_num, agent_name, train_episodes
         task.cfg.rng_mode = 1
         if hasattr(task, "fixed_hp"):
             task.fixed_hp = list(replay["hp"])
-    inner = task.make_inner(chains, want_episode_stats=True)
+    inner_kw, run_kw = _segment_keywords(task, episodes_per_launch, on_segment)
+    inner = task.make_inner(chains, want_episode_stats=True, **inner_kw)
     keys = np.concatenate([chain_keys(int(seed), int(mi), np.arange(n_ag), np.zeros(n_ag, np.int64)) for mi in model_indices])
     keys_t = torch.from_numpy(keys.view(np.int64)).to(dev)
     if M == 1:
@@ -163,9 +190,9 @@ def _launch(train_envs, test_env, config, agents_num, agent_name, train_episodes
             rows.append(fresh_agent_init(task.agent_bounds, n_ag, g, dev))
         agent_init = torch.cat(rows)
     if replay is None:
-        task.scores(inner, theta, eps, worker, sign, keys_t, agent_init)
+        task.scores(inner, theta, eps, worker, sign, keys_t, agent_init, **run_kw)
     else:
-        _replay_launch(task, inner, theta, eps, worker, sign, keys_t, agent_init, replay)
+        _replay_launch(task, inner, theta, eps, worker, sign, keys_t, agent_init, replay, **run_kw)
     engine.check_status(inner)
     stats = inner.stats.cpu().numpy()
     finals = inner.final_returns.cpu().numpy()
@@ -248,8 +275,8 @@ def _pad_rows(rows, dtype, width=None):
     return torch.from_numpy(out).cuda()
 
 
-def _replay_launch(task, inner, theta, eps, worker, sign, keys_t, agent_init, replay):
-    """One tape-mode launch with the recorded hyper-parameters, fresh agents and RNG draws of a reference run."""
+def _replay_launch(task, inner, theta, eps, worker, sign, keys_t, agent_init, replay, **run_kw):
+    """One tape-mode launch with the recorded hyper-parameters, fresh agents and RNG draws of a reference run (run_kw: cut into segments)."""
     t = replay["tapes"]
     if "gumbel_act" in t:
         # the TD3-discrete loop's tapes (agents/TD3_discrete_vary.py: Gaussian action / policy noise and the Gumbel draws, one row per draw)
@@ -271,4 +298,4 @@ def _replay_launch(task, inner, theta, eps, worker, sign, keys_t, agent_init, re
     for i, a in enumerate(replay["agent_init"]):
         a = torch.from_numpy(np.ascontiguousarray(a, np.float32))
         init[i, :a.numel()] = a.to(init.device)
-    inner.run(theta, eps, worker, sign, init, tapes=tapes)
+    inner.run(theta, eps, worker, sign, init, tapes=tapes, **run_kw)

@@ -10,6 +10,8 @@ whose config has vary_hp off / on.  Where the reference loops over the models or
 `custom_train_test_agents` that carries a `.fused` attribute (this package's train_test_agents does) gets ALL models in one fused launch:
 model_num * agents_num chains, which is what fills an MI355X (40 models x 10 agents = 400 chains); any other callable is called model by
 model like the reference's pool-less branch.  `pool` is accepted and ignored (one process drives the GPU).
+episodes_per_launch / on_segment (not in the reference; None = the single launch): handed to `custom_train_test_agents` / its `.fused` as
+keywords, so that the launch of all models runs as a series of resumable segments (syn_env_evaluate.train_test_agents) -- same file.
 
 Several GPUs: inside a torch.distributed process group (one process per GPU, `torchrun ... -m learning_environments_amd.experiments.syn_env_run_vary_hp`)
 the models are dealt to the ranks round-robin (model m -> rank m mod N; the chains are keyed by (seed, model index, agent index), so the lists do not
@@ -51,9 +53,11 @@ def _ranks():
 
 
 def run_vary_hp(mode, experiment_name, model_num, agents_num, model_dir, custom_load_envs_and_config, custom_train_test_agents, env_name,
-                pool=None, device="cuda", filter_models_list=None, correlation_exp=False, out_dir=None):
+                pool=None, device="cuda", filter_models_list=None, correlation_exp=False, out_dir=None, episodes_per_launch=None, on_segment=None):
     if mode not in (0, 1, 2):
         raise ValueError("mode 0: real env, mode 1: syn. env. (no vary), mode 2: syn. env. (vary)")
+    # a harness function is called with the reference's arguments alone unless the launch is to run in segments
+    seg_kw = {} if episodes_per_launch is None else dict(episodes_per_launch=episodes_per_launch, on_segment=on_segment)
     train_on_venv = mode != 0
     with_vary_hp = mode == 2
     fused = getattr(custom_train_test_agents, "fused", None)
@@ -66,9 +70,9 @@ def run_vary_hp(mode, experiment_name, model_num, agents_num, model_dir, custom_
         names = [real_env.env.env_name + "_" + str(i) for i in range(model_num)]
         mine = list(range(rank, model_num, world))
         if fused is not None:
-            per_mine = fused([real_env] * len(mine), real_env, config, agents_num, model_indices=mine) if mine else []
+            per_mine = fused([real_env] * len(mine), real_env, config, agents_num, model_indices=mine, **seg_kw) if mine else []
         else:
-            per_mine = [custom_train_test_agents(train_env=real_env, test_env=real_env, config=config, agents_num=agents_num) for _ in mine]
+            per_mine = [custom_train_test_agents(train_env=real_env, test_env=real_env, config=config, agents_num=agents_num, **seg_kw) for _ in mine]
     else:
         names = get_all_files(with_vary_hp=with_vary_hp, model_num=model_num, model_dir=model_dir,
                               custom_load_envs_and_config=custom_load_envs_and_config, env_name=env_name, device=device,
@@ -79,11 +83,11 @@ def run_vary_hp(mode, experiment_name, model_num, agents_num, model_dir, custom_
         # harness function writes its settings for comparability into this very dict)
         config = loaded[0][2] if loaded else (custom_load_envs_and_config(file_name=names[0], model_dir=model_dir, device=device)[2] if names else None)
         if fused is not None and loaded:
-            per_mine = fused([l[0] for l in loaded], loaded[0][1], config, agents_num, model_indices=mine)
+            per_mine = fused([l[0] for l in loaded], loaded[0][1], config, agents_num, model_indices=mine, **seg_kw)
         else:
             per_mine = []
             for virtual_env, real_env, cfg_m in loaded:
-                per_mine.append(custom_train_test_agents(train_env=virtual_env, test_env=real_env, config=cfg_m, agents_num=agents_num))
+                per_mine.append(custom_train_test_agents(train_env=virtual_env, test_env=real_env, config=cfg_m, agents_num=agents_num, **seg_kw))
                 if world == 1:
                     config = cfg_m
     if world > 1:
@@ -134,6 +138,9 @@ def main(argv=None):
     parser.add_argument('--agent', type=str, default='DDQN_vary', help='the sibling script: ' + ', '.join(sorted(HARNESS_AGENTS)))
     parser.add_argument('--train_episodes', type=int, default=1000, help='1000; the Acrobot TD3_discrete script uses 500')
     parser.add_argument('--out_dir', type=str, default=None)
+    parser.add_argument('--episodes_per_launch', type=int, default=None,
+                        help='run every launch as a series of resumable segments of this many training episodes (same results; one progress line '
+                             'per segment).  TD3_discrete_vary, and the DDQN agents in the modes with vary_hp on; default: one launch')
     parser.add_argument('--generalization_gap', action='store_true',
                         help='the *_eval_generalization_gap script: vary_hp off, the fixed optimised DDQN hyper-parameters (4-57-2 tanh, batch 199)')
     parser.add_argument('--correlation', action='store_true',
@@ -141,6 +148,9 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.agent.lower() not in HARNESS_AGENTS:
         parser.error("unknown --agent %r (one of %s)" % (args.agent, sorted(HARNESS_AGENTS)))
+    if args.episodes_per_launch is not None and (args.correlation or args.generalization_gap or args.episodes_per_launch < 1):
+        parser.error("--episodes_per_launch needs a positive count and the plain harness (the --correlation / --generalization_gap launches "
+                     "run fixed-shape agents on kernels without a segment entry)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         # under torchrun: one process per GPU; the only exchange is one all_gather_object of python lists per mode (gloo carries it)
         import torch
@@ -168,7 +178,10 @@ def main(argv=None):
     for mode in ([args.mode] if args.mode is not None else range(3)):
         out[mode] = run_vary_hp(mode=mode, experiment_name=experiment_name, model_num=args.model_num, agents_num=args.agents_num,
                                 model_dir=args.model_dir, custom_load_envs_and_config=load_envs_and_config, custom_train_test_agents=harness,
-                                env_name=args.env_name, pool=None, device=args.device, out_dir=args.out_dir)
+                                env_name=args.env_name, pool=None, device=args.device, out_dir=args.out_dir,
+                                episodes_per_launch=args.episodes_per_launch,
+                                on_segment=lambda done, finished, mode=mode: print("mode %d: %d of %d training episodes launched, %d agents finished"
+                                                                                   % (mode, done, args.train_episodes, finished), flush=True))
         print("mode %d: %d agents, mean test return %.2f" % (mode, len(out[mode][0]), float(np.mean([np.mean(r) for r in out[mode][0]]))))
     return out
 

@@ -201,6 +201,92 @@ def run_td3_episode_time(name, cfgd, shape, chains=8, timed=2):
     return out
 
 
+def _td3d_loop(chains, episodes, real_env=False, init_episodes=6, max_steps=None, seed=0):
+    """A Td3DiscreteInnerLoop at the histogram scripts' shape (`td3_discrete_vary_layer_norm_2`: 4-128-128-2 tanh with LayerNorm, the agent section
+    of fixture g12t) as the evaluation harness launches it -- test_mode 1, every chain its own key and freshly drawn agent -- on the reference-written
+    CartPole SE checkpoint of the test suite (its config: episodes of 40 steps; max_steps: another length, CartPole-v0's own is 200), or on the
+    real CartPole (a RewardEnv of type 0); no early out.  (inner loop, run arguments, keywords)"""
+    import numpy as np
+    from learning_environments_amd import engine
+    from learning_environments_amd.config import td3d_cfg_from_config, td3d_rn_cfg_from_config
+    golden = os.path.join(ROOT, "tests", "golden")
+    save = torch.load(os.path.join(golden, "ckpt_cartpole_se_reference_b.pt"), map_location="cpu", weights_only=False)
+    cfgd = save["config"]
+    g = np.load(os.path.join(golden, "g12t_train_test_agents_cartpole_mode2_td3_discrete_vary.npz"), allow_pickle=True)
+    cfgd["agents"]["td3_discrete_vary"] = dict(json.loads(str(g["config_json"]))["agents"]["td3_discrete_vary"], train_episodes=episodes,
+                                               init_episodes=init_episodes, early_out_num=10, early_out_virtual_diff=0.0, vary_hp=False)
+    cfgd["agents"]["gtn"] = dict(cfgd["agents"].get("gtn", {}), agent_name="td3_discrete_vary", synthetic_env_type=1 if real_env else 0)
+    e = cfgd["envs"][cfgd["env_name"]]
+    e["solved_reward"] = 1e9
+    if max_steps is not None:
+        e["max_steps"] = max_steps
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    rn = None
+    if real_env:
+        e["reward_env_type"] = 0
+        rn = td3d_rn_cfg_from_config(cfgd)
+    cfg = td3d_cfg_from_config(cfgd, test_mode=1)
+    il = engine.Td3DiscreteInnerLoop(cfg, chains, want_episode_stats=True, want_final_params=True, rn=rn)
+    theta = torch.zeros(il.p_theta, dtype=torch.float32, device="cuda") if real_env else dev(g["theta"])
+    keys = dev(np.array([engine.chain_key(17 + seed, 0, c, 0) for c in range(chains)], np.uint64).view(np.int64))
+    il.draw_agent_init(keys)
+    return il, (theta, None, None, None, None), dict(rng_keys=keys)
+
+
+def run_td3d_entry_builds(name, loop, other_lib, runs=7):
+    """The single-launch entry of `loop` on this build against the same entry of another build of the library (the parent commit's: its path is
+    the caller's), a warm-up of each, then `runs` alternating launches; medians, the runs' ranges and whether the outputs agree bit for bit."""
+    import ctypes as C
+    from learning_environments_amd import _lib
+    il, pos, kw = loop
+    args = il._launch_args(*pos, kw["rng_keys"], None)
+    fn_name = il.entry[0]
+    other = C.CDLL(os.path.abspath(other_lib))
+    fns = {"this_build": getattr(_lib.lib(), fn_name), "other_build": getattr(other, fn_name)}
+    fns["other_build"].restype, fns["other_build"].argtypes = _lib.SIGNATURES[fn_name]
+    times, snaps = {k: [] for k in fns}, {}
+    for r in range(runs + 1):
+        for k, fn in fns.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _lib.check(fn(C.byref(il.cfg), *il._prefix_args(), *args), k)
+            torch.cuda.synchronize()
+            if r:
+                times[k].append(time.perf_counter() - t0)
+            snaps[k] = [getattr(il, n).cpu().numpy().tobytes() for n in ("score", "stats", "status", "episode_test_mean", "episode_len", "final_params")]
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    out = dict(config=name, entry=fn_name, runs_each=runs, s_median=med, s_min={k: min(v) for k, v in times.items()},
+               s_max={k: max(v) for k, v in times.items()}, s_spread={k: max(v) - min(v) for k, v in times.items()},
+               s_samples={k: [round(t, 5) for t in v] for k, v in times.items()}, ratio_this_to_other=med["this_build"] / med["other_build"],
+               difference_inside_the_runs_spread=bool(abs(med["this_build"] - med["other_build"]) <= max(max(v) - min(v) for v in times.values())),
+               bit_identical=snaps["this_build"] == snaps["other_build"], status_ok=bool(int(il.status.min()) == 0))
+    print(json.dumps(out))
+    return out
+
+
+def run_td3d_episode_time(name, loop):
+    """Seconds per FULL-LENGTH learning episode (max_steps agent steps, each with a learn step) of the harness's TD3_discrete chains: segment
+    launches of one episode each, every one timed.  A workgroup per chain, so a segment takes what its longest chain takes; the figure is the
+    median over the learning segments in which some chain ran max_steps steps, beside every learning segment's time scaled to max_steps by its
+    longest chain's length."""
+    il, pos, kw = loop
+    E, full_len, init = il.cfg.train_episodes, il.cfg.max_steps, il.cfg.init_episodes
+    times = _timed_segments(il, pos, kw, E)
+    fin, status = il.segment_state()
+    longest = il.episode_len.cpu().numpy().max(axis=0)
+    full = sorted(t for t, n in zip(times[init:], longest[init:]) if n == full_len)
+    scaled = sorted(t * full_len / n for t, n in zip(times[init:], longest[init:]))
+    st = il.stats.cpu().numpy()
+    out = dict(config=name, chains=il.chains, episodes=E, init_episodes=init, max_steps=full_len, full_length_segments=len(full),
+               s_per_full_length_episode=full[len(full) // 2] if full else None, s_full_min=full[0] if full else None, s_full_max=full[-1] if full else None,
+               s_scaled_to_full_length_median=scaled[len(scaled) // 2], s_scaled_to_full_length_min=scaled[0], s_scaled_to_full_length_max=scaled[-1],
+               s_init_episode_median=sorted(times[1:init])[len(times[1:init]) // 2] if init > 1 else None,
+               longest_chain_steps_per_learning_segment=[int(n) for n in longest[init:]], status_ok=bool(int(status.min()) == 0),
+               finished=int(fin.sum()), train_steps_per_chain=float(st[:, 1].mean()), learn_steps_per_chain=float(st[:, 2].mean()))
+    print(json.dumps(out))
+    return out
+
+
 def _dueling_loop(cfgd, chains, shape, seed=0, lr=None):
     """An InnerLoop built for segments (the generic GEMM-tiled kernel, per-chain hyper-parameter arrays with `shape` = (hidden, layers, batch) for
     every chain, as experiments/transfer_cartpole.py launches its agents) with seeded inputs: (inner loop, run arguments, keyword arguments)."""
@@ -897,6 +983,28 @@ if __name__ == "__main__":
         c["envs"]["MountainCarContinuous-v0"]["max_steps"] = 200
         run_segments("MountainCarContinuous SE + TD3 (B 256) 48 chains, 60 episodes x 100 agent steps: 1 launch / 1 segment / 6 segments",
                      _td3_loop(c, 48, train_episodes=60), "final_params", 60, 6)
+    if "td3d_segments" in which:
+        # the evaluation harness's TD3_discrete chains (4-128-128-2 tanh with LayerNorm, test_mode 1) on the reference-written CartPole SE, 48 chains,
+        # 60 episodes (6 init episodes) of 40 steps, the checkpoint's max_steps (this SE never reports done): the old entry, one segment, six segments; then the same with ONE chain (no chain
+        # waits for another at a boundary: what is left is the cost of splitting itself)
+        run_segments("CartPole SE + TD3_discrete 128x2 LayerNorm, 48 chains, 60 episodes x 40 steps: 1 launch / 1 segment / 6 segments",
+                     _td3d_loop(48, 60), "final_params", 60, 6, boundary_wait=True)
+        run_segments("CartPole SE + TD3_discrete 128x2 LayerNorm, 1 chain, 60 episodes x 40 steps: 1 launch / 1 segment / 6 segments",
+                     _td3d_loop(1, 60), "final_params", 60, 6, boundary_wait=True)
+    if "td3d_entry_builds" in which:
+        # the two old entries on this build against another build of the library (usage: td3d_entry_builds <path of the other .so>): the workload of
+        # td3d_segments on the SE, and 48 chains x 30 episodes on the real CartPole for the RENV instantiation
+        other = os.path.join(ROOT, which[which.index("td3d_entry_builds") + 1])            # (an absolute path stays what it is)
+        run_td3d_entry_builds("lenv_td3d_inner_loop, CartPole SE + TD3_discrete 128x2 LayerNorm, 48 chains, 60 episodes: this build / the other build",
+                              _td3d_loop(48, 60), other)
+        run_td3d_entry_builds("lenv_td3d_rn_inner_loop, real CartPole + TD3_discrete 128x2 LayerNorm, 48 chains, 30 episodes: this build / the other build",
+                              _td3d_loop(48, 30, real_env=True), other)
+    if "td3d_episode_time" in which:
+        # a full-length learning episode of the harness's chains, on the SE and on the real CartPole (10 init episodes as the comparability block sets)
+        # and CartPole-v0's 200 steps per episode
+        run_td3d_episode_time("CartPole SE (200 steps) + TD3_discrete 128x2 LayerNorm, 8 chains", _td3d_loop(8, 25, init_episodes=10, max_steps=200))
+        run_td3d_episode_time("real CartPole (200 steps) + TD3_discrete 128x2 LayerNorm, 8 chains",
+                              _td3d_loop(8, 25, real_env=True, init_episodes=10, max_steps=200))
     if "td3_episode_time" in which:
         # the TD3 *_transfer_vary_hp scripts' chains (a RewardEnv on the real env, full-length episodes): the nominal shape and the largest one
         # their hyper-parameter draw can give (hidden 384, 3 layers, batch 768)
