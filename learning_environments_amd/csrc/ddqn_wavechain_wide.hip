@@ -20,6 +20,7 @@
 // three team barriers per learn step (head outputs exchanged; d_h1 / d_h2 rows complete; parameters updated).  Everything outside the learn
 // step (SE step, greedy action, test episodes) runs redundantly on every member, as in dueling_wavechain.hip.
 #include "lenv_wavechain.cuh"
+#include "lenv_chain_frame.cuh"
 #include "lenv_wavechain_host.h"
 #include "lenv_host.h"
 
@@ -808,45 +809,16 @@ __global__ __launch_bounds__(NT) void ddqn_wavechain_wide_kernel(const WwArgs a)
     const int test_before = test_steps;
     if (!team_dead) test_phase();
     if (budgeted) {
-        if (tid == 0) {
-            int64_t used = 0;
-            int stop = T;
-            for (int te = 0; te < T; ++te) {
-                if (used > remaining) { stop = te; break; }
-                used += tlen[te];
-            }
-            double mn = -1e9;
-            if (stop > 0) { mn = ret[0]; for (int i = 1; i < stop; ++i) if (ret[i] < mn) mn = ret[i]; }
-            for (int te = stop; te < T; ++te) ret[te] = mn;
-            ictrl[4] = (int)used;
+        if (tid == 0) {                                   // thread 0 counts and pads, ictrl[4] carries `used` to the others
+            const BudgetCut cut = chain_budget_cut(tlen, T, remaining);
+            chain_pad_returns(ret, cut.stop, T);
+            ictrl[4] = (int)cut.used;
         }
         __syncthreads();
         test_steps = test_before + ictrl[4];
     }
-    if (tid == 0 && g == 0) {
-        double sm = 0.0;
-        for (int i = 0; i < T; ++i) sm += ret[i];
-        a.out.score[chain] = sm / (double)T;
-        if (a.out.final_returns) for (int i = 0; i < T; ++i) a.out.final_returns[chain * T + i] = ret[i];
-        if (a.out.stats) {
-            a.out.stats[chain * 4 + 0] = episodes_run; a.out.stats[chain * 4 + 1] = train_steps;
-            a.out.stats[chain * 4 + 2] = learn_it; a.out.stats[chain * 4 + 3] = test_steps;
-        }
-        double pad_r = __builtin_nan("");
-        int pad_l = 0;
-        if (timed_out_at >= 0) {
-            pad_r = -1e9; pad_l = 1000000000;
-            if (episodes_run > 0) { pad_r = meter[0]; for (int i = 1; i < episodes_run; ++i) if (meter[i] < pad_r) pad_r = meter[i]; }
-            if (episodes_run > 0 && a.out.episode_len) {
-                pad_l = a.out.episode_len[chain * cfg.train_episodes];
-                for (int i = 1; i < episodes_run; ++i) { const int l = a.out.episode_len[chain * cfg.train_episodes + i]; if (l > pad_l) pad_l = l; }
-            }
-        }
-        for (int e = episodes_run; e < cfg.train_episodes; ++e) {
-            if (a.out.episode_test_mean) a.out.episode_test_mean[chain * cfg.train_episodes + e] = pad_r;
-            if (a.out.episode_len) a.out.episode_len[chain * cfg.train_episodes + e] = pad_l;
-        }
-    }
+    if (tid == 0 && g == 0)
+        chain_close(a.out, chain, T, ret, meter, cfg.train_episodes, episodes_run, train_steps, learn_it, test_steps, timed_out_at);
     if (a.out.final_online && g == 0)
         for (int p = tid; p < a.P; p += NT) a.out.final_online[chain * a.P + p] = online[ww_sd_to_arena(p)];
     if (a.out.status && status != 0) atomicMin(&a.out.status[chain], status);

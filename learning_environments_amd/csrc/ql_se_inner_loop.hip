@@ -20,6 +20,7 @@
 // with one workgroup barrier behind each.  Every dot product is the canonical order of oracle/lenv_oracle.h (orc_mlp_forward) and of
 // se_step_kernel, so the SE outputs equal lenv_se_step_population's bit for bit.  docs/notebook_ql_se.md has the layout's reasoning.
 #include "lenv_device.cuh"
+#include "lenv_chain_frame.cuh"
 #include "lenv_host.h"
 
 namespace lenv {
@@ -352,24 +353,8 @@ __global__ __launch_bounds__(QSE_NT_MAX) void ql_se_inner_kernel(const QlSeArgs 
     test_phase(cfg.step_budget > 0, cfg.step_budget - (train_steps + test_steps));
     a.out.score[chain] = mean_rets();
     if (a.out.final_returns) for (int i = 0; i < cfg.test_episodes; ++i) a.out.final_returns[chain * cfg.test_episodes + i] = rets[i];
-    if (a.out.stats) {
-        a.out.stats[chain * 4 + 0] = episodes_run; a.out.stats[chain * 4 + 1] = train_steps;
-        a.out.stats[chain * 4 + 2] = learn_steps; a.out.stats[chain * 4 + 3] = test_steps;
-    }
-    double pad_r = __builtin_nan("");
-    int pad_l = 0;
-    if (timed_out_at >= 0) {                                               // time_is_up's padding, base_agent.py:33-44
-        pad_r = -1e9; pad_l = 1000000000;
-        if (episodes_run > 0) { pad_r = meter[0]; for (int i = 1; i < episodes_run; ++i) if (meter[i] < pad_r) pad_r = meter[i]; }
-        if (episodes_run > 0 && a.out.episode_len) {
-            pad_l = a.out.episode_len[chain * cfg.train_episodes];
-            for (int i = 1; i < episodes_run; ++i) { const int l = a.out.episode_len[chain * cfg.train_episodes + i]; if (l > pad_l) pad_l = l; }
-        }
-    }
-    for (int e = episodes_run; e < cfg.train_episodes; ++e) {
-        if (a.out.episode_test_mean) a.out.episode_test_mean[chain * cfg.train_episodes + e] = pad_r;
-        if (a.out.episode_len) a.out.episode_len[chain * cfg.train_episodes + e] = pad_l;
-    }
+    chain_write_stats(a.out, chain, episodes_run, train_steps, learn_steps, test_steps);
+    chain_pad_episodes(a.out, chain, cfg.train_episodes, episodes_run, meter, timed_out_at);
     if (a.out.q_table) for (int i = 0; i < N * A; ++i) a.out.q_table[chain * N * A + i] = q[i];
     if (a.out.status) a.out.status[chain] = status;
 }

@@ -17,6 +17,7 @@
 // Arena layout of ONE network (actor, critic_1, critic_2 alike; every matrix K-MAJOR):
 //   W1t[24][128] (rows >= in_dim zero) b1[128] | W2t[128][128] b2[128] | Wo[128][8] (columns >= out_dim zero) bo[8]
 #include "lenv_wavechain.cuh"
+#include "lenv_chain_frame.cuh"
 #include "lenv_wavechain_host.h"
 #include "lenv_host.h"
 
@@ -1600,48 +1601,17 @@ __global__ __launch_bounds__(NT) void td3_wavechain_kernel(const T3wArgs a)
     const int test_before = test_steps;
     if (!team_dead) test_phase();
     if (budgeted) {
-        int64_t used = 0;
-        int stop = T;
-        for (int te = 0; te < T; ++te) {
-            if (used > remaining) { stop = te; break; }
-            used += tlen[te];
-        }
-        if (tid == 0) {
-            double mn = -1e9;
-            if (stop > 0) { mn = ret[0]; for (int i = 1; i < stop; ++i) if (ret[i] < mn) mn = ret[i]; }
-            for (int te = stop; te < T; ++te) ret[te] = mn;
-        }
-        test_steps = test_before + (int)used;
+        const BudgetCut cut = chain_budget_cut(tlen, T, remaining);      // every thread counts, thread 0 pads
+        if (tid == 0) chain_pad_returns(ret, cut.stop, T);
+        test_steps = test_before + (int)cut.used;
         __syncthreads();
     }
     TPT_MARK(9);
 #if defined(LENV_PHASE_TIMING) && !defined(LENV_PHASE_TIMING_SUB)
     if (tid == 0 && chain == 0) { for (int pi = 0; pi < 12; ++pi) g_t3w_phase_cycles[pi] = pt_acc[pi]; g_t3w_phase_cycles[11] = bar_cycles; }
 #endif
-    if (tid == 0 && g == 0) {
-        double sm = 0.0;
-        for (int i = 0; i < T; ++i) sm += ret[i];
-        a.out.score[chain] = sm / (double)T;
-        if (a.out.final_returns) for (int i = 0; i < T; ++i) a.out.final_returns[chain * T + i] = ret[i];
-        if (a.out.stats) {
-            a.out.stats[chain * 4 + 0] = episodes_run; a.out.stats[chain * 4 + 1] = train_steps;
-            a.out.stats[chain * 4 + 2] = learn_it; a.out.stats[chain * 4 + 3] = test_steps;
-        }
-        double pad_r = __builtin_nan("");
-        int pad_l = 0;
-        if (timed_out_at >= 0) {
-            pad_r = -1e9; pad_l = 1000000000;
-            if (episodes_run > 0) { pad_r = meter[0]; for (int i = 1; i < episodes_run; ++i) if (meter[i] < pad_r) pad_r = meter[i]; }
-            if (episodes_run > 0 && a.out.episode_len) {
-                pad_l = a.out.episode_len[chain * cfg.train_episodes];
-                for (int i = 1; i < episodes_run; ++i) { const int l = a.out.episode_len[chain * cfg.train_episodes + i]; if (l > pad_l) pad_l = l; }
-            }
-        }
-        for (int e = episodes_run; e < cfg.train_episodes; ++e) {
-            if (a.out.episode_test_mean) a.out.episode_test_mean[chain * cfg.train_episodes + e] = pad_r;
-            if (a.out.episode_len) a.out.episode_len[chain * cfg.train_episodes + e] = pad_l;
-        }
-    }
+    if (tid == 0 && g == 0)
+        chain_close(a.out, chain, T, ret, meter, cfg.train_episodes, episodes_run, train_steps, learn_it, test_steps, timed_out_at);
     if (a.out.final_params && g == 0) {
         for (int p = tid; p < a.P; p += NT) {
             int q;

@@ -3011,6 +3011,69 @@ def test_wavechain_td3_pendulum_shape_every_team_size(eng, orc):
         assert np.array_equal(ref[4][c], o["final_params"])
 
 
+def test_wavechain_td3_step_budget_equals_gemm_queue_kernel(eng, orc):
+    """lenv_td3_cfg::step_budget on the TD3 wave-chain kernel (the Pendulum RewardEnv shape: ten test episodes; the automatic team and one
+    workgroup per chain) against kernel_variant NO_WAVECHAIN (the GEMM-queue kernel, held to the oracle by
+    test_step_budget_other_kernels_vs_oracle), every output bit for bit.  Two budgets, both derived from the step counts of an unbudgeted run
+    of the same cfg: one that one training episode with its tests just fits (the check in front of an episode asks `steps so far > budget`, so
+    the chains time out in front of the second or third of four episodes and the per-episode lists are padded), and one that lets training
+    finish and leaves the final test the steps of about three of its ten episodes."""
+    import ctypes as C
+    from learning_environments_amd import _lib, configs
+    from learning_environments_amd.agents.nes_common import chain_keys
+    E, chains = 4, 4
+    cfgd = configs.fixed_work(configs.pendulum_reward_env_td3(2), E)
+    cfgd["agents"]["td3"]["init_episodes"] = 1
+    cfgd["envs"]["Pendulum-v0"]["max_steps"] = 20
+    ocfg, cfg = _td3_cfgs(orc, cfgd, 0)
+    T = cfg.test_episodes
+    assert (cfg.hidden, cfg.layers, cfg.batch_size, T, cfg.rn_layers) == (128, 2, 192, 10, 2)
+    Pa, Pc = orc.td3_param_counts(ocfg)
+    P_rn = orc.rn_num_params(2, 3, 0, 128, 2)
+    rng = np.random.RandomState(19)
+    theta = (rng.randn(P_rn) * 0.1).astype(np.float32)
+    eps = (rng.randn(2, P_rn) * 0.05).astype(np.float32)
+    worker = (np.arange(chains) // 3).astype(np.int32)
+    sign = np.tile(np.array([0.0, 1.0, -1.0], np.float32), 2)[:chains].copy()
+    keys = chain_keys(83, 2, worker, np.arange(chains) % 3)
+    init = rng.uniform(-0.08, 0.08, (chains, Pa + 2 * Pc)).astype(np.float32)
+    names = ("score", "stats", "episode_test_mean", "episode_len", "final_returns", "final_params")
+
+    def run(budget, variant, team_size):
+        cfg.step_budget, cfg.kernel_variant, cfg.team_size = budget, variant, team_size
+        il = eng.Td3InnerLoop(cfg, chains, want_final_params=True, want_episode_stats=True)
+        il.run(dev(theta), dev(eps), dev(worker), dev(sign), dev(init), rng_keys=dev(keys.view(np.int64)))
+        torch.cuda.synchronize()
+        assert il.status.cpu().tolist() == [0] * chains
+        return dict(zip(names, (t.cpu().numpy().copy() for t in (il.score, il.stats, il.episode_test_mean, il.episode_len, il.final_returns,
+                                                                 il.final_params))))
+
+    free = run(0, _lib.VARIANT_NO_WAVECHAIN, 0)
+    assert (free["stats"][:, 0] == E).all()
+    final_len = np.full(chains, T * cfg.max_steps, np.int64)                 # Pendulum-v0 never terminates: every test episode runs max_steps
+    before_final = free["stats"][:, 1] + free["stats"][:, 3] - final_len     # env steps in front of the final test
+    budgets = {"training": int(before_final.min()) // E, "final_test": int(before_final.max()) + 3 * int(final_len.min()) // T}
+    for which, budget in budgets.items():
+        ref = run(budget, _lib.VARIANT_NO_WAVECHAIN, 0)
+        if which == "training":
+            ran = ref["stats"][:, 0]
+            assert ((ran >= 1) & (ran <= 2) & (ran < E)).all(), ran.tolist()
+            for c in range(chains):                                        # time_is_up's padding: minimum of the means, maximum of the lengths
+                n = int(ran[c])
+                assert (ref["episode_test_mean"][c, n:] == ref["episode_test_mean"][c, :n].min()).all()
+                assert (ref["episode_len"][c, n:] == ref["episode_len"][c, :n].max()).all()
+        else:
+            assert (ref["stats"][:, 0] == E).all()
+            used = ref["stats"][:, 1] + ref["stats"][:, 3] - before_final
+            assert ((used > 0) & (used < final_len)).all(), used.tolist()   # the final test stopped between its episodes 1 and T - 1
+        cfg.step_budget, cfg.kernel_variant, cfg.team_size = budget, 0, 0
+        assert _lib.lib().lenv_td3_rn_team_size(C.byref(cfg), chains) > 1
+        for team_size in (0, 1):
+            got = run(budget, 0, team_size)
+            for name in names:
+                assert np.array_equal(got[name], ref[name], equal_nan=True), (which, team_size, name)
+
+
 def test_wavechain_td3_cmc_shape_every_team_size(eng, orc):
     """The TD3 wave-chain kernel's third shape -- default_config_cmc_reward_env.yaml: MountainCarContinuous-v0 (an env that TERMINATES: the
     episode ends at the flag), actor 2-128-128-1, twin critics 3-128-128-1, leakyrelu, batch 192, one test episode, tanh reward net with one

@@ -136,6 +136,58 @@ def test_wavechain_wide_every_team_size_equals_gemm_queue_and_oracle(eng, orc, c
         assert np.array_equal(ref[5][c], o["final_online"])
 
 
+def test_wavechain_wide_step_budget_equals_gemm_queue(eng, orc):
+    """lenv_ddqn_cfg::step_budget on the wave-chain kernel (teams of four, and one workgroup per chain) against kernel_variant NO_WAVECHAIN
+    (the GEMM-queue kernel, held to the oracle by test_gpu_parity.py's budget tests), every output bit for bit.  Two budgets, both derived from
+    the step counts of an unbudgeted run of the same cfg: one that one training episode with its tests just fits (the check in front of an
+    episode asks `steps so far > budget`, so the chains time out in front of the second or third of four episodes and the per-episode lists
+    are padded), and one that lets training finish and leaves the final test the steps of about three of its ten episodes."""
+    from learning_environments_amd import _lib, configs
+    from learning_environments_amd.config import ddqn_cfg_from_config
+    E, chains = 4, 3
+    cfgd = configs.fixed_work(configs.mountaincar_syn_env_ddqn(4), E)
+    cfgd["agents"]["ddqn"].update(init_episodes=1, rb_size=60)
+    cfgd["envs"]["MountainCar-v0"]["max_steps"] = 30
+    cfg = ddqn_cfg_from_config(cfgd)
+    T = cfg.test_episodes
+    theta, eps, worker, sign, agent_init, keys = _chain_inputs(orc, cfg, chains, 33, -10.0)
+    names = ("score", "stats", "episode_test_mean", "episode_len", "final_returns", "final_online")
+
+    def run(budget, variant, team_size):
+        cfg.step_budget, cfg.kernel_variant, cfg.team_size = budget, variant, team_size
+        il = eng.InnerLoop(cfg, chains, want_final_online=True)
+        il.run(dev(theta), dev(eps), dev(worker), dev(sign), dev(agent_init), rng_keys=dev(keys.view(np.int64)))
+        torch.cuda.synchronize()
+        assert il.status.cpu().tolist() == [0] * chains
+        return dict(zip(names, (t.cpu().numpy().copy() for t in (il.score, il.stats, il.episode_test_mean, il.episode_len, il.final_returns,
+                                                                 il.final_online))))
+
+    free = run(0, _lib.VARIANT_NO_WAVECHAIN, 0)
+    assert (free["stats"][:, 0] == E).all()
+    final_len = (-free["final_returns"]).sum(axis=1).astype(np.int64)        # MountainCar-v0 pays -1 per step: |return| = length
+    before_final = free["stats"][:, 1] + free["stats"][:, 3] - final_len     # env steps in front of the final test
+    budgets = {"training": int(before_final.min()) // E, "final_test": int(before_final.max()) + 3 * int(final_len.min()) // T}
+    for which, budget in budgets.items():
+        ref = run(budget, _lib.VARIANT_NO_WAVECHAIN, 0)
+        if which == "training":
+            ran = ref["stats"][:, 0]
+            assert ((ran >= 1) & (ran <= 2) & (ran < E)).all(), ran.tolist()
+            for c in range(chains):                                        # time_is_up's padding: minimum of the means, maximum of the lengths
+                n = int(ran[c])
+                assert (ref["episode_test_mean"][c, n:] == ref["episode_test_mean"][c, :n].min()).all()
+                assert (ref["episode_len"][c, n:] == ref["episode_len"][c, :n].max()).all()
+        else:
+            assert (ref["stats"][:, 0] == E).all()
+            used = ref["stats"][:, 1] + ref["stats"][:, 3] - before_final
+            assert ((used > 0) & (used < final_len)).all(), used.tolist()   # the final test stopped between its episodes 1 and T - 1
+        cfg.step_budget, cfg.kernel_variant, cfg.team_size = budget, 0, 0
+        assert _lib.lib().lenv_dueling_team_size(C.byref(cfg), chains) == 4
+        for team_size in (0, 1):
+            got = run(budget, 0, team_size)
+            for name in names:
+                assert np.array_equal(got[name], ref[name], equal_nan=True), (which, team_size, name)
+
+
 def test_gtn_generation_wavechain_equals_no_wavechain():
     """One GTN_Master generation of configs.mountaincar_syn_env_ddqn(16) in fixed-work form (48 chains, teams of four): the wave-chain
     kernel and kernel_variant NO_WAVECHAIN (the GEMM-queue kernel) leave the same updated theta and chain outputs, bit for bit."""
