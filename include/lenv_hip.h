@@ -1055,6 +1055,45 @@ int lenv_cont_env_reset(int32_t env_id, const uint64_t *keys, const int64_t *epi
 int lenv_cont_env_step(int32_t env_id, int32_t max_steps, int64_t n, const float *action, double *state, int32_t *elapsed,
                        float *obs, float *reward, float *done, void *stream);
 
+/*
+ * Supervised fit of `models` VirtualEnvs on recorded transitions: the "Supervised Learning / MBRL Baseline" of the reference's README, whose
+ * experiments/syn_env_evaluate_cartpole_mbrl_baseline.py leaves fit_mbrl_baseline() unimplemented.  The three descs are the state, reward and
+ * done net of a VirtualEnv (envs/virtual_env.py:16-33); theta [models, P] holds their parameters in the SE layout state | reward | done
+ * (P = lenv_se_fit_num_params), adam_m / adam_v [models, P] the moments; all three are read and written.  x [N, in_dim] are the nets' inputs
+ * cat(action, state), y_state [N, S], y_reward [N], y_done [N] the targets.
+ *
+ * Model m takes the Adam steps step_begin .. step_end-1 (torch.optim.Adam's single-tensor step, torch defaults for what is not an argument;
+ * beta^t by repeated multiplication in double from step 0, so a fit cut into consecutive calls that hand theta and the moments on is the fit
+ * in one call) on loss_k = F.mse_loss(net_k(x_b), y_k_b), one loss per net: the nets share no parameter, so this is one Adam over their sum.
+ * Step t uses `batch` rows drawn with replacement: batch_idx [models, step_end-step_begin, batch] where given (tape mode; an index outside
+ * [0, N) reads the nearest row), else row u64_to_below(rng_u64(rng_keys[m], 15, t * batch + j), N) for j < batch (counter mode).  Exactly one
+ * of rng_keys / batch_idx is given.  loss [models, step_end-step_begin, 3] (may be NULL) receives the three means BEFORE the step.
+ *
+ * Arithmetic order (restated on the CPU by tests/se_fit_ref.c, which the kernel equals bit for bit): the forward is lenv_mlp_forward's, so a
+ * fitted model steps exactly as lenv_mlp_forward / lenv_se_step_population compute it; the squared errors are summed by an fmaf chain over
+ * rows ascending and outputs ascending inside a row, then divided by (float)(batch * out_dim); dL/dy = (float)(2.0 / (double)(batch * out_dim))
+ * * e; every weight and bias gradient is a chain over the minibatch rows in ascending order.
+ *
+ * Shapes: equal in_dim (1..32), hidden (1..128), layers (1..2) and act (identity, relu, leakyrelu, tanh) on the three descs, state out_dim
+ * 1..32, reward and done out_dim 1, batch 1..256; LENV_ERR_UNSUPPORTED beyond that: PReLU (torch would train the slope, theta has no place
+ * for it), use_layer_norm, three hidden layers, models or N >= 2^31.  One workgroup per (model, net); a net's parameters, moments and
+ * gradient stay in LDS where they fit behind the minibatch activations (lenv_se_fit_lds_bytes), else the gradient lives in the workspace
+ * (lenv_se_fit_workspace_bytes, 0 for a launch that needs none; `workspace` may then be NULL): the bits are the same on either path.
+ * LENV_ERR_INVALID: a NULL desc, a NULL data array with N > 0, N < 1 with step_end > step_begin, step_begin < 0, step_end < step_begin,
+ * models < 0, a NULL theta / adam_m / adam_v with models > 0, both or neither of rng_keys / batch_idx.  LENV_ERR_WORKSPACE: a workspace
+ * smaller than the query's.  models == 0 or step_end == step_begin: LENV_OK after these checks, without a launch.
+ */
+int64_t lenv_se_fit_num_params(const lenv_mlp_desc *state_net /*HOST*/, const lenv_mlp_desc *reward_net /*HOST*/, const lenv_mlp_desc *done_net /*HOST*/);
+int64_t lenv_se_fit_lds_bytes(const lenv_mlp_desc *state_net /*HOST*/, const lenv_mlp_desc *reward_net /*HOST*/, const lenv_mlp_desc *done_net /*HOST*/,
+                              int32_t batch);
+int64_t lenv_se_fit_workspace_bytes(const lenv_mlp_desc *state_net /*HOST*/, const lenv_mlp_desc *reward_net /*HOST*/,
+                                    const lenv_mlp_desc *done_net /*HOST*/, int32_t batch, int64_t models);
+int lenv_se_fit_population(const lenv_mlp_desc *state_net /*HOST*/, const lenv_mlp_desc *reward_net /*HOST*/, const lenv_mlp_desc *done_net /*HOST*/,
+                           const float *x, const float *y_state, const float *y_reward, const float *y_done, int64_t N, int32_t batch,
+                           int64_t step_begin, int64_t step_end, double lr, double beta1, double beta2, double adam_eps,
+                           const uint64_t *rng_keys, const int32_t *batch_idx, int64_t models, float *theta, float *adam_m, float *adam_v,
+                           float *loss, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Counter-RNG key of a chain (same function as the oracle's): kind 0 = theta, 1 = theta+eps, 2 = theta-eps. HOST. */
 /* out[c][i] = (2u - 1) * bounds[i], u = unit(rng(rng_keys[c], rng_stream, i)), i < p: freshly initialised parameter vectors
  * (nn.Linear default init with bounds[i] = 1/sqrt(fan_in)) keyed by the chains' counter-RNG keys.  rng_stream 10 reproduces

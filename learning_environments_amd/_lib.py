@@ -282,6 +282,11 @@ SIGNATURES = {
                                 [_P(PpoTapes), _i64, _vp, C.c_size_t, _P(PpoOut), _vp]),
     "lenv_ppo_icm_inner_loop_segment": (C.c_int, [_P(PpoCfg), _i32, _i32, C.c_double, C.c_double, C.c_double, _P(IcmIo)] + [_vp] * 6 +
                                         [_P(PpoTapes), _i64, _vp, C.c_size_t, _P(PpoOut), _i32, _i32, _vp, _vp]),
+    "lenv_se_fit_num_params": (_i64, [_P(MlpDesc)] * 3),
+    "lenv_se_fit_lds_bytes": (_i64, [_P(MlpDesc)] * 3 + [_i32]),
+    "lenv_se_fit_workspace_bytes": (_i64, [_P(MlpDesc)] * 3 + [_i32, _i64]),
+    "lenv_se_fit_population": (C.c_int, [_P(MlpDesc)] * 3 + [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _i64, _f64, _f64, _f64, _f64, _vp, _vp, _i64,
+                                         _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "lenv_nes_worker_best": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "lenv_nes_worker_best_multi": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "lenv_nes_draw": (C.c_int, [C.c_uint64, C.c_uint64] + _NES_DRAW_TAIL),

@@ -228,7 +228,8 @@ enum { STREAM_EPS = 0, STREAM_ACTION = 1, STREAM_REPLAY = 2, STREAM_TRAIN_RESET 
        STREAM_NES_EPS = 9, STREAM_AGENT_INIT = 10,
        STREAM_VARY_HP = 11,     // host side only (agents/vary.py): the four hyper-parameter draws of a *_vary agent
        STREAM_ICM_INIT = 12,    // fresh ICMModel parameters of an ICM agent (lenv_chain_uniform_init)
-       STREAM_PPO_ACT_NOISE = 13, STREAM_PPO_TEST_NOISE = 14 };   // PPO: the Normal draw of actor_old.forward while training / testing
+       STREAM_PPO_ACT_NOISE = 13, STREAM_PPO_TEST_NOISE = 14,     // PPO: the Normal draw of actor_old.forward while training / testing
+       STREAM_SE_FIT_BATCH = 15 };   // supervised SE fit (se_fit.hip): the minibatch rows of a step, drawn with replacement
 
 // natural log, same sequence as the oracle's orc_log (fdlibm scheme, fma Horner); used by the counter-mode Box-Muller
 __device__ __forceinline__ double det_log(double x)

@@ -137,6 +137,67 @@ def se_step_population_vec(descs, theta, eps, worker, sign, state, action, repea
     return ns, r, d
 
 
+def se_fit_num_params(descs):
+    """P of lenv_se_fit_population: the SE theta layout state | reward | done (host only)."""
+    sn, rn, dn = descs
+    n = int(_lib.lib().lenv_se_fit_num_params(C.byref(sn), C.byref(rn), C.byref(dn)))
+    _lib.check(n if n < 0 else 0, "lenv_se_fit_num_params")
+    return n
+
+
+def se_fit_population(descs, theta, x, y_state, y_reward, y_done, batch_size, steps, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, rng_keys=None,
+                      batch_idx=None, step_begin=0, adam_m=None, adam_v=None, steps_per_launch=None):
+    """Supervised fit of a population of VirtualEnvs (lenv_se_fit_population): model m takes the Adam steps step_begin .. step_begin+steps-1 on
+    F.mse_loss of its three nets over minibatches of `batch_size` rows of (x [N,in], y_state [N,S], y_reward [N], y_done [N]).  theta
+    [models,P] are the start parameters (not modified); moments that are not given start at zero.  The rows of a step come from rng_keys
+    (int64 / uint64 [models], counter mode) or from batch_idx (int32 [models,steps,batch_size], tape mode): exactly one of the two.
+    steps_per_launch splits a long fit into consecutive launches that hand the moments on (the same bits).  Returns dict(theta, adam_m, adam_v,
+    loss [models,steps,3] = the three losses before each step)."""
+    dev = require_device()
+    sn, rn, dn = descs
+    P = se_fit_num_params(descs)
+    if theta.dim() != 2 or theta.shape[1] != P:
+        raise ValueError("theta must be [models,%d]" % P)
+    models, steps, batch_size, step_begin = theta.shape[0], int(steps), int(batch_size), int(step_begin)
+    N = x.shape[0]
+    for t, n, shape in ((theta, "theta", (models, P)), (x, "x", (N, sn.in_dim)), (y_state, "y_state", (N, sn.out_dim)), (y_reward, "y_reward", (N,)),
+                        (y_done, "y_done", (N,)), (adam_m, "adam_m", (models, P)), (adam_v, "adam_v", (models, P))):
+        if t is not None and tuple(_chk(t, torch.float32, n).shape) != shape:
+            raise ValueError("%s must be %s" % (n, list(shape)))
+    if (rng_keys is None) == (batch_idx is None):
+        raise ValueError("exactly one of rng_keys / batch_idx")
+    if rng_keys is not None:
+        if not rng_keys.is_cuda or rng_keys.dtype not in (torch.int64, torch.uint64) or not rng_keys.is_contiguous() or rng_keys.numel() != models:
+            raise ValueError("rng_keys must be a contiguous 64-bit integer CUDA tensor [models]")
+    else:
+        if tuple(_chk(batch_idx, torch.int32, "batch_idx").shape) != (models, steps, batch_size):
+            raise ValueError("batch_idx must be [models,steps,batch_size]")
+        if batch_idx.numel() and N > 0 and (int(batch_idx.min()) < 0 or int(batch_idx.max()) >= N):
+            raise ValueError("batch_idx holds a row outside the data set")
+    L = _lib.lib()
+    ws_bytes = int(L.lenv_se_fit_workspace_bytes(C.byref(sn), C.byref(rn), C.byref(dn), batch_size, models))
+    _lib.check(ws_bytes if ws_bytes < 0 else 0, "lenv_se_fit_workspace_bytes")
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if ws_bytes else None
+    out = dict(theta=theta.clone(), adam_m=torch.zeros_like(theta) if adam_m is None else adam_m.clone(),
+               adam_v=torch.zeros_like(theta) if adam_v is None else adam_v.clone())
+    if steps < 0 or (steps_per_launch is not None and int(steps_per_launch) < 1):
+        raise ValueError("steps must not be negative and steps_per_launch must be positive")
+    per = max(steps, 1) if steps_per_launch is None else int(steps_per_launch)      # steps == 0: one call that returns without a launch
+    losses = []
+    for s0 in range(0, max(steps, 1), per):
+        n = min(per, steps - s0)
+        loss = torch.zeros((models, n, 3), dtype=torch.float32, device=dev)
+        idx = batch_idx[:, s0:s0 + n].contiguous() if batch_idx is not None else None
+        rc = L.lenv_se_fit_population(C.byref(sn), C.byref(rn), C.byref(dn), _ptr(x), _ptr(y_state), _ptr(y_reward), _ptr(y_done), N, batch_size,
+                                      step_begin + s0, step_begin + s0 + n, float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                      _ptr(rng_keys), _ptr(idx), models, _ptr(out["theta"]), _ptr(out["adam_m"]), _ptr(out["adam_v"]), _ptr(loss),
+                                      _ptr(ws), ws_bytes, _stream())
+        _lib.check(rc, "lenv_se_fit_population")
+        losses.append(loss)
+    out["loss"] = losses[0] if len(losses) == 1 else torch.cat(losses, dim=1)
+    return out
+
+
 # observation words, fp64 state words and action width of the vector-state real envs (csrc/lenv_device.cuh); action width 0 = a discrete index
 REAL_ENV_DIMS = {_lib.ENV[k]: v for k, v in {"CartPole-v0": (4, 4, 0), "Acrobot-v1": (6, 4, 0), "MountainCar-v0": (2, 4, 0), "HalfCheetah-v3": (17, 17, 6),
                                                 "Pendulum-v0": (3, 2, 1), "MountainCarContinuous-v0": (2, 2, 1)}.items()}

@@ -772,6 +772,73 @@ def run_ql_test(name, agents=400, test_episodes=10, runs=7, seed=0):
     return out
 
 
+def run_se_fit(name, models=5, steps=9500, batch=64, rows=2000, runs=7, torch_models=None, seed=0):
+    """The supervised VirtualEnv fit at the published CartPole SE shape (6-128-{4,1,1}, leakyrelu): lenv_se_fit_population for `models` models
+    in one launch against the only route there was, an eager torch loop (three nn.Sequential, one torch.optim.Adam, F.mse_loss) fitting
+    `torch_models` of them one after the other on the device from the same data, initial weights and index tapes (None: all of them; 0: the
+    torch side is not run).  Host clock around a synchronise, a warm-up of each, then `runs` runs in alternation; medians and ranges."""
+    from learning_environments_amd import engine
+    from learning_environments_amd.experiments import mbrl_baseline as mb
+    from learning_environments_amd.envs.env_factory import EnvFactory
+    import numpy as np
+    dev = engine.require_device()
+    config = configs.with_vary(configs.cartpole_syn_env_ddqn(num_workers=1))
+    config["envs"]["CartPole-v0"]["hidden_size"] = 128
+    config["device"] = "cuda"
+    fac = EnvFactory(config)
+    venv = fac.generate_virtual_env()
+    x, y_state, y_reward, y_done = mb.rows_to_dataset(venv, mb.collect_transitions(fac.generate_real_env(), rows, seed=seed))
+    descs = venv.env.descs()
+    P = engine.se_fit_num_params(descs)
+    g = torch.Generator().manual_seed(seed)
+    theta0 = ((torch.rand((models, P), generator=g) * 2 - 1) * torch.from_numpy(mb._se_bounds(descs))).to(dev)
+    tape = torch.randint(0, rows, (models, steps, batch), generator=g, dtype=torch.int32).to(dev)
+    torch_models = models if torch_models is None else torch_models
+    last = {}
+
+    def kernel():
+        last["kernel"] = engine.se_fit_population(descs, theta0, x, y_state, y_reward, y_done, batch, steps, batch_idx=tape)
+
+    def eager():
+        ys = (y_state, y_reward.reshape(-1, 1), y_done.reshape(-1, 1))
+        finals, tails = [], []
+        for m in range(torch_models):
+            nets, off = [], 0
+            for d in descs:
+                net = torch.nn.Sequential(torch.nn.Linear(d.in_dim, d.hidden), torch.nn.LeakyReLU(), torch.nn.Linear(d.hidden, d.out_dim)).to(dev)
+                with torch.no_grad():
+                    for prm in net.parameters():
+                        prm.copy_(theta0[m, off:off + prm.numel()].reshape(prm.shape))
+                        off += prm.numel()
+                nets.append(net)
+            opt = torch.optim.Adam([p for n in nets for p in n.parameters()], lr=1e-3)
+            idx = tape[m].long()
+            for t in range(steps):
+                opt.zero_grad()
+                xb = x[idx[t]]
+                total = sum(torch.nn.functional.mse_loss(n(xb), y[idx[t]]) for n, y in zip(nets, ys))
+                total.backward()
+                opt.step()
+                if t >= steps - 10:
+                    tails.append(total.detach())
+            finals.append(torch.cat([p.detach().reshape(-1) for n in nets for p in n.parameters()]))
+        last["torch"], last["torch_loss"] = torch.stack(finals), torch.stack(tails).reshape(torch_models, -1).mean(dim=1)
+
+    forms = (("se_fit_population", kernel),) + ((("torch_eager", eager),) if torch_models else ())
+    med, times = _time_forms(forms, runs)
+    out = dict(config=name, models=models, torch_models=torch_models, steps=steps, batch=batch, rows=rows, params_per_model=P, runs_each=runs,
+               ms_median={k: 1e3 * v for k, v in med.items()}, ms_min={k: 1e3 * min(v) for k, v in times.items()},
+               ms_max={k: 1e3 * max(v) for k, v in times.items()}, ms_samples={k: [round(1e3 * x, 3) for x in v] for k, v in times.items()},
+               us_per_step_kernel=1e6 * med["se_fit_population"] / steps,
+               final_loss_kernel=[float(v) for v in last["kernel"]["loss"][:, -10:].sum(dim=2).mean(dim=1).cpu()][:5])
+    if torch_models:
+        out["torch_over_kernel_per_model"] = (med["torch_eager"] / torch_models) / (med["se_fit_population"] / models)
+        out["final_loss_torch"] = [float(v) for v in last["torch_loss"].cpu()]
+        out["max_abs_theta_diff_to_torch"] = float((last["kernel"]["theta"][:torch_models] - last["torch"]).abs().max())
+    print(json.dumps(out))
+    return out
+
+
 def _frac(model):
     def f(cfg, st, dt):
         nbytes, flops = model(cfg, st)
@@ -1094,6 +1161,12 @@ if __name__ == "__main__":
                                                                       gumbel_softmax_hard=False, action_std=0.1, policy_delay=2, init_episodes=10))
     if "ql_test" in which:
         run_ql_test("Cliff, 400 Q-tables x 10 test episodes of up to 50 steps: lenv_ql_rn_inner_loop (train_episodes 0) / ql_test_population")
+    if "se_fit" in which:
+        # the supervised (MBRL baseline) fit: 5 models x 9 500 Adam steps at the CartPole SE shape in one launch against an eager torch loop over
+        # the models, then 256 models (kernel alone: the eager loop would take 51 x its 5-model time)
+        kw = dict(steps=9500, runs=7)
+        run_se_fit("CartPole-v0 SE 6-128-{4,1,1}, 5 models x %d Adam steps, batch 64: se_fit_population / eager torch" % kw["steps"], models=5, **kw)
+        run_se_fit("CartPole-v0 SE 6-128-{4,1,1}, 256 models x %d Adam steps, batch 64: se_fit_population" % kw["steps"], models=256, torch_models=0, **kw)
     if "5" in which:
         c = configs.fixed_work(configs.halfcheetah_reward_env_td3(32), 3)
         c["agents"]["td3"]["init_episodes"] = 1
